@@ -1,6 +1,6 @@
 """Benchmark: MCTS simulations/sec of the fused batched search (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W]                       # N=1
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]   # N=1
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W             # N>1, one rank per GPU
     python bench.py --gpus N ...                                           # N>1 without a launcher:
@@ -18,9 +18,19 @@ One step = one mzh_search launch over every root on the rank (root inference + S
 MLP, backup} + play policy), followed by one RCCL all_gather of every root's result (visit
 histogram, action, fp64 root Q: what run_mcts returns; north_star's only exchange).  Inputs are resident in HBM before timing starts.
 
-Rank 0 prints ONE JSON line (contract in the task statement) including
+A plain run does what the headline figure needs and no more: set-up, one checked launch, the warm-up
+launches, the `--steps` timed ones, then the result line.  `--dump-outputs DIR` also writes what the
+last timed step computed (the arrays a caller of the search receives) as DIR/<name>.npy; the inputs
+depend only on the arguments, so two builds can be compared output for output.  `--full` adds the
+measurements that take runs of their own: the CPU baseline, the caller-bounds (minmax_in) leg and the
+select / backup (replay) leg; without it those fields of the line are null.
+
+Rank 0 prints ONE JSON line including
   roofline        the fused search kernel (fp32-MFMA bound; achieved = algorithmic matmul FLOPs per
-                  launch / mean launch time from HIP events on the launch stream);
+                  launch / median launch time from HIP events on the timed launches);
+ with --full:
+  roofline.with_minmax_in  the instantiation training / acting searches launch, timed A B B A against
+                  the plain one;
   roofline.tree   select / expand / backup (HBM-bound): the same kernel's replay instantiation --
                   identical tree code with the network outputs read from HBM instead of computed --
                   timed live on the same roots; algorithmic tree bytes from the
@@ -135,6 +145,11 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=3)
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements beside the headline: the CPU baseline, the caller-bounds "
+                        "(minmax_in) leg and the select/backup (replay) leg (each still has its --no-... switch)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write the last timed step's search outputs to DIR/<name>.npy (float32 / float64)")
     p.add_argument("--config", type=int, choices=sorted(CONFIGS), default=2,
                    help="BASELINE.json configs[K]; the global batch is sharded over the ranks (strong scaling)")
     p.add_argument("--roots-per-gpu", type=int, default=None,
@@ -459,10 +474,51 @@ def waves_per_simd(plan, B):
     return min(2, max(1, -(-waves // 1024)))
 
 
+DUMP_BYTES_MAX = 64 * 2 ** 20
+
+
+def dump_outputs(path, out, gathered, write):
+    """--dump-outputs: the search outputs of the last timed step as <path>/<name>.npy -- this rank's
+    visits, root_q, minmax, extra_ties, action, pi, latent (entries past latent_len zeroed: the kernel
+    leaves them unwritten), latent_len and sel_steps, and at N > 1 the exchanged global_visits /
+    global_action / global_root_q.  fp64 arrays stay float64, fp32 float32, integer ones become float64
+    (exact).  Above DUMP_BYTES_MAX in all, the same seeded sample of roots is kept of every array and
+    its indices written as sample_rows.npy."""
+    arrs = {k: v.detach().cpu().numpy() for k, v in out.items() if isinstance(v, torch.Tensor)}
+    if "latent" in arrs and "latent_len" in arrs:
+        arrs["latent"] = np.where(np.arange(arrs["latent"].shape[1])[None, :] < arrs["latent_len"][:, None],
+                                  arrs["latent"], 0)
+    for k, v in (gathered or {}).items():
+        arrs["global_" + k] = v.detach().cpu().numpy()
+    arrs = {k: v if v.dtype in (np.float32, np.float64) else v.astype(np.float64) for k, v in arrs.items()}
+    if not write:
+        return
+    total = sum(v.nbytes for v in arrs.values())
+    if total > DUMP_BYTES_MAX:
+        # rows are roots in every array: keep the same fraction of each (the sample's own indices included)
+        frac = DUMP_BYTES_MAX / (total + 16 * max(len(v) for v in arrs.values()))
+        pick = {}
+        for k in sorted(arrs):
+            n = len(arrs[k])
+            if n not in pick:
+                pick[n] = np.sort(np.random.default_rng(0).choice(n, size=int(n * frac), replace=False))
+            arrs[k] = arrs[k][pick[n]]
+        arrs["sample_rows"] = pick[len(out["visits"])].astype(np.float64)
+        if gathered:
+            arrs["global_sample_rows"] = pick[len(gathered["visits"])].astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrs.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(v))
+
+
 def main():
     a = parse()
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if not a.full:  # a plain run: the headline's timed steps only
+        a.no_cpu_baseline = a.no_minmax_leg = a.no_tree = True
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(relaunch_with_ranks(a.gpus))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -595,6 +651,10 @@ def main():
         gather_ms = float(np.mean([s_.elapsed_time(e_) for s_, e_ in gp]))
     elif gather:
         gather_ms = float(np.mean([evs[k][1].elapsed_time(gevs[k]) for k in range(a.steps)]))
+
+    if a.dump_outputs:
+        # every rank takes part in the exchange; rank 0 writes
+        dump_outputs(a.dump_outputs, out, mdist.gather_results(out, GB, world) if gather else None, rank == 0)
 
     # the instantiation training and acting searches run: the same roots with caller-given MinMaxStats
     # bounds (run_mcts passes the MCTS instance's persistent bounds; fresh ones here), timed apart

@@ -238,3 +238,60 @@ def test_gpus_8_driver_form_dry_run():
     assert rec["dist"]["roots_per_rank"] == [8192] * 8
     assert sorted(d["local_rank"] for d in rec["dist"]["devices"]) == list(range(8))
     assert [d["rank"] for d in rec["dist"]["devices"]] == list(range(8))
+
+
+def test_plain_run_is_the_headline_only(monkeypatch):
+    """without --full the legs beside the headline are off (their --no-... switches set); with it they
+    run unless switched off one by one"""
+    import bench
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "2"])
+    a = bench.parse()
+    assert not a.full and a.dump_outputs is None and a.steps == 4 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-tree", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.no_tree and not a.no_cpu_baseline and not a.no_minmax_leg and a.dump_outputs == "d"
+
+
+def test_dump_outputs_arrays(tmp_path):
+    """--dump-outputs: every tensor of the search outputs as float32 / float64 .npy (integers exact in
+    float64, unwritten latent entries zeroed, non-tensors left out); above the byte limit the same seeded
+    rows of every array, their indices beside them, the same from run to run"""
+    import numpy as np
+    import torch
+
+    import bench
+
+    B, S = 1000, 5
+    g = torch.Generator().manual_seed(0)
+    out = dict(visits=torch.randint(0, S, (B, 6), dtype=torch.int32, generator=g),
+               root_q=torch.randn(B, dtype=torch.float64, generator=g),
+               latent=torch.randint(1, 6, (B, S + 1), dtype=torch.int32, generator=g),
+               latent_len=torch.randint(0, S + 2, (B,), dtype=torch.int32, generator=g), _plan={"kernel": "k"})
+    bench.dump_outputs(str(tmp_path / "a"), out, None, True)
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert sorted(got) == ["latent", "latent_len", "root_q", "visits"]
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert np.array_equal(got["visits"], out["visits"].numpy()) and np.array_equal(got["root_q"], out["root_q"].numpy())
+    keep = np.arange(S + 1)[None, :] < out["latent_len"].numpy()[:, None]
+    assert np.array_equal(got["latent"], np.where(keep, out["latent"].numpy(), 0))
+    bench.dump_outputs(str(tmp_path / "none"), out, None, False)  # not the writing rank
+    assert not (tmp_path / "none").exists()
+
+    glob = dict(visits=torch.zeros((4 * B, 6), dtype=torch.int32), action=torch.ones(4 * B, dtype=torch.int32))
+    full = sum(v.nbytes for v in got.values()) + 4 * B * 7 * 8
+    old = bench.DUMP_BYTES_MAX
+    try:
+        bench.DUMP_BYTES_MAX = full // 3
+        for d in ("b", "c"):
+            bench.dump_outputs(str(tmp_path / d), out, glob, True)
+    finally:
+        bench.DUMP_BYTES_MAX = old
+    b = {f[:-4]: np.load(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")}
+    c = {f[:-4]: np.load(tmp_path / "c" / f) for f in os.listdir(tmp_path / "c")}
+    assert sorted(b) == sorted(c) and all(np.array_equal(b[k], c[k]) for k in b)
+    assert 0 < sum(v.nbytes for v in b.values()) <= full // 3
+    rows = b["sample_rows"].astype(np.int64)
+    assert len(rows) == len(b["visits"]) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(b["visits"], got["visits"][rows]) and np.array_equal(b["root_q"], got["root_q"][rows])
+    assert len(b["global_sample_rows"]) == len(b["global_visits"]) == len(b["global_action"])

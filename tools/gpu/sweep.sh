@@ -6,7 +6,7 @@ set -e
 mkdir -p gpurun_out
 for spec in "$@"; do
   T=${spec%%:*}
-  A=${spec#*:}
+  A="--full ${spec#*:}"  # the select/backup and caller-bounds legs are part of every line recorded here
   TAG=$T BENCH_ARGS="$A" bash tools/prof.sh > gpurun_out/sweep_$T.log 2>&1 || { tail -5 gpurun_out/sweep_$T.log; exit 1; }
   python tools/traffic.py gpurun_out $T --traffic-json gpurun_out/traffic_latest.json > gpurun_out/traffic_$T.json
   timeout -k 10 300 python bench.py $A --no-cpu-baseline --traffic-json gpurun_out/traffic_latest.json > gpurun_out/bench_$T.json 2> gpurun_out/bench_$T.err

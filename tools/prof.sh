@@ -8,7 +8,7 @@ R=$PWD
 T=${TAG:-run}
 export TMPDIR=/tmp
 mkdir -p gpurun_out
-B="$R/bench.py --steps 10 --warmup 2 --no-cpu-baseline ${BENCH_ARGS}"
+B="$R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline ${BENCH_ARGS}"
 # the same command un-profiled first (same box and build: the HIP-event time the profile is compared with)
 timeout -k 10 300 python3 $B > $R/gpurun_out/prof_${T}_plain.json 2> $R/gpurun_out/prof_${T}_plain.err
 cd /tmp
