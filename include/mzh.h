@@ -324,6 +324,56 @@ int mzh_replay_sample(const mzh_replay_args* args, mzh_stream stream);
 int mzh_replay_set_priorities(float* prio, int64_t size, const int64_t* indx, const float* values, int m,
                               int32_t* status, mzh_stream stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Episode ingest: the record of one batched lockstep self-play run (BatchedSelfPlay.play with
+ * record_obs, T recorded steps of B envs) into the replay ring, for TD_return=True.  Replaces, per
+ * episode, compute_n_step_returns (utils.py:28-69), the priorities |return - root Q| in float32
+ * (Muzero.py:188-205), organise_transitions (Muzero.py:276-323), the filter of the training loop (only
+ * episodes whose last return is > 0 enter, Muzero.py:98) and Buffer.add (buffer.py:62-77), with the same
+ * bits as that host path.  Two launches: a one-workgroup filter + scan over the envs, then one workgroup
+ * per entering episode writing its rows.
+ *   B, T, d_state, U, A : envs, recorded steps, observation width, unroll_n_steps, actions
+ *   n_step              : n_TD_step
+ *   size, ptr           : the ring's capacity in rows and Buffer.ptr before the call (0 <= ptr < size)
+ *   obs [T][B][d_state] f32, action [T][B] i32, reward [T][B] f64, pi [T][B][A] f64, root_q [T][B] f64,
+ *   steps [B] i32       : the record; env b played steps[b] in [1, T] steps, and what the record holds at
+ *                         t >= steps[b] is never used
+ *   pad_action [B] i64  : organise_transitions' np.random.randint(0, n_action) of each episode (drawn by
+ *                         the caller for every env, entering or not, as the host path draws them)
+ *   disc_pow [n_step+1] f64 : discount**i as the caller's Python computes it
+ *   states [size][d_state] f32, rwds [size][U] f32, actions [size][U] i64, pi_probs [size][U][A] f32,
+ *   returns [size][U] f32, prio [size] f32 : the ring (in/out)
+ *   first [B] i64       : workspace (an entering episode's position in the sequential row order, else -1)
+ *   status [2] i64      : device-written (out): [1] = G, the rows of the entering episodes in env order;
+ *                         row g of them lands at (ptr + g) % size, and rows g < G - size are not written
+ *                         (a later row of the same call overwrites them in the sequential order);
+ *                         [0] = 0 written, 1 = an entering episode is longer than the ring (the
+ *                         reference's assert n <= size), 2 = a steps[b] outside [1, T]: nothing written
+ * The caller advances ptr by G modulo size after reading status.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct mzh_ingest_args {
+  int32_t B, T, d_state, U, A, n_step;
+  int64_t size, ptr;
+  const float* obs;
+  const int32_t* action;
+  const double* reward;
+  const double* pi;
+  const double* root_q;
+  const int32_t* steps;
+  const int64_t* pad_action;
+  const double* disc_pow;
+  float* states;
+  float* rwds;
+  int64_t* actions;
+  float* pi_probs;
+  float* returns;
+  float* prio;
+  int64_t* first;
+  int64_t* status;
+} mzh_ingest_args;
+
+int mzh_episode_ingest(const mzh_ingest_args* args, mzh_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

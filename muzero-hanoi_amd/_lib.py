@@ -77,6 +77,15 @@ class ReplayArgs(ctypes.Structure):
                 ("out_actions", _vp), ("out_pi", _vp), ("out_returns", _vp), ("status", _vp)]
 
 
+class IngestArgs(ctypes.Structure):
+    """mirror of struct mzh_ingest_args (include/mzh.h)"""
+    _fields_ = [("B", _i32), ("T", _i32), ("d_state", _i32), ("U", _i32), ("A", _i32), ("n_step", _i32),
+                ("size", ctypes.c_int64), ("ptr", ctypes.c_int64),
+                ("obs", _vp), ("action", _vp), ("reward", _vp), ("pi", _vp), ("root_q", _vp), ("steps", _vp),
+                ("pad_action", _vp), ("disc_pow", _vp), ("states", _vp), ("rwds", _vp), ("actions", _vp),
+                ("pi_probs", _vp), ("returns", _vp), ("prio", _vp), ("first", _vp), ("status", _vp)]
+
+
 # name -> (restype, argtypes); every symbol include/mzh.h declares
 SIGNATURES = {
     "mzh_abi_version": (ctypes.c_int, []),
@@ -107,6 +116,7 @@ SIGNATURES = {
     "mzh_train_update": (ctypes.c_int, [ctypes.POINTER(TrainArgs), _vp]),
     "mzh_replay_sample": (ctypes.c_int, [ctypes.POINTER(ReplayArgs), _vp]),
     "mzh_replay_set_priorities": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, ctypes.c_int, _vp, _vp]),
+    "mzh_episode_ingest": (ctypes.c_int, [ctypes.POINTER(IngestArgs), _vp]),
 }
 
 _lib = None

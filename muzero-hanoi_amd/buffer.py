@@ -48,6 +48,7 @@ class Buffer:
             self._prio = self._dev_replay.prio
         else:
             self._prio = np.zeros((size,), dtype=np.float32)  # host: drives np.random.choice
+        self._prio_shadow = None  # add_episodes' device copy of the priorities it writes (host mode)
         self.ptr = 0
         self.is_full = False
 
@@ -89,6 +90,73 @@ class Buffer:
         if self.ptr + n >= self.size:
             self.is_full = True
         self.ptr = (self.ptr + n) % self.size
+
+    def add_episodes(self, res, *, discount, n_step, pad_action):
+        """Every successful episode of a BatchedSelfPlay.play(record_obs=True) result into the ring in one
+        call, on the device (csrc/mzh_ingest.hip): the n-step TD returns, the priorities, the unroll targets,
+        the `returns[-1, 0] > 0` filter and `add` per episode in env order, with the same bits as
+        selfplay.episode_records + add.  pad_action: organise_transitions' padding action of every env
+        (selfplay.ingest_records draws them).  Returns the number of rows added.  An entering episode
+        longer than the ring is add's AssertionError, raised before anything is written."""
+        from . import _lib
+
+        if self.dev.type != "cuda":
+            raise ValueError("Buffer.add_episodes runs on the device: it needs a GPU buffer")
+        want = (("obs", torch.float32, 3), ("action", torch.int32, 2), ("reward", torch.float64, 2),
+                ("pi", torch.float64, 3), ("root_q", torch.float64, 2), ("steps", torch.int32, 1))
+        rec = {}
+        for k, dt, nd in want:
+            t = res[k]
+            if t.dtype != dt or t.dim() != nd or t.device.type != "cuda":
+                raise ValueError(f"add_episodes: res[{k!r}] must be a {nd}-d {dt} device tensor "
+                                 "(BatchedSelfPlay.play(record_obs=True))")
+            rec[k] = t.contiguous()
+        T, B = rec["action"].shape
+        if rec["obs"].shape != (T, B, self.d_state) or rec["pi"].shape != (T, B, self.n_action) \
+                or rec["reward"].shape != (T, B) or rec["root_q"].shape != (T, B) or rec["steps"].shape != (B,):
+            raise ValueError("add_episodes: the record's shapes do not match each other or the buffer")
+        n_step = int(n_step)
+        if n_step < 1:
+            raise ValueError("the n_step return must be greater than zero")
+        pad_np = np.asarray(pad_action, np.int64).reshape(-1)
+        if pad_np.shape[0] != B:
+            raise ValueError(f"add_episodes: {pad_np.shape[0]} padding actions for {B} episodes")
+        dev = self.dev
+        pad = torch.from_numpy(pad_np).to(dev)
+        disc_pow = torch.tensor([discount ** i for i in range(n_step + 1)], dtype=torch.float64).to(dev)
+        first = torch.empty(B, dtype=torch.int64, device=dev)
+        status = torch.empty(2, dtype=torch.int64, device=dev)
+        if self.device_sampling:
+            prio = self._prio  # stream order puts the write after any pending draw's reads
+        else:
+            if self._prio_shadow is None:
+                self._prio_shadow = torch.zeros((self.size,), dtype=torch.float32, device=dev)
+            prio = self._prio_shadow
+        a = _lib.IngestArgs()
+        a.B, a.T, a.d_state, a.U, a.A, a.n_step = B, T, self.d_state, self.unroll_n_steps, self.n_action, n_step
+        a.size, a.ptr = self.size, self.ptr
+        a.obs, a.action, a.reward = rec["obs"].data_ptr(), rec["action"].data_ptr(), rec["reward"].data_ptr()
+        a.pi, a.root_q, a.steps = rec["pi"].data_ptr(), rec["root_q"].data_ptr(), rec["steps"].data_ptr()
+        a.pad_action, a.disc_pow = pad.data_ptr(), disc_pow.data_ptr()
+        a.states, a.rwds, a.actions = self.states.data_ptr(), self.rwds.data_ptr(), self.actions.data_ptr()
+        a.pi_probs, a.returns, a.prio = self.pi_probs.data_ptr(), self.mc_returns.data_ptr(), prio.data_ptr()
+        a.first, a.status = first.data_ptr(), status.data_ptr()
+        _lib.check(_lib.lib().mzh_episode_ingest(ctypes.byref(a), _lib.stream_handle(dev)), "mzh_episode_ingest")
+        code, G = (int(x) for x in status.cpu())  # the one synchronisation of the call
+        if code == 1:  # an entering episode with n > size (buffer.py:62-77's assert); nothing was written
+            raise AssertionError("an episode is longer than the buffer")
+        if code != 0:
+            raise ValueError("add_episodes: res['steps'] has an entry outside [1, recorded steps]")
+        if not self.device_sampling and G > 0:  # the written ring range of the shadow into the host priorities
+            lo, cnt = (self.ptr + max(0, G - self.size)) % self.size, min(G, self.size)
+            head = min(cnt, self.size - lo)
+            self._prio[lo:lo + head] = prio[lo:lo + head].cpu().numpy()
+            if head < cnt:
+                self._prio[:cnt - head] = prio[:cnt - head].cpu().numpy()
+        if self.ptr + G >= self.size:
+            self.is_full = True
+        self.ptr = (self.ptr + G) % self.size
+        return G
 
     def _gather(self, indx):
         i = torch.as_tensor(indx, dtype=torch.int64).to(self.dev)

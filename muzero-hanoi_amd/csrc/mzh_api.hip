@@ -949,3 +949,20 @@ extern "C" int mzh_replay_set_priorities(float* prio, int64_t size, const int64_
   hipError_t e = mzr_launch_set_priorities(prio, size, indx, values, m, status, (hipStream_t)stream);
   return e == hipSuccess ? MZH_OK : hip_fail(e, "replay set_priorities launch");
 }
+
+extern "C" int mzh_episode_ingest(const mzh_ingest_args* a, mzh_stream stream) {
+  if (!a) return fail(MZH_ERR_ARG, "episode_ingest: null args");
+  if (a->B < 1 || a->T < 1 || a->d_state < 1 || a->U < 1 || a->A < 1 || a->n_step < 1 || a->size < 1)
+    return fail(MZH_ERR_ARG, "episode_ingest: bad B=%d T=%d d_state=%d U=%d A=%d n_step=%d size=%lld (each >= 1)", a->B,
+                a->T, a->d_state, a->U, a->A, a->n_step, (long long)a->size);
+  // the writer indexes a pass of 1,024 rows of each array with 32-bit element counts
+  if (a->d_state > (1 << 20) || (int64_t)a->U * a->A > (1 << 20))
+    return fail(MZH_ERR_ARG, "episode_ingest: d_state=%d / U*A=%lld above 2^20", a->d_state, (long long)a->U * a->A);
+  if (a->ptr < 0 || a->ptr >= a->size)
+    return fail(MZH_ERR_ARG, "episode_ingest: ptr=%lld outside [0, size=%lld)", (long long)a->ptr, (long long)a->size);
+  if (!a->obs || !a->action || !a->reward || !a->pi || !a->root_q || !a->steps || !a->pad_action || !a->disc_pow ||
+      !a->states || !a->rwds || !a->actions || !a->pi_probs || !a->returns || !a->prio || !a->first || !a->status)
+    return fail(MZH_ERR_ARG, "episode_ingest: null pointer");
+  hipError_t e = mzi_launch_ingest(*a, (hipStream_t)stream);
+  return e == hipSuccess ? MZH_OK : hip_fail(e, "episode ingest launch");
+}

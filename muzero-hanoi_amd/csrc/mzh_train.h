@@ -71,3 +71,6 @@ hipError_t mzt_launch_transpose(const float* W, float* WT, int out, int in, int 
 hipError_t mzr_launch_sample(const mzh_replay_args& a, hipStream_t stream);
 hipError_t mzr_launch_set_priorities(float* prio, long long size, const int64_t* idx, const float* val, int m,
                                      int32_t* status, hipStream_t stream);
+
+// episode ingest (mzh_ingest.hip): the filter + scan launch and the ring writer launch
+hipError_t mzi_launch_ingest(const mzh_ingest_args& a, hipStream_t stream);

@@ -7,7 +7,9 @@ Same constructor and `training_loop(n_loops, min_replay_size, print_acc)` as the
     n_ep_x_loop episodes of a loop play in lockstep -- one search launch and one env-kernel launch
     per step for all of them (selfplay.BatchedSelfPlay), each episode an agent whose MinMaxStats
     starts from the MCTS instance's, then the reference's per-episode bookkeeping
-    (selfplay.episode_records) and buffer filter.  With n_ep_x_loop > 1 that is NOT the
+    (selfplay.episode_records) and buffer filter -- or, with ingest="device", that bookkeeping, the
+    filter and the buffer writes as one device call on the play's record (selfplay.ingest_records:
+    the same buffer, priorities and RNG stream).  With n_ep_x_loop > 1 that is NOT the
     reference's schedule (one MinMaxStats chain through the episodes in order, Muzero.py:55; other
     per-step draw interleaving): a RuntimeWarning says so, and "sequential" (the default) is the
     parity mode;
@@ -31,16 +33,29 @@ from torch.autograd.graph import increment_version
 from .buffer import Buffer
 from .mcts import MCTS
 from .networks import MuZeroNet
-from .selfplay import BatchedSelfPlay, episode_records, play_game
+from .selfplay import BatchedSelfPlay, episode_records, ingest_records, play_game
 from .utils import adjust_temperature, organise_transitions
 
 
 class Muzero:
     def __init__(self, env, s_space_size, n_action, discount, dirichlet_alpha, n_mcts_simulations, unroll_n_steps,
                  batch_s, TD_return, n_TD_step, lr, buffer_size, priority_replay, device, n_ep_x_loop=1,
-                 n_update_x_loop=1, update_impl="torch", selfplay="sequential", device_sampling=None):
+                 n_update_x_loop=1, update_impl="torch", selfplay="sequential", device_sampling=None, ingest="host"):
         self.dev = device
         self.env = env
+        # ingest (not in the reference's signature): "host" = the reference's per-episode bookkeeping and
+        # Buffer.add on the host; "device" = the batched record into the ring on the device
+        # (Buffer.add_episodes), n-step TD returns only (Monte-Carlo returns stay on the host path)
+        if ingest not in ("host", "device"):
+            raise ValueError(f"ingest must be 'host' or 'device', not {ingest!r}")
+        if ingest == "device":
+            if selfplay != "batched":
+                raise ValueError("Muzero(ingest='device') ingests a batched play's record: it needs selfplay='batched'")
+            if not TD_return:
+                raise ValueError("Muzero(ingest='device') implements the n-step TD returns: it needs TD_return=True")
+            if torch.device(device).type != "cuda":
+                raise ValueError("Muzero(ingest='device') needs a GPU device")
+        self.ingest = ingest
         self.n_ep_x_loop = n_ep_x_loop  # episodes collected per training loop
         self.discount = discount
         self.n_action = n_action
@@ -88,7 +103,11 @@ class Muzero:
         value_loss, rwd_loss, pi_loss = [], [], []
         for n in range(1, n_loops):
             ep_steps = []
-            if self.selfplay == "batched":
+            if self.ingest == "device":  # played, filtered and written to the buffer on the device
+                ep_steps = [int(s) for s in self._play_games(self.n_ep_x_loop, episode=n * self.n_ep_x_loop,
+                                                             deterministic=False)]
+                episodes = ()
+            elif self.selfplay == "batched":
                 episodes = self._play_games(self.n_ep_x_loop, episode=n * self.n_ep_x_loop, deterministic=False)
             else:
                 episodes = (self._play_game(episode=n * self.n_ep_x_loop, deterministic=False)
@@ -129,7 +148,8 @@ class Muzero:
         """n_games episodes from env.reset()'s start in lockstep (BatchedSelfPlay): each one an
         agent whose MinMaxStats starts from this MCTS instance's; afterwards the instance keeps
         the union (max of the maxima, min of the minima).  Draws come from the global NumPy stream
-        (for n_games = 1 exactly the draws of _play_game).  Returns _play_game's tuple per episode."""
+        (for n_games = 1 exactly the draws of _play_game).  Returns _play_game's tuple per episode; with
+        ingest="device" the episodes go into the buffer here and only their step counts come back."""
         env, mm = self.env, self.mcts.min_max_stats
         sp = BatchedSelfPlay(self.networks, env.discs, env.max_steps, int(self.mcts.n_simulations),
                              discount=self.discount, dirichlet_alpha=self.mcts.root_dirichlet_alpha,
@@ -140,6 +160,9 @@ class Muzero:
                       minmax=[[mm.maximum, mm.minimum]] * n_games, record_obs=True)
         fin = res["minmax"].cpu().numpy()
         mm.maximum, mm.minimum = float(fin[:, 0].max()), float(fin[:, 1].min())
+        if self.ingest == "device":
+            return ingest_records(res, self.buffer, discount=self.discount, n_step=self.n_step,
+                                  unroll_n_steps=self.unroll_n_steps, n_action=self.n_action)
         return episode_records(res, discount=self.discount, TD_return=self.TD_return, n_step=self.n_step,
                                unroll_n_steps=self.unroll_n_steps, n_action=self.n_action)
 

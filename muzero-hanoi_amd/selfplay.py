@@ -10,6 +10,8 @@ BatchedSelfPlay    B envs resident on the GPU (HanoiBatch) stepping with search-
                    (minmax_out -> minmax_in), starting from the `minmax` handed in.
 episode_records    the reference's per-episode bookkeeping (returns, priorities,
                    organise_transitions) of every env of a BatchedSelfPlay run.
+ingest_records     that bookkeeping, the success filter and Buffer.add for every env in one device call
+                   (Buffer.add_episodes, csrc/mzh_ingest.hip): the same ring, priorities and RNG stream.
 evaluate           acting_ablations.get_results (acting_experiments/acting_ablations.py:72-128)
                    and illegal_move_rate (illegal_move_rate_comparison.py:27-50) over episodes:
                    error = steps - hanoi_solver(start), per-episode illegal-move rates (mean and
@@ -226,6 +228,20 @@ def episode_records(res, *, discount=0.8, TD_return=True, n_step=10, unroll_n_st
                                             n_step=n_step, unroll_n_steps=unroll_n_steps, n_action=n_action)
         out.append((T,) + tuple(trans[:4]) + (trans[4], priorities))
     return out
+
+
+def ingest_records(res, buffer, *, discount=0.8, n_step=10, unroll_n_steps=5, n_action=6):
+    """episode_records + the `returns[-1, 0] > 0` filter + Buffer.add for every env of a
+    BatchedSelfPlay.play(record_obs=True) result, on the device (n-step TD returns only).  The padding
+    actions are organise_transitions' draws: one np.random.randint(0, n_action) per env in env order,
+    successful or not -- drawn as one array, which yields the same values and leaves the legacy stream
+    where the scalar calls leave it.  Returns the per-env step counts as a host array."""
+    if unroll_n_steps != buffer.unroll_n_steps or n_action != buffer.n_action:
+        raise ValueError("ingest_records: unroll_n_steps / n_action differ from the buffer's")
+    B = int(res["steps"].shape[0])
+    pad_action = np.random.randint(0, n_action, size=B)
+    buffer.add_episodes(res, discount=discount, n_step=n_step, pad_action=pad_action)
+    return res["steps"].cpu().numpy()
 
 
 def _reward_py(r):
