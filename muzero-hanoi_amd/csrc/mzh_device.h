@@ -202,6 +202,20 @@ __device__ __forceinline__ float mzh_vmax(float a, float b) {
   asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
   return r;
 }
+// Cross-row exchange without LDS: v_permlane16_swap / v_permlane32_swap of a register with itself
+// leave {own, partner} (rows r, r^1 resp. halves h, h^1) in the two results, in the same order on
+// both lanes of a pair, so op(a, b) is bit-identical on both (and equal to op(own, partner) for a
+// commutative op: max / min / add / or).
+__device__ __forceinline__ void mzh_pair16(float v, float& a, float& b) {
+  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  a = __uint_as_float(r[0]);
+  b = __uint_as_float(r[1]);
+}
+__device__ __forceinline__ void mzh_pair32(float v, float& a, float& b) {
+  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  a = __uint_as_float(r[0]);
+  b = __uint_as_float(r[1]);
+}
 __device__ __forceinline__ float mzh_min8_nonan(float v) {
   float a, b, c;
   asm volatile("s_nop 1\n\tv_min_f32_dpp %0, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf" : "=v"(a) : "v"(v));

@@ -14,7 +14,7 @@
 // bias added after (bin 32 of a 33-bin head: four chains over k = g mod 4, ((p0 + p1) + (p2 + p3)) + bias),
 // the one-hot action columns as the one non-zero step of that chain (acc + w: the zero steps add +-0 to a
 // sum that is never -0), IEEE division in normalize_h_state, the heads through mzh_heads_row and the tree
-// arithmetic through the helpers every search kernel shares (mzh_tree.h), so results equal the other kernels'
+// arithmetic through the helpers every search kernel shares (mzh_mcts.h), so results equal the other kernels'
 // bit for bit.
 //
 // Per simulation (mcts.py:71-109), with a workgroup barrier after each step:
@@ -277,22 +277,24 @@ __device__ __forceinline__ OneHeads one_heads(const MzhOneSmem& sm, int l16, boo
 // the wave (exact, order-free: DPP within each 16-lane row, then the gfx950 row swaps across rows -- no LDS
 // crossbar round trips), IEEE division as the oracle's normalize_h.  The raw units are NaN- and -0-free (an FMA
 // chain from +0 plus a bias), so v_min / v_max are the oracle's min / max.
-__device__ __forceinline__ float one_rowswap_min(float v, bool b32) {
-  const auto r = b32 ? __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false)
-                     : __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return mzh_vmin(__uint_as_float(r[0]), __uint_as_float(r[1]));
+__device__ __forceinline__ float one_rowswap_min(float v) {  // over the 4 rows: rows r, r^1, then halves
+  float a, b;
+  mzh_pair16(v, a, b);
+  mzh_pair32(mzh_vmin(a, b), a, b);
+  return mzh_vmin(a, b);
 }
-__device__ __forceinline__ float one_rowswap_max(float v, bool b32) {
-  const auto r = b32 ? __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false)
-                     : __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return mzh_vmax(__uint_as_float(r[0]), __uint_as_float(r[1]));
+__device__ __forceinline__ float one_rowswap_max(float v) {
+  float a, b;
+  mzh_pair16(v, a, b);
+  mzh_pair32(mzh_vmax(a, b), a, b);
+  return mzh_vmax(a, b);
 }
 __device__ __forceinline__ float one_normalize64(float h) {
   float mn = mzh_min8_nonan(h), mx = mzh_max8_nonan(h), a, b;
   asm volatile("s_nop 1\n\tv_min_f32_dpp %0, %1, %1 row_mirror row_mask:0xf bank_mask:0xf" : "=v"(a) : "v"(mn));
   asm volatile("s_nop 1\n\tv_max_f32_dpp %0, %1, %1 row_mirror row_mask:0xf bank_mask:0xf" : "=v"(b) : "v"(mx));
-  mn = one_rowswap_min(one_rowswap_min(a, false), true);
-  mx = one_rowswap_max(one_rowswap_max(b, false), true);
+  mn = one_rowswap_min(a);
+  mx = one_rowswap_max(b);
   const float d = (mx - mn) + 9.999999939225290290778502821922302246094e-09f;
   return (h - mn) / d;
 }
@@ -317,8 +319,8 @@ __host__ __device__ inline OneLayout one_layout(int S, bool latl) {
 size_t mzh_one_smem_bytes(int S, bool latl) { return (one_layout(S, latl).total + 15) & ~(size_t)15; }
 
 // The root's 8-lane group (wave 0, lanes 0-7; lane c = child slot c) over the LDS tree.  The same operations,
-// in the same order, as MzhTree (mzh_tree.h) -- node.py:53-123's arithmetic in fp64 with the shared helpers --
-// only the storage differs: every block in LDS, the path a flat array.
+// in the same order, as MzhTree (mzh_tree.h) -- node.py:53-123's arithmetic in fp64 with the shared helpers
+// (mzh_mcts.h) -- only the storage differs: every block in LDS, the path a flat array.
 struct MzhOneTree {
   const MzhSearchParams& p;
   MzhRootBlk& rb;
@@ -334,8 +336,8 @@ struct MzhOneTree {
 
   template <bool EXACT>
   __device__ __forceinline__ void select_impl(const int c, MzhRootReg& rs) {
-    const double mmax = rs.mmax, mmin = rs.mmin, den = rs.den, dinv = rs.dinv;
-    const bool has = mmax > mmin;
+    const double mmin = rs.mm.mmin, den = rs.mm.den, dinv = rs.mm.dinv;
+    const bool has = rs.mm.has();
     int firstTie = rs.firstTie, extra = rs.extra;
     const int tie = rs.tie;
     // level 0: the root block (all 8 slots initialised; slots 6, 7 never win)
@@ -405,7 +407,7 @@ struct MzhOneTree {
   // MMIN (caller-given MinMaxStats bounds): the exact normaliser when max - min is a non-zero subnormal
   template <bool MMIN>
   __device__ __forceinline__ void select(const int c, MzhRootReg& rs) {
-    if (MMIN && __builtin_expect(mzh_need_exact(rs.mmax > rs.mmin, rs.den), 0))
+    if (MMIN && __builtin_expect(mzh_need_exact(rs.mm.has(), rs.mm.den), 0))
       select_impl<true>(c, rs);
     else
       select_impl<false>(c, rs);
@@ -482,74 +484,21 @@ struct MzhOneTree {
     }
     rs.rootN += 1;
     mzh_maxmin8d(lmax, lmin);
-    rs.set_mm(lmax > rs.mmax ? lmax : rs.mmax, lmin < rs.mmin ? lmin : rs.mmin);
+    rs.mm.update(lmax, lmin);
 #ifdef MZH_STAMPS
-    asm volatile("" ::"v"(rs.dinv));
+    asm volatile("" ::"v"(rs.mm.dinv));
 #endif
     MZH_LSTAMP(3);
     MZH_LSTAMP_COUNT();
     MZH_LSTAMP_FLUSH(14);
   }
 
-  // results of root r (mcts.py:111-126, 154-176): MzhTree::results from the registers / LDS, one lane
+  // results of root `root` (mcts.py:111-126, 154-176) from the registers / LDS, one lane
   __device__ __forceinline__ void results(const int root, const MzhRootReg& rs) {
-    const int PL = p.S + 1;
     int vis[MZH_A];
-    for (int a = 0; a < MZH_A; ++a) {
-      vis[a] = rb.N[a];
-      p.visits[(size_t)root * MZH_A + a] = vis[a];
-    }
-    if (p.root_q) p.root_q[root] = rs.rootN == 0 ? 0.0 : rs.rootW / (double)rs.rootN;
-    if (p.minmax_out) {
-      p.minmax_out[2 * root] = rs.mmax;
-      p.minmax_out[2 * root + 1] = rs.mmin;
-    }
-    if (p.extra_ties) p.extra_ties[root] = rs.extra;
-    if (p.sel_steps) p.sel_steps[root] = rs.steps;
-    const int d = p.S > 0 ? rs.depth : 0;
-    if (p.latent && p.S > 0) {
-      for (int j = 0; j < d; ++j) p.latent[(size_t)root * PL + j] = path[j] & 7;
-      for (int j = d; j < PL; ++j) p.latent[(size_t)root * PL + j] = -1;
-    }
-    if (p.latent_len) p.latent_len[root] = d;
-    if (p.pi || p.action) {
-      double v[MZH_A];
-      for (int a = 0; a < MZH_A; ++a) v[a] = (double)vis[a];
-      if (p.temperature > 0.0) {
-        double ex = 1.0 / p.temperature;
-        ex = ex < 5.0 ? ex : 5.0;  // max(1.0, min(5.0, 1/T))
-        ex = ex > 1.0 ? ex : 1.0;
-        for (int a = 0; a < MZH_A; ++a) v[a] = mzh_pow(v[a], vis[a], ex, p.pow_table);
-      }
-      double sum = 0.0;
-      for (int a = 0; a < MZH_A; ++a) sum = sum + v[a];
-      double pi[MZH_A];
-      for (int a = 0; a < MZH_A; ++a) pi[a] = v[a] / sum;
-      if (p.pi)
-        for (int a = 0; a < MZH_A; ++a) p.pi[(size_t)root * MZH_A + a] = pi[a];
-      int act = 0;
-      if (p.deterministic || !p.action_u) {
-        for (int a = 1; a < MZH_A; ++a)
-          if (vis[a] > vis[act]) act = a;
-      } else {
-        double cdf[MZH_A];
-        double acc = 0.0;
-        for (int a = 0; a < MZH_A; ++a) {
-          acc = acc + pi[a];
-          cdf[a] = acc;
-        }
-        const double last = cdf[MZH_A - 1];
-        const double u = p.action_u[root];
-        act = MZH_A - 1;
-        for (int a = 0; a < MZH_A; ++a) {
-          if (cdf[a] / last > u) {
-            act = a;
-            break;
-          }
-        }
-      }
-      if (p.action) p.action[root] = act;
-    }
+    for (int a = 0; a < MZH_A; ++a) vis[a] = rb.N[a];
+    mzh_write_results(p, root, vis, rs.rootW, rs.rootN, rs.mm.mmax, rs.mm.mmin, rs.extra, rs.steps, rs.depth,
+                      [&](int j) { return (int)path[j]; });
   }
 };
 
@@ -690,19 +639,15 @@ __global__ __launch_bounds__(512, 2) void mzh_search_one_kernel(MzhNet net, MzhO
       rb.X[c] = -1;
       rb.R[c] = 0.0f;
       rb.W[c] = 0.0;
-      double v = (double)pr;
-      if (noised && c < MZH_A) {
-        const float scaled = (float)(1.0 - p.eps) * pr;  // (1-eps) * prob, float32 array
-        v = (double)scaled + p.eps * p.noise[(size_t)r * MZH_A + c];
-      }
-      rb.P64[c] = v;
+      const bool mix = noised && c < MZH_A;
+      rb.P64[c] = mzh_root_prior(pr, mix, p.eps, mix ? p.noise[(size_t)r * MZH_A + c] : 0.0);
       MzhRootReg rs;
       double mx = -__builtin_inf(), mn = __builtin_inf();
       if (p.minmax_in) {
         mx = p.minmax_in[2 * r];
         mn = p.minmax_in[2 * r + 1];
       }
-      rs.set_mm(mx, mn);
+      rs.mm.set(mx, mn);
       rs.rootW = 0.0;
       rs.rootN = 0;
       rs.firstTie = 0;

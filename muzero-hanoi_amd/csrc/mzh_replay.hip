@@ -211,7 +211,7 @@ __device__ __forceinline__ double wave_scan(double v) {
 }
 
 // a / b (a >= 0, b > 0, the quotient in [0, 1] and not subnormal) from y = RN(1/b): Markstein's correction,
-// equal to IEEE division there (mzh_tree.h mzh_div; tests/test_markstein.py)
+// equal to IEEE division there (mzh_mcts.h mzh_div; tests/test_markstein.py)
 __device__ __forceinline__ double rdiv(double a, double b, double y) {
   const double q = a * y;
   return __builtin_fma(__builtin_fma(-q, b, a), y, q);

@@ -84,9 +84,9 @@ __device__ __forceinline__ void mzh_search_body(const MzhNet& net, const MzhSear
     st.depth[r] = 0;
     st.tie[r] = (p.tie_idx && r < nvalid) ? p.tie_idx[root0 + r] : 0;
     if (p.minmax_in && r < nvalid) {
-      mzh_mm_set(st.mm[r], p.minmax_in[2 * (root0 + r)], p.minmax_in[2 * (root0 + r) + 1]);
+      st.mm[r].set(p.minmax_in[2 * (root0 + r)], p.minmax_in[2 * (root0 + r) + 1]);
     } else {
-      mzh_mm_set(st.mm[r], -__builtin_inf(), __builtin_inf());
+      st.mm[r].set(-__builtin_inf(), __builtin_inf());
     }
   }
 
@@ -118,12 +118,8 @@ __device__ __forceinline__ void mzh_search_body(const MzhNet& net, const MzhSear
     rb.X[c] = -1;
     rb.R[c] = 0.0f;
     rb.W[c] = 0.0;
-    double v = (double)pr;
-    if (noised && r < nvalid && c < MZH_A) {
-      const float scaled = (float)(1.0 - p.eps) * pr;  // (1-eps) * prob, float32 array
-      v = (double)scaled + p.eps * p.noise[(size_t)(root0 + r) * MZH_A + c];
-    }
-    rb.P64[c] = v;
+    const bool mix = noised && r < nvalid && c < MZH_A;
+    rb.P64[c] = mzh_root_prior(pr, mix, p.eps, mix ? p.noise[(size_t)(root0 + r) * MZH_A + c] : 0.0);
   }
   if (tid < R && tid >= nvalid) sm.act[tid] = 0;  // rows beyond the batch: any valid one-hot index
   floatx4 fa[NF], fb[NF];

@@ -1,12 +1,14 @@
 // mzh_tree.h -- the search tree on the device: layout in HBM / LDS and the per-root select,
-// expand/backup and result steps of the cooperative search kernels (mzh_search.hip,
-// mzh_split.hip).  Each root is owned by one aligned 8-lane group (lane c = child slot c).
+// expand/backup and result steps of the cooperative search kernels (mzh_search.hip).  Each root is
+// owned by one aligned 8-lane group (lane c = child slot c).  The arithmetic shared with the wave
+// and latency kernels is in mzh_mcts.h.
 //
 // Reference: MCTS/mcts.py:34-176 (run_mcts, generate_play_policy), MCTS/node.py:30-136
 // (expand / backup / best_child / child_Q / child_U), MCTS/utils_mcts.py:1-16 (MinMaxStats).
 #pragma once
 #include "mzh_device.h"
 #include "mzh_internal.h"
+#include "mzh_mcts.h"
 
 // ------------------------------------------------------------------------------------------
 // tree block: the 6 children of one expanded node in exactly one 128-byte cache line, so a
@@ -55,7 +57,7 @@ struct SearchSmem {
   MzhRootBlk root[R];
   MzhPathEnt pc[R][DC + 1];  // entry DC: where the selection's stores of deeper levels land (never read)
   double rootW[R];
-  double mm[R][4];  // MinMaxStats (maximum, minimum) + normaliser (max - min, RN(1/(max - min)))
+  MzhMinMax mm[R];
   int rootN[R];
   int firstTie[R];
   int extra[R];
@@ -67,91 +69,27 @@ struct SearchSmem {
   int lvl[2][MZH_WAVES];  // p.lockstep_levels: each wave's deepest selection, by selection parity
 };
 
-// a / b correctly rounded from y = RN(1/b) (Markstein: q = RN(a*y) is within one ulp, the fma
-// residual is exact, and one correction step rounds to RN(a/b)); 3 fp64 ops instead of the
-// ~12-op div_scale/rcp/fmas/fixup sequence on the select chain.  Equal to `a / b` for every
-// finite non-subnormal quotient; checked against true division in tests/test_markstein.py.
-__device__ __forceinline__ double mzh_div(double a, double b, double y) {
-  const double q = a * y;
-  const double r = __builtin_fma(-q, b, a);
-  return __builtin_fma(r, y, q);
-}
-
-// MinMaxStats.normalize (utils_mcts.py:12-16) with den = max - min, dinv = RN(1/den).  The
-// Markstein quotient needs a normal den (its reciprocal finite, the residual exact); `exact`
-// (wave-uniform: some lane of the wave has a subnormal den -- only reachable from caller-given
-// MinMaxStats bounds, never from fp32 network outputs) takes the IEEE division instead
-__device__ __forceinline__ double mzh_normalize(double v, bool has, double mn, double den, double dinv, bool exact) {
-  return has ? (exact ? (v - mn) / den : mzh_div(v - mn, den, dinv)) : v;
-}
-// whether any lane of the wave needs the exact normaliser (a non-zero subnormal max - min)
-__device__ __forceinline__ bool mzh_need_exact(bool has, double den) {
-  return __builtin_amdgcn_ballot_w64(has && !(den >= 2.2250738585072014e-308)) != 0;
-}
-
-// ucb = fl32(Q) + fl32(U) for one child (node.py:90-123); `tnp` = table[N_parent], inv[k] = RN(1/k)
-// Branch-free: both reciprocals are read together (one ds_read2_b64) and the Q and U chains run side
-// by side; for Nc = 0 the Q chain computes from inv[0] = inf and its result is discarded.
-__device__ __forceinline__ float mzh_ucb(int Nc, double Wc, float Rc, double P64, bool p64_semantics, double tnp,
-                                         double disc, bool has, double mn, double den, double dinv,
-                                         const double* inv, bool exact) {
-  const double i0 = inv[Nc], i1 = inv[Nc + 1];
-  const double qn = mzh_normalize((double)Rc + disc * mzh_div(Wc, (double)Nc, i0), has, mn, den, dinv, exact);
-  const float q32 = Nc > 0 ? (float)qn : 0.0f;
-  const double w = mzh_div(tnp, (double)(Nc + 1), i1);
-  // np.float64 priors (Dirichlet-mixed root) or NumPy-1 promotion: fl32(fl64(prior * w));
-  // NumPy-2 with np.float32 priors: fl32(prior * fl32(w))
-  const float u32 = p64_semantics ? (float)(P64 * w) : (float)P64 * (float)w;
-  return q32 + u32;
-}
-
-// MinMaxStats update with the select-side normaliser precomputed (den, RN(1/den))
-__device__ __forceinline__ void mzh_mm_set(double* mm, double mx, double mn) {
-  mm[0] = mx;
-  mm[1] = mn;
-  mm[2] = mx - mn;
-  mm[3] = mx > mn ? 1.0 / (mx - mn) : 0.0;
-}
-
-// argmax over the 6 children held by the 8-lane group, with the reference's tie handling:
-// np.random.choice(argmax set) -- the first 6-way tie takes the host-drawn index, any other tie
-// is counted (RNG-stream divergence) and resolved to the lowest index.  Branch-free; every lane
-// of the group returns the same pick.
+// argmax over the 6 children held by the 8-lane group, with the reference's tie handling
+// (mzh_tie_pick).  Branch-free; every lane of the group returns the same pick.
 __device__ __forceinline__ int mzh_group_pick(float ucb, int c, int lane, int tie, int& firstTie, int& extra) {
   const float m = mzh_max8_nonan(ucb);
   (void)c;  // lanes 6, 7 carry -inf, never the group maximum (the UCBs are finite)
   const unsigned long long bal = __builtin_amdgcn_ballot_w64(ucb == m);
   const unsigned mask = (unsigned)(bal >> (lane & ~7)) & 0x3Fu;
-  const int cnt = __popc(mask);
-  const int first = __ffs(mask) - 1;
-  const bool six = (cnt == MZH_A) & (firstTie == 0);
-  extra += ((cnt > 1) & !six) ? 1 : 0;
-  firstTie |= six ? 1 : 0;
-  return six ? tie : first;
+  return mzh_tie_pick(mask, tie, firstTie, extra);
 }
-
-
 
 // A root's search state between the tree steps, held in registers by every lane of its 8-lane group
 // (all values group-uniform: every lane runs the value chain).  The LDS copy
 // (SearchSmem) is read once before the first selection and written back once for the results.
 struct MzhRootReg {
-  double mmax, mmin, den, dinv;  // MinMaxStats + normaliser (mzh_mm_set)
+  MzhMinMax mm;
   double rootW;
   int rootN, firstTie, extra, tie, steps;
   int depth, leafE, leafA;  // the current simulation's leaf (select -> backup)
-  __device__ __forceinline__ void set_mm(double mx, double mn) {
-    mmax = mx;
-    mmin = mn;
-    den = mx - mn;
-    dinv = mx > mn ? 1.0 / (mx - mn) : 0.0;
-  }
   template <int R, int DC>
   __device__ __forceinline__ void load(const SearchSmem<R, DC>& st, int r) {
-    mmax = st.mm[r][0];
-    mmin = st.mm[r][1];
-    den = st.mm[r][2];
-    dinv = st.mm[r][3];
+    mm = st.mm[r];
     rootW = st.rootW[r];
     rootN = st.rootN[r];
     firstTie = st.firstTie[r];
@@ -164,7 +102,9 @@ struct MzhRootReg {
   }
   template <int R, int DC>
   __device__ __forceinline__ void store(SearchSmem<R, DC>& st, int r) const {
-    mzh_mm_set(st.mm[r], mmax, mmin);
+    // from the bounds alone: a copy would keep den / dinv live past the last backup (one spilled
+    // register in the two-workgroups-per-CU kernel)
+    st.mm[r].set(mm.mmax, mm.mmin);
     st.rootW[r] = rootW;
     st.rootN[r] = rootN;
     st.firstTie[r] = firstTie;
@@ -196,7 +136,7 @@ struct MzhTree {
   // the kernel carries only the Markstein copy.
   template <bool MMIN>
   __device__ __forceinline__ void select(const int r, const int c, const int s, MzhRootReg& rs) {
-    if (MMIN && __builtin_expect(mzh_need_exact(rs.mmax > rs.mmin, rs.den), 0))
+    if (MMIN && __builtin_expect(mzh_need_exact(rs.mm.has(), rs.mm.den), 0))
       select_impl<true>(r, c, s, rs);
     else
       select_impl<false>(r, c, s, rs);
@@ -205,8 +145,8 @@ struct MzhTree {
   template <bool EXACT>
   __device__ __forceinline__ void select_impl(const int r, const int c, const int s, MzhRootReg& rs) {
     const MzhBlock* tb = reinterpret_cast<const MzhBlock*>(p.tree) + (size_t)(root0 + r) * p.E;
-    const double mmax = rs.mmax, mmin = rs.mmin, den = rs.den, dinv = rs.dinv;
-    const bool has = mmax > mmin;
+    const double mmin = rs.mm.mmin, den = rs.mm.den, dinv = rs.mm.dinv;
+    const bool has = rs.mm.has();
     constexpr bool exact = EXACT;
     int firstTie = rs.firstTie;
     int extra = rs.extra;
@@ -459,68 +399,15 @@ struct MzhTree {
     MZH_STAMP(18);
     rs.rootN += 1;
     mzh_maxmin8d(lmax, lmin);
-    rs.set_mm(lmax > rs.mmax ? lmax : rs.mmax, lmin < rs.mmin ? lmin : rs.mmin);
+    rs.mm.update(lmax, lmin);
     MZH_STAMP(29);
   }
 
   // ---------------- results of root r (mcts.py:111-126, 154-176), one lane ----------------
   __device__ __forceinline__ void results(const int r) {
-    const int root = root0 + r;
     int vis[MZH_A];
-    for (int a = 0; a < MZH_A; ++a) {
-      vis[a] = st.root[r].N[a];
-      p.visits[(size_t)root * MZH_A + a] = vis[a];
-    }
-    if (p.root_q) p.root_q[root] = st.rootN[r] == 0 ? 0.0 : st.rootW[r] / (double)st.rootN[r];
-    if (p.minmax_out) {
-      p.minmax_out[2 * root] = st.mm[r][0];
-      p.minmax_out[2 * root + 1] = st.mm[r][1];
-    }
-    if (p.extra_ties) p.extra_ties[root] = st.extra[r];
-    if (p.sel_steps) p.sel_steps[root] = st.steps[r];
-    if (p.latent && p.S > 0) {
-      const int d = st.depth[r];
-      for (int j = 0; j < d; ++j) p.latent[(size_t)root * PL + j] = path[r * PL + j] & 7;
-      for (int j = d; j < PL; ++j) p.latent[(size_t)root * PL + j] = -1;
-    }
-    if (p.latent_len) p.latent_len[root] = p.S > 0 ? st.depth[r] : 0;
-    if (p.pi || p.action) {
-      double v[MZH_A];
-      for (int a = 0; a < MZH_A; ++a) v[a] = (double)vis[a];
-      if (p.temperature > 0.0) {
-        double ex = 1.0 / p.temperature;
-        ex = ex < 5.0 ? ex : 5.0;  // max(1.0, min(5.0, 1/T))
-        ex = ex > 1.0 ? ex : 1.0;
-        for (int a = 0; a < MZH_A; ++a) v[a] = mzh_pow(v[a], vis[a], ex, p.pow_table);
-      }
-      double sum = 0.0;
-      for (int a = 0; a < MZH_A; ++a) sum = sum + v[a];
-      double pi[MZH_A];
-      for (int a = 0; a < MZH_A; ++a) pi[a] = v[a] / sum;
-      if (p.pi)
-        for (int a = 0; a < MZH_A; ++a) p.pi[(size_t)root * MZH_A + a] = pi[a];
-      int act = 0;
-      if (p.deterministic || !p.action_u) {
-        for (int a = 1; a < MZH_A; ++a)
-          if (vis[a] > vis[act]) act = a;
-      } else {
-        double cdf[MZH_A];
-        double acc = 0.0;
-        for (int a = 0; a < MZH_A; ++a) {
-          acc = acc + pi[a];
-          cdf[a] = acc;
-        }
-        const double last = cdf[MZH_A - 1];
-        const double u = p.action_u[root];
-        act = MZH_A - 1;
-        for (int a = 0; a < MZH_A; ++a) {
-          if (cdf[a] / last > u) {
-            act = a;
-            break;
-          }
-        }
-      }
-      if (p.action) p.action[root] = act;
-    }
+    for (int a = 0; a < MZH_A; ++a) vis[a] = st.root[r].N[a];
+    mzh_write_results(p, root0 + r, vis, st.rootW[r], st.rootN[r], st.mm[r].mmax, st.mm[r].mmin, st.extra[r],
+                      st.steps[r], st.depth[r], [&](int j) { return (int)path[r * PL + j]; });
   }
 };

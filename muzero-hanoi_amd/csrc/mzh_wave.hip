@@ -22,11 +22,14 @@
 // MCTS/utils_mcts.py:1-16 (MinMaxStats), networks.py:71-196 (initial/recurrent inference).
 #include "mzh_device.h"
 #include "mzh_internal.h"
+#include "mzh_mcts.h"
 
 #define MZW_WAVES 4   // waves per workgroup; two workgroups per CU = two waves per SIMD (256 VGPRs)
 #define MZW_DC 16     // selection-path depths cached in LDS per root (deeper: HBM pathx)
 
-// tree block: identical to mzh_search.hip's MzhBlock (one 128-B line per expanded node)
+// tree block: one 128-B line per expanded node, field-major (N|X of the 6 children, then R, P, W), so
+// a lane of a root's pair loads its 3 children of each field as one run; mzh_tree.h's MzhBlock holds
+// the same fields slot-major
 struct MzwNX {
   uint16_t N;
   int16_t X;
@@ -65,47 +68,34 @@ __device__ __forceinline__ void mzw_wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// Cross-row exchange without LDS: v_permlane16_swap / v_permlane32_swap of a register with itself
-// leave {own, partner} (rows r, r^1 resp. halves h, h^1) in the two results, in the same order on
-// both lanes of a pair, so op(r[0], r[1]) is bit-identical on both (and equal to op(own, partner)
-// for the commutative max / min / add used here).
-__device__ __forceinline__ void mzw_pair16(float v, float& a, float& b) {
-  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  a = __uint_as_float(r[0]);
-  b = __uint_as_float(r[1]);
-}
-__device__ __forceinline__ void mzw_pair32(float v, float& a, float& b) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  a = __uint_as_float(r[0]);
-  b = __uint_as_float(r[1]);
-}
+// Cross-row reductions over the row swaps (mzh_pair16 / mzh_pair32, mzh_device.h).
 // The maxima below feed only exponent arguments (x - max: identical for a +0 / -0 max), the
 // normaliser's max - min (likewise) and argmax equality masks, and no operand is NaN: v_max_f32
 // (one instruction) instead of compare + select (two, with a VCC hazard wait between them).
 __device__ __forceinline__ float mzw_max4g(float v) {  // max over the 4 lane groups (rows) of a column
   float a, b;
-  mzw_pair16(v, a, b);
+  mzh_pair16(v, a, b);
   v = __builtin_fmaxf(a, b);
-  mzw_pair32(v, a, b);
+  mzh_pair32(v, a, b);
   return __builtin_fmaxf(a, b);
 }
 // min over the 4 lane groups for the latent normalisation: no operand is NaN or -0 (a latent unit is
 // an FMA chain from +0 plus a bias, which never rounds to -0), so v_min_f32 is the select's result
 __device__ __forceinline__ float mzw_min4g(float v) {
   float a, b;
-  mzw_pair16(v, a, b);
+  mzh_pair16(v, a, b);
   v = __builtin_fminf(a, b);
-  mzw_pair32(v, a, b);
+  mzh_pair32(v, a, b);
   return __builtin_fminf(a, b);
 }
 __device__ __forceinline__ float mzw_add16(float v) {  // row0 + row1 (row2 + row3)
   float a, b;
-  mzw_pair16(v, a, b);
+  mzh_pair16(v, a, b);
   return a + b;
 }
 __device__ __forceinline__ float mzw_add32(float v) {  // rows 0-1 + rows 2-3
   float a, b;
-  mzw_pair32(v, a, b);
+  mzh_pair32(v, a, b);
   return a + b;
 }
 
@@ -119,9 +109,6 @@ __device__ __forceinline__ float mzw_add32(float v) {  // rows 0-1 + rows 2-3
 // The weight stream goes through a buffer resource: the lane's byte offset sits in one VGPR, the
 // fragment / block offset is uniform (SGPR or immediate), so no load costs 64-bit VALU address
 // arithmetic (the 64-bit pointer form spent ~13 VALU per two hidden blocks on it).
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t mzw_rsrc(const void* p) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, 0x7FFFFFFF, 0x00020000);
-}
 __device__ __forceinline__ floatx4 mzw_ld4(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
   return __builtin_bit_cast(floatx4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
 }
@@ -381,29 +368,7 @@ __device__ __forceinline__ floatx4 mzw_policy(const floatx4 l, int lane) {
   return p;
 }
 
-// ---- tree helpers (same arithmetic as mzh_search.hip) ----
-// a / b correctly rounded from y = RN(1/b) (Markstein; see mzh_search.hip mzh_div)
-__device__ __forceinline__ double mzw_div(double a, double b, double y) {
-  const double q = a * y;
-  const double r = __builtin_fma(-q, b, a);
-  return __builtin_fma(r, y, q);
-}
-// ucb = fl32(Q) + fl32(U) for one child (node.py:90-123); inv[k] = RN(1/k) (LDS table)
-__device__ __forceinline__ float mzw_ucb(int Nc, double Wc, float Rc, double P64, bool p64_semantics, double tnp,
-                                         double disc, bool has, double mn, double den, double dinv,
-                                         const double* inv, bool exact) {
-  // branch-free: both reciprocals in one LDS read, the Q and U chains side by side (for Nc = 0 the
-  // Q chain runs on inv[0] = inf and is discarded)
-  const double i0 = inv[Nc], i1 = inv[Nc + 1];
-  const double v = (double)Rc + disc * mzw_div(Wc, (double)Nc, i0);
-  // exact (wave-uniform): IEEE division for a subnormal den (see mzh_tree.h mzh_normalize)
-  const double qn = has ? (exact ? (v - mn) / den : mzw_div(v - mn, den, dinv)) : v;
-  const float q32 = Nc > 0 ? (float)qn : 0.0f;
-  const double w = mzw_div(tnp, (double)(Nc + 1), i1);
-  const float u32 = p64_semantics ? (float)(P64 * w) : (float)P64 * (float)w;
-  return q32 + u32;
-}
-// argmax over the 6 children with the reference's tie handling (see mzh_group_pick):
+// argmax over the 6 children with the reference's tie handling (mzh_tie_pick, mzh_mcts.h):
 // the 6 children are split over a lane pair (i, i + 32), 3 each: the pair's
 // max and its 6-bit argmax mask combine through v_permlane32_swap (max and OR are order-free), so
 // both lanes return the same pick and tie bookkeeping
@@ -412,20 +377,14 @@ __device__ __forceinline__ int mzw_pick_pair(const float (&u)[3], int half, int 
   m = __builtin_fmaxf(u[1], m);
   m = __builtin_fmaxf(u[2], m);
   float a, b;
-  mzw_pair32(m, a, b);
+  mzh_pair32(m, a, b);
   const float M = __builtin_fmaxf(a, b);
   int mask = 0;
 #pragma unroll
   for (int j = 0; j < 3; ++j) mask |= (u[j] == M ? 1 : 0) << j;
   mask <<= 3 * half;
   const auto r = __builtin_amdgcn_permlane32_swap((unsigned)mask, (unsigned)mask, false, false);
-  const int full = (int)(r[0] | r[1]);
-  const int cnt = __popc(full);
-  const int first = __ffs(full) - 1;
-  const bool six = (cnt == MZH_A) & (firstTie == 0);
-  extra += ((cnt > 1) & !six) ? 1 : 0;
-  firstTie |= six ? 1 : 0;
-  return six ? tie : first;
+  return mzh_tie_pick(r[0] | r[1], tie, firstTie, extra);
 }
 
 // The two waves a SIMD holds drift apart.  Phase-locking them (8-wave workgroups, one barrier per
@@ -444,7 +403,7 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // provably wave-uniform (scalar branches)
   const int g = lane >> 4, col = lane & 15;
-  const __amdgpu_buffer_rsrc_t rw = mzw_rsrc(net.wbase);
+  const __amdgpu_buffer_rsrc_t rw = mzh_rsrc(net.wbase);
 
   if (!REPLAY)
     for (int i = tid; i < MZH_A * MZH_F; i += MZW_WAVES * 64) ohl[i] = net.oh[i];
@@ -469,12 +428,11 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
   const int rroot = wr0 + rho;
   const bool rvalid = rho < ROOTS && rroot < p.B;
   MzwBlock* tb = reinterpret_cast<MzwBlock*>(p.tree) + (size_t)(rvalid ? rroot : 0) * E;
-  double mmax = -__builtin_inf(), mmin = __builtin_inf();
-  if (rvalid && p.minmax_in) {
-    mmax = p.minmax_in[2 * rroot];
-    mmin = p.minmax_in[2 * rroot + 1];
-  }
-  double den = mmax - mmin, dinv = mmax > mmin ? 1.0 / (mmax - mmin) : 0.0;
+  MzhMinMax mm;
+  if (rvalid && p.minmax_in)
+    mm.set(p.minmax_in[2 * rroot], p.minmax_in[2 * rroot + 1]);
+  else
+    mm.set(-__builtin_inf(), __builtin_inf());
   int firstTie = 0, extra = 0, steps = 0, rootN = 0, depth = 0, leafE = 0, leafA = 0;
   int lsum = 0;  // p.lockstep_levels: the wave's deepest selection below the root, summed over simulations
   double rootW = 0.0;
@@ -538,12 +496,8 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
         const int c = 4 * g + i;
         if (c < MZH_A && cvalid[n]) {
           const float pr = REPLAY ? p.rp_root_pi[(size_t)croot[n] * MZH_A + c] : rpi[n][i];
-          double v = (double)pr;
-          if (noised) {
-            const float scaled = (float)(1.0 - p.eps) * pr;  // (1-eps) * prob, float32 array
-            v = (double)scaled + p.eps * p.noise[(size_t)croot[n] * MZH_A + c];
-          }
-          ws.rP[c][16 * n + col] = v;
+          ws.rP[c][16 * n + col] =
+              mzh_root_prior(pr, noised, p.eps, noised ? p.noise[(size_t)croot[n] * MZH_A + c] : 0.0);
         }
       }
   }
@@ -578,13 +532,14 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
     constexpr bool exact = decltype(ex)::value;
     // ---------------- select (mcts.py:75-86; node.py:72-123): one lane per root ----------------
     if (rvalid) {
-      const bool has = mmax > mmin;
+      const bool has = mm.has();
+      const double mmin = mm.mmin, den = mm.den, dinv = mm.dinv;
       float u[3];
       const double tr = table[rootN];
 #pragma unroll
       for (int j = 0; j < 3; ++j) {
         const int c = 3 * half + j;
-        u[j] = mzw_ucb(ws.rN[c][rho], ws.rW[c][rho], ws.rR[c][rho], ws.rP[c][rho], noised || p.np1, tr, disc, has,
+        u[j] = mzh_ucb(ws.rN[c][rho], ws.rW[c][rho], ws.rR[c][rho], ws.rP[c][rho], noised || p.np1, tr, disc, has,
                        mmin, den, dinv, inv, exact);
       }
       int pick = mzw_pick_pair(u, half, tie, firstTie, extra);
@@ -633,7 +588,7 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
           }
           const double tn = table[Np];
   #pragma unroll
-          for (int j = 0; j < 3; ++j) u[j] = mzw_ucb(hn[j] & 0xFFFF, hw[j], hr[j], (double)hp[j], p.np1, tn, disc, has, mmin, den, dinv, inv, exact);
+          for (int j = 0; j < 3; ++j) u[j] = mzh_ucb(hn[j] & 0xFFFF, hw[j], hr[j], (double)hp[j], p.np1, tn, disc, has, mmin, den, dinv, inv, exact);
           pick = mzw_pick_pair(u, half, tie, firstTie, extra);
           // this lane's candidate for the picked slot (valid on the owning half), then the owner's copy
           const int jl = pick - 3 * half;
@@ -841,7 +796,7 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
         const double rw = (j == depth - 1) ? (double)rr : (double)Rj;
         Wn = Wj + v;
         Nn = Nj + 1;
-        const double q = rw + disc * mzw_div(Wn, (double)Nn, inv[Nn]);  // MinMaxStats input
+        const double q = rw + disc * mzh_div(Wn, (double)Nn, inv[Nn]);  // MinMaxStats input
         lmax = q > lmax ? q : lmax;
         lmin = q < lmin ? q : lmin;
         v = rw + disc * v;
@@ -881,19 +836,16 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
       }
       rootW = rootW + v;
       rootN = rootN + 1;
-      const double q = 0.0 + disc * mzw_div(rootW, (double)rootN, inv[rootN]);  // root rwd = 0.0
+      const double q = 0.0 + disc * mzh_div(rootW, (double)rootN, inv[rootN]);  // root rwd = 0.0
       lmax = q > lmax ? q : lmax;
       lmin = q < lmin ? q : lmin;
-      mmax = lmax > mmax ? lmax : mmax;
-      mmin = lmin < mmin ? lmin : mmin;
-      den = mmax - mmin;
-      dinv = mmax > mmin ? 1.0 / (mmax - mmin) : 0.0;
+      mm.update(lmax, lmin);
     }
   };
 
   for (int s = 0; s < S; ++s) {
     MZH_STAMP(4);
-    if (__builtin_expect(__builtin_amdgcn_ballot_w64(rvalid && mmax > mmin && !(den >= 2.2250738585072014e-308)) != 0, 0))
+    if (__builtin_expect(mzh_need_exact(rvalid && mm.has(), mm.den), 0))
       phase_select(s, MzhBool<true>{});
     else
       phase_select(s, MzhBool<false>{});
@@ -914,64 +866,11 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
   // ---------------- results (mcts.py:111-126, 154-176) ----------------
   if (p.lockstep_levels && lane == 0) p.lockstep_levels[blockIdx.x * MZW_WAVES + wave] = lsum;
   if (!rvalid || half) return;
-  const int root = rroot;
   int vis[MZH_A];
-  for (int a = 0; a < MZH_A; ++a) {
-    vis[a] = ws.rN[a][rho];
-    p.visits[(size_t)root * MZH_A + a] = vis[a];
-  }
-  if (p.root_q) p.root_q[root] = rootN == 0 ? 0.0 : rootW / (double)rootN;
-  if (p.minmax_out) {
-    p.minmax_out[2 * root] = mmax;
-    p.minmax_out[2 * root + 1] = mmin;
-  }
-  if (p.extra_ties) p.extra_ties[root] = extra;
-  if (p.sel_steps) p.sel_steps[root] = steps;
-  const int PL = S + 1;
-  if (p.latent && S > 0) {
-    for (int j = 0; j < depth; ++j)
-      p.latent[(size_t)root * PL + j] = (j < MZW_DC ? (int)ws.path[j][rho] : (int)p.pathx[(size_t)root * E + j]) & 7;
-    for (int j = depth; j < PL; ++j) p.latent[(size_t)root * PL + j] = -1;
-  }
-  if (p.latent_len) p.latent_len[root] = S > 0 ? depth : 0;
-  if (p.pi || p.action) {
-    double v[MZH_A];
-    for (int a = 0; a < MZH_A; ++a) v[a] = (double)vis[a];
-    if (p.temperature > 0.0) {
-      double ex = 1.0 / p.temperature;
-      ex = ex < 5.0 ? ex : 5.0;  // max(1.0, min(5.0, 1/T))
-      ex = ex > 1.0 ? ex : 1.0;
-      for (int a = 0; a < MZH_A; ++a) v[a] = mzh_pow(v[a], vis[a], ex, p.pow_table);
-    }
-    double sum = 0.0;
-    for (int a = 0; a < MZH_A; ++a) sum = sum + v[a];
-    double pi[MZH_A];
-    for (int a = 0; a < MZH_A; ++a) pi[a] = v[a] / sum;
-    if (p.pi)
-      for (int a = 0; a < MZH_A; ++a) p.pi[(size_t)root * MZH_A + a] = pi[a];
-    int act = 0;
-    if (p.deterministic || !p.action_u) {
-      for (int a = 1; a < MZH_A; ++a)
-        if (vis[a] > vis[act]) act = a;
-    } else {
-      double cdf[MZH_A];
-      double acc = 0.0;
-      for (int a = 0; a < MZH_A; ++a) {
-        acc = acc + pi[a];
-        cdf[a] = acc;
-      }
-      const double last = cdf[MZH_A - 1];
-      const double u = p.action_u[root];
-      act = MZH_A - 1;
-      for (int a = 0; a < MZH_A; ++a) {
-        if (cdf[a] / last > u) {
-          act = a;
-          break;
-        }
-      }
-    }
-    if (p.action) p.action[root] = act;
-  }
+  for (int a = 0; a < MZH_A; ++a) vis[a] = ws.rN[a][rho];
+  mzh_write_results(p, rroot, vis, rootW, rootN, mm.mmax, mm.mmin, extra, steps, depth, [&](int j) {
+    return j < MZW_DC ? (int)ws.path[j][rho] : (int)p.pathx[(size_t)rroot * E + j];
+  });
 }
 
 size_t mzh_wave_smem_bytes(int S, int nt) {

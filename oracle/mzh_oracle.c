@@ -372,7 +372,7 @@ void orc_recurrent_inference(const float* flat, int in_dim, int support, int B, 
 #define PB_C_INIT 1.25  /* mcts.py:25 */
 
 /* (log((N + base + 1) / base) + init) * sqrt(N)   -- node.py:114-121 up to the "/ (child.N+1)" */
-/* Property check for the device's division (csrc/mzh_search.hip mzh_div): a / b computed as
+/* Property check for the device's division (csrc/mzh_mcts.h mzh_div): a / b computed as
  * q = a*y, r = fma(-q, b, a), q' = fma(r, y, q) with y = RN(1/b) must equal IEEE a / b.  Runs n
  * random trials over the select/backup operand domains (W / N and table[Np] / (N + 1) with integer
  * N in [1, 64]; normalise's (v - min) / (max - min) with real denominators) and returns the number

@@ -377,6 +377,56 @@ def _random_search_inputs(B, n, seed):
     return obs, noise, tie, u
 
 
+_EPILOGUE_REF = {}
+
+
+def _epilogue_case(oracle, S, T, det):
+    """inputs and the oracle's outputs of one results-epilogue case (computed once, shared by every kernel):
+    5 roots of N = 3 with Dirichlet noise and caller-given MinMaxStats bounds -- fresh, finite, equal
+    (max == min: no normalisation until a backup widens them), and two more finite pairs"""
+    key = (S, T, det)
+    if key not in _EPILOGUE_REF:
+        n, B = 3, 5
+        flat, in_dim, sup = _weights(oracle, f"weights_N{n}_s0")
+        obs, noise, tie, u = _random_search_inputs(B, n, 4242)
+        mm = np.array([[-np.inf, np.inf], [0.4, -0.2], [0.05, 0.05], [1.5, 0.0], [0.0, -1.0]], np.float64)
+        ref = oracle.search(n, S, obs, flat=flat, support=sup, noise=noise, tie_idx=tie, action_u=u, temperature=T,
+                            deterministic=det, minmax_in=mm)
+        _EPILOGUE_REF[key] = (flat, sup, obs, noise, tie, u, mm, ref)
+    return _EPILOGUE_REF[key]
+
+
+@pytest.mark.parametrize("det", [False, True])
+@pytest.mark.parametrize("T", [0.0, 0.1, 0.3, 1.0])
+@pytest.mark.parametrize("S", [1, 8])
+@pytest.mark.parametrize("kernel,tile", [(k, t) for k in KERNELS_MLP for t in ((16, 32) if k == "coop" else (None,))])
+def test_search_results_epilogue_vs_oracle(mzh, oracle, kernel, tile, S, T, det):
+    """The results epilogue every kernel shares (mzh_write_results, mzh_mcts.h) through every kernel: a ragged
+    batch of 5 roots, 1 and 8 simulations, temperatures that take no power (0.0), the clamped exponent 5 (0.1),
+    a table-driven non-integer exponent (0.3) and exponent 1 (1.0), the cdf draw and the argmax, with Dirichlet
+    noise and caller-given MinMaxStats bounds == the oracle, every output bit for bit."""
+    n, B = 3, 5
+    flat, sup, obs, noise, tie, u, mm, ref = _epilogue_case(oracle, S, T, det)
+    eng = _engine(mzh, n, S, B, sup, flat)
+    tt = lambda a: torch.tensor(np.asarray(a), device=DEV)
+    kw = dict(obs=tt(obs), tie_idx=tt(tie), noise=tt(noise), action_u=tt(u), minmax_in=tt(mm), temperature=T,
+              deterministic=det, kernel=kernel, tile=tile)
+    if kernel in ("occ2", "one") and not _forced_fits(kernel, sup, S):
+        # a forced kernel that cannot serve the search is an error, never a silent fallback (mzh.h)
+        assert S != 8, "every kernel serves an 8-simulation search"
+        with pytest.raises(RuntimeError, match="MZH_FLAG_COOP_OCC2" if kernel == "occ2" else "MZH_FLAG_KERNEL_ONE"):
+            eng.search(S, **kw)
+        eng.close()
+        return
+    o = eng.search(S, **kw)
+    o = {k: v.cpu().numpy() for k, v in o.items() if not k.startswith("_")}
+    eng.close()
+    for k, want in (("visits", ref["visits"]), ("pi", ref["pi"]), ("action", ref["action"]), ("root_q", ref["rootQ"]),
+                    ("minmax", np.stack([ref["mm_max"], ref["mm_min"]], 1)), ("extra_ties", ref["extra_ties"]),
+                    ("sel_steps", ref["sel_steps"]), ("latent", ref["latent"]), ("latent_len", ref["latent_len"])):
+        assert np.array_equal(o[k], want), k
+
+
 @pytest.mark.parametrize("B,S,n,td", [(40000, 50, 4, 1), (33000, 12, 3, 0)])
 def test_search_wave_equals_coop_large_batch(mzh, oracle, B, S, n, td):
     """At the bench's batch sizes the two kernels agree on every output, bit for bit (ragged last
