@@ -15,7 +15,8 @@
 //
 // Schedule variants measured and not shipped (numbers in DESIGN.md §6/§8): an explicit ping-pong of
 // the two waves per SIMD, software-pipelined MLP chains, LDS parking of the tree statistics,
-// laundered weight pointers, cached child values in the tree block, a register reciprocal.  The
+// laundered weight pointers, cached child values in the tree block, a register reciprocal, a touch of the leaf's parent latent
+// at the end of a root's walk.  The
 // child-block prefetch in selection is shipped for 16-root waves only (neutral at 32 roots per wave).
 //
 // Reference: MCTS/mcts.py:34-126 (run_mcts), MCTS/node.py:30-136 (expand/backup/best_child),
@@ -117,9 +118,11 @@ __device__ __forceinline__ floatx4 mzw_ld4(__amdgpu_buffer_rsrc_t r, int voff, i
 // Chained form (WS > 0): the rolling buffer is the caller's wst[WS], which arrives holding this chain's
 // block 0 (loaded by the previous chain), and the last block's refills load the NEXT chain's block 0
 // (fragments 0..WS-1 at byte offset next_soff) instead of the zero pad, so no chain starts on an L2 round trip.
+// b2[NO]: layer 2's bias fragments for mzw_bias2, loaded ahead of the hidden blocks so that the chain does not
+// end on a load and its use (16,384 roots x 200 simulations -1.7%; 65,536 roots neutral)
 template <int NT, int KB1, int NO, bool OH, bool B32 = false, int WS = 0>
 __device__ __forceinline__ void mzw_chain(const MzhWMlp& L, __amdgpu_buffer_rsrc_t rw, const floatx4 (&x)[NT][4],
-                                          const float* const (&oh)[NT], floatx4 (&out)[NO][NT], int lane,
+                                          const float* const (&oh)[NT], floatx4 (&out)[NO][NT], floatx4* b2, int lane,
                                           float* p32 = nullptr, floatx4* wst = nullptr, int next_soff = 0) {
   constexpr int FR = KB1 + NO;
   static_assert(WS == 0 || WS >= FR, "chained buffer too small");
@@ -139,6 +142,8 @@ __device__ __forceinline__ void mzw_chain(const MzhWMlp& L, __amdgpu_buffer_rsrc
 #pragma unroll
     for (int f = 0; f < FR; ++f) w[f] = mzw_ld4(rw, vs, L.soff + f * 1024);
   }
+#pragma unroll
+  for (int ot = 0; ot < NO; ++ot) b2[ot] = mzw_ld4(rw, vb, L.b2off + 64 * ot);
   float a32[NT];
 #pragma unroll
   for (int n = 0; n < NT; ++n) a32[n] = 0.0f;
@@ -187,6 +192,11 @@ __device__ __forceinline__ void mzw_chain(const MzhWMlp& L, __amdgpu_buffer_rsrc
       if (B32) {
 #pragma unroll
         for (int n = 0; n < NT; ++n) a32[n] = __builtin_fmaf(hid[n][t], w32[t], a32[n]);
+        // keep the column tiles' chains apart for the SLP vectoriser: paired, they become one v_pk_fma_f32
+        // fed by register-pair moves (28 VALU + 16 v_mov + 10 v_pk_* per two hidden blocks instead of 48 VALU),
+        // which costs more beside the MFMAs (65,536 roots -0.7%).  -fno-slp-vectorize for the file also
+        // unpacks the heads, where the packed form is the cheaper one (16,384 roots x 200 simulations +0.6%)
+        if (NT > 1) asm("" : "+v"(a32[0]));
       }
     }
 #pragma unroll
@@ -204,10 +214,10 @@ __device__ __forceinline__ void mzw_chain(const MzhWMlp& L, __amdgpu_buffer_rsrc
 }
 
 template <int NT, int NO>
-__device__ __forceinline__ void mzw_bias2(const MzhWMlp& L, __amdgpu_buffer_rsrc_t rw, floatx4 (&out)[NO][NT], int g) {
+__device__ __forceinline__ void mzw_bias2(floatx4 (&out)[NO][NT], const floatx4* b2) {  // b2: from mzw_chain
 #pragma unroll
   for (int ot = 0; ot < NO; ++ot) {
-    const floatx4 b = mzw_ld4(rw, 16 * g, L.b2off + 64 * ot);
+    const floatx4 b = b2[ot];
 #pragma unroll
     for (int n = 0; n < NT; ++n)
 #pragma unroll
@@ -231,11 +241,30 @@ __device__ __forceinline__ void mzw_normalize(const floatx4 (&hp)[4][NT], int n,
   mx = mzw_max4g(mx);
   const float d = (mx - mn) + 9.999999939225290290778502821922302246094e-09f;
   const float y = 1.0f / d;
-  bool slow = false;
+  // mzh_fdiv's quotients with its exactness test decided once per lane instead of once per element
+  // (per column tile ~50 VALU and ~30 SALU less; 65,536 roots -0.8%).  An element flags `slow` when its
+  // numerator a is non-zero and a < 2^-100 or its Markstein quotient res < 2^-100.  For a finite d,
+  // res < 2^-100 implies a < 2^-99 d: if a >= 2^-100 and a >= 2^-99 d, then y = RN(1/d) is within a
+  // relative 2^-22 of 1/d (2^-24 while y is normal), so q = RN(a y) >= 2^-99 (1 - 2^-21) is normal, the
+  // residual r = RN(a - q d) is at most 2^-20 a in magnitude, |r y| <= 2^-19 q, and res = RN(q + r y) >=
+  // q (1 - 2^-18) > 2^-100.  An infinite d gives res = NaN, which compares false: only a < 2^-100 flags.
+  // So every flagged element has 0 < a < lim, and the lane's smallest non-zero numerator decides.  A lane
+  // that this test flags and the per-element test would not only sends the wave to the IEEE rerun, which
+  // gives the same bits wherever the Markstein form is exact.  Numerators are >= +0 (v - mn with mn the
+  // column's minimum) or NaN, so the order of the non-NaN ones is that of their bit patterns, a NaN's
+  // pattern lies above lim's (no flag, as in mzh_fdiv), and bits - 1 sends 0 above every pattern.
+  const float lim = __builtin_fmaxf(d < __builtin_inff() ? d * 0x1p-99f : 0.0f, 0x1p-100f);
+  unsigned amin = 0xFFFFFFFFu;
 #pragma unroll
   for (int ot = 0; ot < 4; ++ot)
 #pragma unroll
-    for (int i = 0; i < 4; ++i) hn[n][ot][i] = mzh_fdiv(hp[ot][n][i] - mn, d, y, slow);
+    for (int i = 0; i < 4; ++i) {
+      const float a = hp[ot][n][i] - mn;
+      amin = min(amin, __float_as_uint(a) - 1u);
+      const float q = a * y;
+      hn[n][ot][i] = __builtin_fmaf(__builtin_fmaf(-q, d, a), y, q);
+    }
+  const bool slow = amin < __float_as_uint(lim) - 1u;
   if (__builtin_expect(__ballot(slow) != 0, 0)) {
 #pragma unroll
     for (int ot = 0; ot < 4; ++ot)
@@ -462,13 +491,14 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
           x[n][kb][t] = (cvalid[n] && k < p.in_dim) ? p.obs[(size_t)croot[n] * p.in_dim + k] : 0.0f;
         }
     floatx4 hp[4][NT];
+    floatx4 b2[4];  // a chain's layer-2 bias fragments, loaded by the chain (mzw_chain b2)
     switch (net.rep.kb1) {
-      case 1: mzw_chain<NT, 1, 4, false>(net.rep, rw, x, noh, hp, lane); break;
-      case 2: mzw_chain<NT, 2, 4, false>(net.rep, rw, x, noh, hp, lane); break;
-      case 3: mzw_chain<NT, 3, 4, false>(net.rep, rw, x, noh, hp, lane); break;
-      default: mzw_chain<NT, 4, 4, false>(net.rep, rw, x, noh, hp, lane); break;
+      case 1: mzw_chain<NT, 1, 4, false>(net.rep, rw, x, noh, hp, b2, lane); break;
+      case 2: mzw_chain<NT, 2, 4, false>(net.rep, rw, x, noh, hp, b2, lane); break;
+      case 3: mzw_chain<NT, 3, 4, false>(net.rep, rw, x, noh, hp, b2, lane); break;
+      default: mzw_chain<NT, 4, 4, false>(net.rep, rw, x, noh, hp, b2, lane); break;
     }
-    mzw_bias2<NT, 4>(net.rep, rw, hp, g);
+    mzw_bias2<NT, 4>(hp, b2);
 #pragma unroll
     for (int n = 0; n < NT; ++n) {
       mzw_normalize<NT>(hp, n, hreg);
@@ -479,10 +509,10 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
       }
     }
     floatx4 pl[1][NT];
-    mzw_chain<NT, 4, 1, false>(net.pol, rw, hreg, noh, pl, lane);
-    mzw_bias2<NT, 1>(net.pol, rw, pl, g);
+    mzw_chain<NT, 4, 1, false>(net.pol, rw, hreg, noh, pl, b2, lane);
+    mzw_bias2<NT, 1>(pl, b2);
     floatx4 vl[NOV][NT];
-    mzw_chain<NT, 4, NOV, false>(net.val, rw, hreg, noh, vl, lane);  // root value: computed, unused (mcts.py:50)
+    mzw_chain<NT, 4, NOV, false>(net.val, rw, hreg, noh, vl, b2, lane);  // root value: computed, unused (mcts.py:50)
     (void)vl;
 #pragma unroll
     for (int n = 0; n < NT; ++n) rpi[n] = mzw_policy(pl[0][n], lane);
@@ -523,7 +553,7 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
 #pragma unroll
     for (int f = 0; f < 8; ++f) wst[f] = mzw_ld4(rw, 16 * lane, net.dyn.soff + f * 1024);
   }
-  MZH_STAMP_DECL  // diagnostic build: phase stamps (the M phase's are 5-9, see tools/wave_probe.py)
+  MZH_STAMP_DECL  // diagnostic build: phase stamps per simulation (MZH_STAMP 0-11, read by tools/wave_stamps.py)
   // select one leaf per root, then hand its parent latent index / move to the column lanes
   // ex: MzhBool<true> = the exact (IEEE-division) normaliser, for a wave where some root's max - min
   // is a non-zero subnormal (caller-given bounds only); chosen once per selection
@@ -554,6 +584,8 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
       // (65,536 roots: neutral), so NT = 2 leaves the load queue to the block loads
       constexpr bool kPF = NT == 1;
       int pf0 = 0, pf1 = 0, pf2 = 0;
+      // (a root lane touching its leaf's parent latent when its walk ends, ahead of the M phase's gather,
+      // measured slower: 65,536 roots +0.6%, 16,384 roots x 200 simulations +3.7%)
       while (X >= 0 && d <= S) {  // depth <= s + 1 always; the bound only guards against a corrupt tree
         e = X;
         int nx;
@@ -664,8 +696,9 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
 #pragma unroll
     for (int n = 0; n < NT; ++n) ohp[n] = ohl + an[n] * MZH_F + 4 * g;
     MZH_STAMP(10);  // latent gather
-    mzw_chain<NT, 4, 4, true, false, 8>(net.dyn, rw, x, ohp, hp, lane, nullptr, wst, net.rwd.soff);
-    mzw_bias2<NT, 4>(net.dyn, rw, hp, g);  // h' (un-normalised, networks.py:129-138)
+    floatx4 b2[4];  // a chain's layer-2 bias fragments, loaded by the chain (mzw_chain b2)
+    mzw_chain<NT, 4, 4, true, false, 8>(net.dyn, rw, x, ohp, hp, b2, lane, nullptr, wst, net.rwd.soff);
+    mzw_bias2<NT, 4>(hp, b2);  // h' (un-normalised, networks.py:129-138)
     MZH_STAMP(5);
     floatx4 hx[NT][4];
 #pragma unroll
@@ -673,8 +706,8 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
 #pragma unroll
       for (int kb = 0; kb < 4; ++kb) hx[n][kb] = hp[kb][n];
     float r32[NT], v32[NT];
-    mzw_chain<NT, 4, NOV, false, SUP33, 8>(net.rwd, rw, hx, noh, rl, lane, r32, wst, net.pol.soff);  // reward from h' (networks.py:132-135)
-    mzw_bias2<NT, NOV>(net.rwd, rw, rl, g);
+    mzw_chain<NT, 4, NOV, false, SUP33, 8>(net.rwd, rw, hx, noh, rl, b2, lane, r32, wst, net.pol.soff);  // reward from h' (networks.py:132-135)
+    mzw_bias2<NT, NOV>(rl, b2);
     MZH_STAMP(6);
 #pragma unroll
     for (int n = 0; n < NT; ++n) rew[n] = mzw_head<NT, NOV>(rl, n, lane, SUP33 ? r32[n] : 0.0f, net.rwd.b32);
@@ -689,13 +722,13 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
       }
     }
     MZH_STAMP(7);
-    mzw_chain<NT, 4, 1, false, false, 8>(net.pol, rw, hreg, noh, pl, lane, nullptr, wst, net.val.soff);
-    mzw_bias2<NT, 1>(net.pol, rw, pl, g);
+    mzw_chain<NT, 4, 1, false, false, 8>(net.pol, rw, hreg, noh, pl, b2, lane, nullptr, wst, net.val.soff);
+    mzw_bias2<NT, 1>(pl, b2);
 #pragma unroll
     for (int n = 0; n < NT; ++n) cpi[n] = mzw_policy(pl[0][n], lane);
     MZH_STAMP(8);
-    mzw_chain<NT, 4, NOV, false, SUP33, 8>(net.val, rw, hreg, noh, vl, lane, v32, wst, net.dyn.soff);  // + next dyn block 0
-    mzw_bias2<NT, NOV>(net.val, rw, vl, g);
+    mzw_chain<NT, 4, NOV, false, SUP33, 8>(net.val, rw, hreg, noh, vl, b2, lane, v32, wst, net.dyn.soff);  // + next dyn block 0
+    mzw_bias2<NT, NOV>(vl, b2);
     MZH_STAMP(9);
 #pragma unroll
     for (int n = 0; n < NT; ++n) val[n] = mzw_head<NT, NOV>(vl, n, lane, SUP33 ? v32[n] : 0.0f, net.val.b32);

@@ -2,6 +2,8 @@
 fused search (REPLAY = false) and its replay / tree-only instantiation (REPLAY = true) -- the
 rocprofv3 average duration and the per-launch PMC values, HBM bytes corrected as
 MI355X_MICROARCH.md prescribes (FETCH_SIZE x 2 on gfx950, WRITE_SIZE as is; both in KB).
+A further pass written beside prof.sh's as prof_<tag>_valu (rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU
+of the same command, in a run of its own) is summarised too when it is there.
 
   python tools/traffic.py gpurun_out TAG [--traffic-json profiles/traffic_latest.json]
 """
@@ -47,7 +49,7 @@ def summarise(root, tag, want=None):
                 out["other"][r["Name"]] = {"calls": int(r["Calls"]), "avg_ns": float(r["AverageNs"])}
             elif k:
                 out[k].update(kernel=r["Name"], calls=int(r["Calls"]), avg_ns=float(r["AverageNs"]))
-    for p in ("hit", "fetch", "write", "sq"):
+    for p in ("hit", "fetch", "write", "sq", "valu"):
         f = newest(root, f"prof_{tag}_{p}/*/*_counter_collection.csv") or newest(root, f"prof_{tag}_{p}/*_counter_collection.csv")
         if not f:
             continue
