@@ -18,9 +18,10 @@ LIB = os.path.join(HERE, "libmzh.so")
 OBJ = os.path.join(HERE, "_obj")
 SOURCES = ["mzh_api.hip", "mzh_search.hip", "mzh_wave.hip", "mzh_one.hip", "mzh_env.hip", "mzh_train.hip",
            "mzh_replay.hip", "mzh_ingest.hip"]
-# host-only sources, compiled by g++ like the NumPy C code they restate (no -march: no FMA; see
-# csrc/mzh_rng.cpp)
-HOST_SOURCES = ["mzh_rng.cpp"]
+# host-only sources, compiled by g++: mzh_rng.cpp like the NumPy C code it restates (no -march: no FMA;
+# see csrc/mzh_rng.cpp), mzh_pack.cpp (the weight packers: copies only, no HIP) so that a plain C++
+# program can link and check it (tests/pack_check.cpp)
+HOST_SOURCES = ["mzh_rng.cpp", "mzh_pack.cpp"]
 HOST_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("MZH_OFFLOAD_ARCH", "gfx950")

@@ -1,5 +1,6 @@
 // mzh_api.hip -- C ABI (include/mzh.h) over the gfx950 kernels.  No exceptions cross the ABI;
-// every entry point returns a status and records a thread-local message.
+// every entry point returns a status and records a thread-local message.  The weight layouts are
+// packed on the host by mzh_pack.cpp; mzh_load_weights uploads the blob and turns offsets into pointers.
 #include <math.h>
 #include <stdlib.h>
 #include <stdarg.h>
@@ -90,21 +91,10 @@ extern "C" int mzh_stream_synchronize(void* stream) {
   return e == hipSuccess ? MZH_OK : hip_fail(e, "hipStreamSynchronize");
 }
 
-static size_t canonical_size(int in_dim, int support) {
-  const size_t H = MZH_LATENT, F = MZH_HIDDEN, A = MZH_ACTIONS;
-  size_t s = 0;
-  s += F * in_dim + F + H * F + H;
-  s += F * (H + A) + F + H * F + H;
-  s += F * H + F + (size_t)support * F + support;
-  s += F * H + F + A * F + A;
-  s += F * H + F + (size_t)support * F + support;
-  return s;
-}
-
 extern "C" int mzh_weights_size(int n_disks, int support, size_t* n_floats) {
   if (n_disks < 1 || n_disks > 16 || (support != 33 && support != 1) || !n_floats)
     return fail(MZH_ERR_ARG, "bad n_disks=%d / support=%d", n_disks, support);
-  *n_floats = canonical_size(3 * n_disks, support);
+  *n_floats = mzh_canon_view(nullptr, 3 * n_disks, support).total;
   return MZH_OK;
 }
 
@@ -163,255 +153,12 @@ extern "C" int mzh_destroy(mzh_engine* eng) {
   return MZH_OK;
 }
 
-// ---- weight packing: torch [N][K] -> MFMA fragment tiles (see MzhLayer in mzh_device.h) ----
-struct PackedLayer {
-  size_t woff = 0, boff = 0;  // float offsets into the device buffer
-  int kb = 0, nt = 0;
-};
-
-static void pack_weights(std::vector<float>& buf, PackedLayer& L, const float* W, int N, int K, int ldw) {
-  L.nt = (N + 15) / 16;
-  L.kb = (K + 15) / 16;
-  while (buf.size() % 4) buf.push_back(0.0f);
-  L.woff = buf.size();
-  buf.resize(buf.size() + (size_t)L.nt * L.kb * 64 * 4, 0.0f);
-  float* dst = buf.data() + L.woff;
-  for (int nt = 0; nt < L.nt; ++nt)
-    for (int kb = 0; kb < L.kb; ++kb)
-      for (int lane = 0; lane < 64; ++lane)
-        for (int j = 0; j < 4; ++j) {
-          const int n = 16 * nt + (lane & 15);
-          const int k = 16 * kb + 4 * j + (lane >> 4);
-          dst[(((size_t)nt * L.kb + kb) * 64 + lane) * 4 + j] = (n < N && k < K) ? W[(size_t)n * ldw + k] : 0.0f;
-        }
-}
-static void pack_bias(std::vector<float>& buf, PackedLayer& L, const float* b, int N) {
-  while (buf.size() % 4) buf.push_back(0.0f);
-  L.boff = buf.size();
-  buf.resize(buf.size() + (size_t)L.nt * 16, 0.0f);
-  for (int n = 0; n < N; ++n) buf[L.boff + n] = b[n];
-}
-static PackedLayer pack_layer(std::vector<float>& buf, const float* W, const float* b, int N, int K, int ldw) {
-  PackedLayer L;
-  pack_weights(buf, L, W, N, K, ldw);
-  pack_bias(buf, L, b, N);
-  return L;
-}
-
-// ---- wave-kernel packing (MzhWMlp, mzh_internal.h): weights as the MFMA A operand ----
-static int wperm_u(int ht, int r) { return 16 * ht + 4 * (r & 3) + (r >> 2); }
-enum WOut { WOUT_LATENT, WOUT_HEAD33, WOUT_NATURAL };
-// output unit held by C row r (= 4g + i) of output tile ot, -1 for a padding row
-static int wperm_out(WOut kind, int ot, int r, int n_out) {
-  if (kind == WOUT_LATENT) return wperm_u(ot, r);
-  if (kind == WOUT_HEAD33) {
-    const int g = r >> 2, i = r & 3, sl = 4 * ot + i;
-    const int k = 2 * g + (sl & 1) + 8 * (sl >> 1);  // partial q = 2g + (sl & 1), term sl >> 1
-    return k < n_out ? k : -1;
-  }
-  const int k = 16 * ot + r;
-  return k < n_out ? k : -1;
-}
-struct PackedW {
-  size_t soff = 0, b1off = 0, b2off = 0, w32off = 0;
-  float b32 = 0.0f;
-  int kb1 = 0, no = 0;
-};
-
-// bin 32 of a 33-bin head (MzhNet::rwd32 / MzhWMlp::w32): [16 blocks b][4 chains g] float4
-// {W2[32][16b + g], W2[32][16b + 4 + g], W2[32][16b + 8 + g], W2[32][16b + 12 + g]}
-static size_t pack_bin32(std::vector<float>& buf, const float* W2) {
-  while (buf.size() % 4) buf.push_back(0.0f);
-  const size_t off = buf.size();
-  buf.resize(buf.size() + 16 * 4 * 4, 0.0f);
-  const float* row = W2 + (size_t)32 * MZH_HIDDEN;
-  for (int b = 0; b < 16; ++b)
-    for (int g = 0; g < 4; ++g)
-      for (int t = 0; t < 4; ++t) buf[off + (size_t)(b * 4 + g) * 4 + t] = row[16 * b + 4 * t + g];
-  return off;
-}
-static PackedW pack_wmlp(std::vector<float>& buf, const float* W1, const float* b1, int K1, int ldw1, const float* W2,
-                         const float* b2, int n_out, WOut kind) {
-  PackedW P;
-  P.kb1 = (K1 + 15) / 16;
-  // a 33-bin head keeps bins 0..31 in two tiles; bin 32 goes to the vector chains (pack_bin32)
-  P.no = kind == WOUT_HEAD33 ? 2 : (n_out + 15) / 16;
-  const int FR = P.kb1 + P.no;
-  while (buf.size() % 4) buf.push_back(0.0f);
-  P.soff = buf.size();
-  buf.resize(buf.size() + (size_t)17 * FR * 64 * 4, 0.0f);  // ht block 16 = zero pad
-  float* s = buf.data() + P.soff;
-  for (int ht = 0; ht < 16; ++ht)
-    for (int lane = 0; lane < 64; ++lane)
-      for (int t = 0; t < 4; ++t) {
-        const int r = lane & 15, gk = lane >> 4;
-        for (int kb = 0; kb < P.kb1; ++kb) {
-          const int k = 16 * kb + 4 * t + gk;
-          s[(((size_t)ht * FR + kb) * 64 + lane) * 4 + t] = k < K1 ? W1[(size_t)wperm_u(ht, r) * ldw1 + k] : 0.0f;
-        }
-        for (int ot = 0; ot < P.no; ++ot) {
-          const int row = wperm_out(kind, ot, r, n_out);
-          const int k = 16 * ht + 4 * t + gk;
-          s[(((size_t)ht * FR + P.kb1 + ot) * 64 + lane) * 4 + t] = row >= 0 ? W2[(size_t)row * MZH_HIDDEN + k] : 0.0f;
-        }
-      }
-  P.b1off = buf.size();
-  buf.resize(buf.size() + MZH_HIDDEN, 0.0f);
-  for (int ht = 0; ht < 16; ++ht)
-    for (int r = 0; r < 16; ++r) buf[P.b1off + 16 * ht + r] = b1[wperm_u(ht, r)];
-  P.b2off = buf.size();
-  buf.resize(buf.size() + (size_t)16 * P.no, 0.0f);
-  for (int ot = 0; ot < P.no; ++ot)
-    for (int r = 0; r < 16; ++r) {
-      const int row = wperm_out(kind, ot, r, n_out);
-      buf[P.b2off + 16 * ot + r] = row >= 0 ? b2[row] : 0.0f;
-    }
-  while (buf.size() % 4) buf.push_back(0.0f);
-  if (kind == WOUT_HEAD33) {
-    P.w32off = pack_bin32(buf, W2);
-    P.b32 = b2[32];
-  }
-  return P;
-}
-
-// ---- latency-path packing (MzhOneNet, mzh_internal.h): float offsets of its arrays in the blob ----
-struct PackedOne {
-  size_t l1 = 0, b1 = 0, rep0 = 0, rep0b = 0, rep2 = 0, rep2b = 0, l2 = 0;
-};
-static PackedOne pack_one(std::vector<float>& buf, int in, int sup, const float* rep0w, const float* rep0b,
-                          const float* rep2w, const float* rep2b, const float* dyn0w, const float* dyn0b,
-                          const float* dyn2w, const float* dyn2b, const float* rwd0w, const float* rwd0b,
-                          const float* rwd2w, const float* rwd2b, const float* pol0w, const float* pol0b,
-                          const float* pol2w, const float* pol2b, const float* val0w, const float* val0b,
-                          const float* val2w, const float* val2b) {
-  const int H = MZH_LATENT, F = MZH_HIDDEN, A = MZH_ACTIONS;
-  auto align4 = [&]() { while (buf.size() % 4) buf.push_back(0.0f); };
-  PackedOne o;
-  // l1 [66 k4][256 units] float4
-  align4();
-  o.l1 = buf.size();
-  buf.resize(buf.size() + (size_t)66 * F * 4, 0.0f);
-  for (int k4 = 0; k4 < 66; ++k4)
-    for (int u = 0; u < F; ++u)
-      for (int i = 0; i < 4; ++i) {
-        float v = 0.0f;
-        if (k4 < 16) v = dyn0w[(size_t)u * (H + A) + 4 * k4 + i];
-        else if (k4 < 32) v = rwd0w[(size_t)u * H + 4 * (k4 - 16) + i];
-        else if (k4 < 48) v = pol0w[(size_t)u * H + 4 * (k4 - 32) + i];
-        else if (k4 < 64) v = val0w[(size_t)u * H + 4 * (k4 - 48) + i];
-        else if (4 * (k4 - 64) + i < A) v = dyn0w[(size_t)u * (H + A) + H + 4 * (k4 - 64) + i];
-        buf[o.l1 + ((size_t)k4 * F + u) * 4 + i] = v;
-      }
-  o.b1 = buf.size();
-  buf.resize(buf.size() + (size_t)F * 4);
-  for (int u = 0; u < F; ++u) {
-    buf[o.b1 + 4 * u] = dyn0b[u];
-    buf[o.b1 + 4 * u + 1] = rwd0b[u];
-    buf[o.b1 + 4 * u + 2] = pol0b[u];
-    buf[o.b1 + 4 * u + 3] = val0b[u];
-  }
-  // representation_net.0 k-major [in][256], its bias; representation_net.2 [64 k4][64] float4, its bias
-  o.rep0 = buf.size();
-  buf.resize(buf.size() + (size_t)in * F);
-  for (int k = 0; k < in; ++k)
-    for (int u = 0; u < F; ++u) buf[o.rep0 + (size_t)k * F + u] = rep0w[(size_t)u * in + k];
-  o.rep0b = buf.size();
-  buf.insert(buf.end(), rep0b, rep0b + F);
-  align4();
-  o.rep2 = buf.size();
-  buf.resize(buf.size() + (size_t)64 * 64 * 4);
-  for (int k4 = 0; k4 < 64; ++k4)
-    for (int j = 0; j < 64; ++j)
-      for (int i = 0; i < 4; ++i) buf[o.rep2 + ((size_t)k4 * 64 + j) * 4 + i] = rep2w[(size_t)j * F + 4 * k4 + i];
-  o.rep2b = buf.size();
-  buf.insert(buf.end(), rep2b, rep2b + H);
-  // the LDS image
-  align4();
-  o.l2 = buf.size();
-  buf.resize(buf.size() + (size_t)MZH_ONE_L2F4 * 4, 0.0f);
-  float* L = buf.data() + o.l2;
-  const int nb = sup < 32 ? sup : 32;  // bins of each head in the A2 rows
-  for (int k4 = 0; k4 < 64; ++k4)
-    for (int j = 0; j < 64; ++j)
-      for (int i = 0; i < 4; ++i) {
-        const int k = 4 * k4 + i;
-        L[((size_t)MZH_ONE_D2 + k4 * 64 + j) * 4 + i] = dyn2w[(size_t)j * F + k];
-        const int row = j & 31;
-        const float* W2 = j < 32 ? rwd2w : val2w;
-        L[((size_t)MZH_ONE_A2 + k4 * 64 + j) * 4 + i] = row < nb ? W2[(size_t)row * F + k] : 0.0f;
-        if (j < 8) L[((size_t)MZH_ONE_P2 + k4 * 8 + j) * 4 + i] = j < A ? pol2w[(size_t)j * F + k] : 0.0f;
-      }
-  if (sup == 33)
-    for (int i = 0; i < 64; ++i)
-      for (int ln = 0; ln < 8; ++ln) {
-        const float* W2 = ln < 4 ? rwd2w : val2w;
-        L[(size_t)MZH_ONE_C32 * 4 + ln * 64 + i] = W2[(size_t)32 * F + (ln & 3) + 4 * i];
-      }
-  float* B2 = L + (size_t)MZH_ONE_B2 * 4;
-  for (int j = 0; j < 64; ++j) {
-    B2[j] = dyn2b[j];
-    B2[64 + j] = (j & 31) < nb ? (j < 32 ? rwd2b : val2b)[j & 31] : 0.0f;
-  }
-  for (int j = 0; j < A; ++j) B2[128 + j] = pol2b[j];
-  if (sup == 33) {
-    B2[136] = rwd2b[32];
-    B2[137] = val2b[32];
-  }
-  return o;
-}
-
 extern "C" int mzh_load_weights(mzh_engine* eng, const float* flat, size_t n_floats) {
   if (!eng || !flat) return fail(MZH_ERR_ARG, "engine or weights NULL");
-  const size_t want = canonical_size(eng->in_dim, eng->support);
+  const int in = eng->in_dim, sup = eng->support;
+  const size_t want = mzh_canon_view(nullptr, in, sup).total;
   if (n_floats != want) return fail(MZH_ERR_ARG, "weights: expected %zu floats, got %zu", want, n_floats);
-  const int H = MZH_LATENT, F = MZH_HIDDEN, A = MZH_ACTIONS, in = eng->in_dim, sup = eng->support;
-  const float* p = flat;
-  auto take = [&](size_t n) { const float* q = p; p += n; return q; };
-  const float *rep0w = take((size_t)F * in), *rep0b = take(F), *rep2w = take((size_t)H * F), *rep2b = take(H);
-  const float *dyn0w = take((size_t)F * (H + A)), *dyn0b = take(F), *dyn2w = take((size_t)H * F), *dyn2b = take(H);
-  const float *rwd0w = take((size_t)F * H), *rwd0b = take(F), *rwd2w = take((size_t)sup * F), *rwd2b = take(sup);
-  const float *pol0w = take((size_t)F * H), *pol0b = take(F), *pol2w = take((size_t)A * F), *pol2b = take(A);
-  const float *val0w = take((size_t)F * H), *val0b = take(F), *val2w = take((size_t)sup * F), *val2b = take(sup);
-
-  std::vector<float> buf;
-  buf.reserve(200000);
-  PackedLayer L[10];
-  L[0] = pack_layer(buf, rep0w, rep0b, F, in, in);
-  L[1] = pack_layer(buf, rep2w, rep2b, H, F, F);
-  L[2] = pack_layer(buf, dyn0w, dyn0b, F, H, H + A);  // h part only (k < 64)
-  L[3] = pack_layer(buf, dyn2w, dyn2b, H, F, F);
-  L[4] = pack_layer(buf, rwd0w, rwd0b, F, H, H);
-  // 33-bin heads: bins 0..31 as MFMA tiles, bin 32 by vector chains (MzhNet::rwd32 / val32)
-  const int nhead = sup == 33 ? 32 : sup;
-  L[5] = pack_layer(buf, rwd2w, rwd2b, nhead, F, F);
-  // pol0 and val0 weights back to back: the search kernel's prediction chunks take consecutive
-  // tiles of this 32-tile strip and load them as one contiguous run (mzh_mma_store ring refill)
-  pack_weights(buf, L[6], pol0w, F, H, H);
-  pack_weights(buf, L[8], val0w, F, H, H);
-  pack_bias(buf, L[6], pol0b, F);
-  pack_bias(buf, L[8], val0b, F);
-  L[7] = pack_layer(buf, pol2w, pol2b, A, F, F);
-  L[9] = pack_layer(buf, val2w, val2b, nhead, F, F);
-  while (buf.size() % 4) buf.push_back(0.0f);
-  const size_t ohoff = buf.size();
-  buf.resize(buf.size() + (size_t)A * F);
-  for (int a = 0; a < A; ++a)
-    for (int n = 0; n < F; ++n) buf[ohoff + (size_t)a * F + n] = dyn0w[(size_t)n * (H + A) + H + a];
-  // wave-kernel layout
-  const WOut vkind = sup == 33 ? WOUT_HEAD33 : WOUT_NATURAL;
-  PackedW WL[5];
-  WL[0] = pack_wmlp(buf, rep0w, rep0b, in, in, rep2w, rep2b, H, WOUT_LATENT);
-  WL[1] = pack_wmlp(buf, dyn0w, dyn0b, H, H + A, dyn2w, dyn2b, H, WOUT_LATENT);
-  WL[2] = pack_wmlp(buf, rwd0w, rwd0b, H, H, rwd2w, rwd2b, sup, vkind);
-  WL[3] = pack_wmlp(buf, pol0w, pol0b, H, H, pol2w, pol2b, A, WOUT_NATURAL);
-  WL[4] = pack_wmlp(buf, val0w, val0b, H, H, val2w, val2b, sup, vkind);
-  const size_t wohoff = buf.size();
-  buf.resize(buf.size() + (size_t)A * F, 0.0f);
-  for (int a = 0; a < A; ++a)
-    for (int j = 0; j < F; ++j) buf[wohoff + (size_t)a * F + j] = dyn0w[(size_t)wperm_u(j >> 4, j & 15) * (H + A) + H + a];
-  // latency-path layout
-  const PackedOne PO = pack_one(buf, in, sup, rep0w, rep0b, rep2w, rep2b, dyn0w, dyn0b, dyn2w, dyn2b, rwd0w, rwd0b,
-                                rwd2w, rwd2b, pol0w, pol0b, pol2w, pol2b, val0w, val0b, val2w, val2b);
+  const MzhPacked pk = mzh_pack_network(mzh_canon_view(flat, in, sup));
 
   DeviceGuard g(eng->device);
   if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
@@ -421,8 +168,8 @@ extern "C" int mzh_load_weights(mzh_engine* eng, const float* flat, size_t n_flo
     eng->wbuf = nullptr;
     eng->loaded = false;
   }
-  HIP_OK(hipMalloc(&eng->wbuf, buf.size() * sizeof(float)));
-  HIP_OK(hipMemcpy(eng->wbuf, buf.data(), buf.size() * sizeof(float), hipMemcpyHostToDevice));
+  HIP_OK(hipMalloc(&eng->wbuf, pk.blob.size() * sizeof(float)));
+  HIP_OK(hipMemcpy(eng->wbuf, pk.blob.data(), pk.blob.size() * sizeof(float), hipMemcpyHostToDevice));
   const float* base = static_cast<const float*>(eng->wbuf);
   auto mk = [&](const PackedLayer& pl) {
     MzhLayer m;
@@ -436,19 +183,12 @@ extern "C" int mzh_load_weights(mzh_engine* eng, const float* flat, size_t n_flo
   };
   MzhNet& n = eng->net;
   n.wbase = base;
-  n.rep0 = mk(L[0]); n.rep2 = mk(L[1]); n.dyn0 = mk(L[2]); n.dyn2 = mk(L[3]); n.rwd0 = mk(L[4]);
-  n.rwd2 = mk(L[5]); n.pol0 = mk(L[6]); n.pol2 = mk(L[7]); n.val0 = mk(L[8]); n.val2 = mk(L[9]);
+  n.rep0 = mk(pk.L[MZH_REP0]); n.rep2 = mk(pk.L[MZH_REP2]); n.dyn0 = mk(pk.L[MZH_DYN0]); n.dyn2 = mk(pk.L[MZH_DYN2]);
+  n.rwd0 = mk(pk.L[MZH_RWD0]); n.rwd2 = mk(pk.L[MZH_RWD2]); n.pol0 = mk(pk.L[MZH_POL0]); n.pol2 = mk(pk.L[MZH_POL2]);
+  n.val0 = mk(pk.L[MZH_VAL0]); n.val2 = mk(pk.L[MZH_VAL2]);
   if (n.val0.w != n.pol0.w + (size_t)n.pol0.nt * n.pol0.kb * 64)
     return fail(MZH_ERR_STATE, "pol0/val0 weights not contiguous");
-  n.dyn0_onehot = base + ohoff;
-  n.rwd32 = n.val32 = nullptr;
-  n.rwd32b = n.val32b = 0.0f;
-  if (sup == 33) {  // the wave layout's bin-32 arrays serve both kernels
-    n.rwd32 = reinterpret_cast<const float4*>(base + WL[2].w32off);
-    n.val32 = reinterpret_cast<const float4*>(base + WL[4].w32off);
-    n.rwd32b = WL[2].b32;
-    n.val32b = WL[4].b32;
-  }
+  n.dyn0_onehot = base + pk.onehot;
   n.support = sup;
   n.in_dim = in;
   auto mkw = [&](const PackedW& pw) {
@@ -468,18 +208,20 @@ extern "C" int mzh_load_weights(mzh_engine* eng, const float* flat, size_t n_flo
   };
   MzhWNet& w = eng->wnet;
   w.wbase = base;
-  w.rep = mkw(WL[0]); w.dyn = mkw(WL[1]); w.rwd = mkw(WL[2]); w.pol = mkw(WL[3]); w.val = mkw(WL[4]);
-  w.oh = base + wohoff;
+  w.rep = mkw(pk.W[0]); w.dyn = mkw(pk.W[1]); w.rwd = mkw(pk.W[2]); w.pol = mkw(pk.W[3]); w.val = mkw(pk.W[4]);
+  // the wave layout's bin-32 arrays serve both kernels (null and 0 without a 33-bin head)
+  n.rwd32 = w.rwd.w32; n.val32 = w.val.w32; n.rwd32b = w.rwd.b32; n.val32b = w.val.b32;
+  w.oh = base + pk.wonehot;
   w.support = sup;
   w.in_dim = in;
   MzhOneNet& o = eng->onet;
-  o.l1 = reinterpret_cast<const float4*>(base + PO.l1);
-  o.b1 = reinterpret_cast<const float4*>(base + PO.b1);
-  o.rep0 = base + PO.rep0;
-  o.rep0b = base + PO.rep0b;
-  o.rep2 = reinterpret_cast<const float4*>(base + PO.rep2);
-  o.rep2b = base + PO.rep2b;
-  o.l2 = reinterpret_cast<const float4*>(base + PO.l2);
+  o.l1 = reinterpret_cast<const float4*>(base + pk.one.l1);
+  o.b1 = reinterpret_cast<const float4*>(base + pk.one.b1);
+  o.rep0 = base + pk.one.rep0;
+  o.rep0b = base + pk.one.rep0b;
+  o.rep2 = reinterpret_cast<const float4*>(base + pk.one.rep2);
+  o.rep2b = base + pk.one.rep2b;
+  o.l2 = reinterpret_cast<const float4*>(base + pk.one.l2);
   eng->loaded = true;
   return MZH_OK;
 }
@@ -827,21 +569,12 @@ static int train_check(const mzh_train_args* a, bool need_batch) {
   return MZH_OK;
 }
 
-// [out, in] of the ten Linear layers in state_dict order (representation layer 1: in = in_dim;
-// value / reward layer 2: out = support)
-static void layer_dims(const mzh_train_args* a, int l, int* out, int* in) {
-  static const int kOut[10] = {256, 64, 256, 64, 256, -1, 256, 6, 256, -1};
-  static const int kIn[10] = {-1, 256, 70, 256, 64, 256, 64, 256, 64, 256};
-  *out = kOut[l] < 0 ? a->support : kOut[l];
-  *in = kIn[l] < 0 ? a->in_dim : kIn[l];
-}
-
 extern "C" int mzh_train_transpose(const mzh_train_args* a, mzh_stream stream) {
   int st = train_check(a, false);
   if (st) return st;
+  const MzhCanon dims = mzh_canon_view(nullptr, a->in_dim, a->support);
   for (int l = 0; l < 10; ++l) {
-    int out, in;
-    layer_dims(a, l, &out, &in);
+    const int out = dims.out[l], in = dims.in[l];
     hipError_t e = mzt_launch_transpose(a->param[2 * l], a->wt[l], out, in, (out + 3) & ~3, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "train transpose launch");
   }
@@ -881,42 +614,27 @@ extern "C" int mzh_train_update(const mzh_train_args* a, mzh_stream stream) {
   if (e != hipSuccess) return hip_fail(e, "train rows kernel launch");
 
   const int BU = B * U, ldg = SUP > 1 ? 48 : 16;
-  struct Spec {
-    const float* X;
-    int ldx;
-    const float* GY;
-    int ldg, M, out, in, onehot;
-  };
-  const Spec spec[10] = {
-      {s.x0, 32, s.g_rep, 256, B, 256, a->in_dim, -1}, {s.repa, 256, s.g_h0p, 64, B, 64, 256, -1},
-      {s.h, 64, s.g_d, 256, BU, 256, 70, 64},          {s.ad, 256, s.g_hp, 64, BU, 64, 256, -1},
-      {s.hp, 64, s.g_r, 256, BU, 256, 64, -1},         {s.ar, 256, s.g_lr, ldg, BU, SUP, 256, -1},
-      {s.h, 64, s.g_p, 256, BU, 256, 64, -1},          {s.ap, 256, s.g_lp, 16, BU, 6, 256, -1},
-      {s.h, 64, s.g_v, 256, BU, 256, 64, -1},          {s.av, 256, s.g_lv, ldg, BU, SUP, 256, -1}};
-  MztGradParams gp;
+  // the training-scratch facts of each layer, MztGradLayer's leading {X, ldx, GY, ldg, M}; the layer shapes
+  // come from the network's table (mzh_pack.h)
+  MztGradParams gp = {{{s.x0, 32, s.g_rep, 256, B},  {s.repa, 256, s.g_h0p, 64, B}, {s.h, 64, s.g_d, 256, BU},
+                       {s.ad, 256, s.g_hp, 64, BU},  {s.hp, 64, s.g_r, 256, BU},    {s.ar, 256, s.g_lr, ldg, BU},
+                       {s.h, 64, s.g_p, 256, BU},    {s.ap, 256, s.g_lp, 16, BU},   {s.h, 64, s.g_v, 256, BU},
+                       {s.av, 256, s.g_lv, ldg, BU}}};
+  const MzhCanon dims = mzh_canon_view(nullptr, a->in_dim, SUP);
   int tiles = 0;
   for (int l = 0; l < 10; ++l) {
     MztGradLayer& L = gp.L[l];
-    const Spec& q = spec[l];
-    L.X = q.X;
-    L.ldx = q.ldx;
-    L.GY = q.GY;
-    L.ldg = q.ldg;
-    L.M = q.M;
-    L.out = q.out;
-    L.in = q.in;
-    L.onehot_from = q.onehot;
-    L.nkb = (q.in + 15) / 16;
+    L.out = dims.out[l];
+    L.in = dims.in[l];
+    L.onehot_from = l == MZH_DYN0 ? MZH_LATENT : -1;
+    L.nkb = (L.in + 15) / 16;
     L.tile0 = tiles;
-    tiles += ((q.out + 15) / 16) * L.nkb;
-    L.W = a->param[2 * l];
-    L.b = a->param[2 * l + 1];
-    L.mW = a->exp_avg[2 * l];
-    L.vW = a->exp_avg_sq[2 * l];
-    L.mb = a->exp_avg[2 * l + 1];
-    L.vb = a->exp_avg_sq[2 * l + 1];
+    tiles += ((L.out + 15) / 16) * L.nkb;
+    L.W = a->param[2 * l]; L.b = a->param[2 * l + 1];
+    L.mW = a->exp_avg[2 * l]; L.mb = a->exp_avg[2 * l + 1];
+    L.vW = a->exp_avg_sq[2 * l]; L.vb = a->exp_avg_sq[2 * l + 1];
     L.WT = a->wt[l];
-    L.ldwt = (q.out + 3) & ~3;
+    L.ldwt = (L.out + 3) & ~3;
   }
   gp.actions = a->actions;
   gp.step_size = a->step_size;

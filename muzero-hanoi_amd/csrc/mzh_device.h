@@ -316,7 +316,7 @@ __device__ inline void mzh_softmax6(const float* l, float* p) {
 }
 
 // ------------------------------------------------------------------------------------------
-// Packed network (built by mzh_load_weights).  Each nn.Linear [N][K] is stored as MFMA B
+// Packed network (built by mzh_pack_network, mzh_pack.cpp).  Each nn.Linear [N][K] is stored as MFMA B
 // fragments: tile nt (16 output columns) x k-block kb (16 inputs) x lane -> one float4 holding
 // the lane's B values for the 4 consecutive k-steps of the block:
 //     W4[(nt*KB + kb)*64 + lane][j] = W[16nt + (lane&15)][16kb + 4j + (lane>>4)]

@@ -1,10 +1,12 @@
 // mzh_internal.h -- parameter blocks shared by the launchers (mzh_search.hip) and the C ABI
-// implementation (mzh_api.hip).
+// implementation (mzh_api.hip), and the device-pointer form of the wave and latency weight layouts that
+// mzh_pack.cpp fills (its offsets, and the MZH_ONE_* constants, come from mzh_pack.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "mzh_device.h"
+#include "mzh_pack.h"
 
 struct MzhSearchParams {
   int B, S, E;          // roots, simulations, tree blocks per root (engine max_sims + 1)
@@ -131,16 +133,8 @@ struct MzhWNet {
 //      48-63 value_net.0, 64-65 dynamic_net.0 one-hot columns 64..69 (+ 2 zero)
 //   b1 [256] float4 {dynamic_net.0, rwd_net.0, policy_net.0, value_net.0} bias of the unit
 //   rep0 [in_dim][256] representation_net.0 (k-major), rep2 [64 k4][64] float4 representation_net.2
-//   l2: the LDS image, MZH_ONE_* offsets in float4 units
+//   l2: the LDS image, MZH_ONE_* offsets in float4 units (mzh_pack.h)
 // ------------------------------------------------------------------------------------------
-#define MZH_ONE_D2 0                        // dynamic_net.2 [64 k4][64 lanes]
-#define MZH_ONE_A2 (64 * 64)                // rwd_net.2 bins 0-31 (lanes 0-31) | value_net.2 bins 0-31 (lanes 32-63)
-#define MZH_ONE_P2 (2 * 64 * 64)            // policy_net.2 [64 k4][8 lanes] (6 rows + 2 zero)
-#define MZH_ONE_C32 (MZH_ONE_P2 + 64 * 8)   // bin 32 chains [8 lanes][64 i] floats: lane g < 4 the reward head's
-                                            // chain g (k = g + 4i), lane 4 + g the value head's (128 float4)
-#define MZH_ONE_B2 (MZH_ONE_C32 + 128)      // biases (floats): [0,64) dynamic_net.2, [64,128) the A2 rows,
-                                            // [128,136) policy_net.2, 136 / 137 bin 32 of reward / value
-#define MZH_ONE_L2F4 (MZH_ONE_B2 + 36)      // float4s of the LDS image
 struct MzhOneNet {
   const float4* l1;
   const float4* b1;

@@ -1,0 +1,59 @@
+// mzh_pack.h -- the canonical flat weight vector and its three packed device layouts.  Host-only plain
+// C++ (no HIP types; mzh_pack.cpp is compiled by g++): the packers only copy, the kernels define what the
+// copies mean.  The layouts are documented where the kernels read them:
+//   cooperative  MzhLayer / MzhNet            (mzh_device.h)
+//   wave         MzhWMlp / MzhWNet            (mzh_internal.h)
+//   latency      MzhOneNet, MZH_ONE_* below   (mzh_internal.h)
+#pragma once
+#include <vector>
+
+#include "../../include/mzh.h"
+
+// the ten nn.Linear layers in state_dict order (engine.WEIGHT_KEYS: weight then bias of each);
+// MLP i (representation, dynamics, reward, policy, value) is the layer pair 2i, 2i + 1
+enum MzhLayerId { MZH_REP0, MZH_REP2, MZH_DYN0, MZH_DYN2, MZH_RWD0, MZH_RWD2, MZH_POL0, MZH_POL2, MZH_VAL0, MZH_VAL2 };
+
+// view over the canonical flat vector: layer l is w[l] [out[l]][in[l]] then b[l] [out[l]]
+struct MzhCanon {
+  const float* w[10];
+  const float* b[10];
+  int out[10], in[10];
+  int in_dim, support;
+  size_t total;  // floats
+};
+// flat == nullptr: sizes only (w / b stay null)
+MzhCanon mzh_canon_view(const float* flat, int in_dim, int support);
+
+// float offsets into the blob of one cooperative-layout layer, one wave-layout MLP, the latency layout
+struct PackedLayer {
+  size_t woff = 0, boff = 0;
+  int kb = 0, nt = 0;
+};
+struct PackedW {
+  size_t soff = 0, b1off = 0, b2off = 0, w32off = 0;
+  float b32 = 0.0f;
+  int kb1 = 0, no = 0;
+};
+struct PackedOne {
+  size_t l1 = 0, b1 = 0, rep0 = 0, rep0b = 0, rep2 = 0, rep2b = 0, l2 = 0;
+};
+
+struct MzhPacked {
+  std::vector<float> blob;  // the device buffer's contents
+  PackedLayer L[10];        // by MzhLayerId
+  size_t onehot = 0;        // MzhNet::dyn0_onehot
+  PackedW W[5];             // by MLP
+  size_t wonehot = 0;       // MzhWNet::oh
+  PackedOne one;
+};
+MzhPacked mzh_pack_network(const MzhCanon& c);
+
+// the latency layout's LDS image `l2`: offsets in float4 units
+#define MZH_ONE_D2 0                        // dynamic_net.2 [64 k4][64 lanes]
+#define MZH_ONE_A2 (64 * 64)                // rwd_net.2 bins 0-31 (lanes 0-31) | value_net.2 bins 0-31 (lanes 32-63)
+#define MZH_ONE_P2 (2 * 64 * 64)            // policy_net.2 [64 k4][8 lanes] (6 rows + 2 zero)
+#define MZH_ONE_C32 (MZH_ONE_P2 + 64 * 8)   // bin 32 chains [8 lanes][64 i] floats: lane g < 4 the reward head's
+                                            // chain g (k = g + 4i), lane 4 + g the value head's (128 float4)
+#define MZH_ONE_B2 (MZH_ONE_C32 + 128)      // biases (floats): [0,64) dynamic_net.2, [64,128) the A2 rows,
+                                            // [128,136) policy_net.2, 136 / 137 bin 32 of reward / value
+#define MZH_ONE_L2F4 (MZH_ONE_B2 + 36)      // float4s of the LDS image
