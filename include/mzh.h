@@ -117,6 +117,51 @@ int mzh_env_step(int n_disks, int goal_peg, int max_steps, int B, uint8_t* state
                  uint8_t* illegal, int32_t* step_ctr, uint8_t* active, int32_t* err_count,
                  mzh_stream stream);
 
+/* Plan-ahead acting (acting_experiments/planning_multiple_actions.py:139-178): execute a search's latent
+ * path (mcts.return_latent_actions()[:max_plan_len], MCTS/mcts.py:79-86,128-130) open loop, env.step per
+ * entry (env/hanoi.py:47-84), until the plan runs out or the episode ends (goal or max_steps; the rest of
+ * the plan is dropped).  Illegal moves are executed like any other.  One launch for n rows of a sub-batch:
+ * row j is env env_index[j] of the full batch of B envs (env j where env_index is NULL; the indices of one
+ * call must be distinct), its plan is plan[j * plan_stride + k], k < min(plan_len[j], max_plan_len) --
+ * mzh_search_args.latent / latent_len of a search over those rows, with plan_stride = n_sims + 1.  Entries
+ * at or beyond plan_len[j] are never read.
+ *   state, step_ctr, active  in/out  [B] full-batch arrays as in mzh_env_step, indexed by env
+ *   obs          in/out  [B][3n] float32: oneHot_encoding of the last executed step's moved state (what
+ *                        env.step returned last); untouched where nothing was executed
+ *   executed     out     [n] steps executed for row j in this call
+ *   steps_total, illegal_total  in/out  [B] per-env sums of executed steps / executed illegal moves
+ *   rec_action   out     [max_plan_len][n] int32 executed actions, -1 where nothing ran (nullable)
+ *   rec_reward   out     [max_plan_len][n] int8 reward codes of mzh_env_step, 0 where nothing ran (nullable)
+ *   err_count    out     nullable device int32 accumulator
+ * An env that is inactive on entry is left untouched with executed = 0 (no error: the caller's rows may
+ * include finished episodes).  Errors end the row's execution for the call and add 1 to *err_count:
+ * plan_len[j] < 1 on an active env (the reference would index an empty list), an action outside 0..5 at
+ * a position that would execute, an env index outside [0, B).
+ * MZH_ERR_ARG: a NULL required pointer, n < 1, B < 1 (B < n without env_index), max_plan_len < 1,
+ * plan_stride < max_plan_len, n_disks outside [1, 32], goal_peg outside [0, 2]. */
+typedef struct mzh_plan_args {
+  int32_t n_disks, goal_peg, max_steps;
+  int32_t B;            /* envs of the full batch */
+  int32_t n;            /* rows of this call */
+  int32_t max_plan_len; /* planning_multiple_actions.py:47 */
+  int32_t plan_stride;  /* ints between two rows' plans */
+  const int32_t* env_index; /* [n] or NULL */
+  const int32_t* plan;      /* [n][plan_stride] */
+  const int32_t* plan_len;  /* [n] */
+  uint8_t* state;
+  int32_t* step_ctr;
+  uint8_t* active;
+  float* obs;
+  int32_t* executed;
+  int32_t* steps_total;
+  int32_t* illegal_total;
+  int32_t* rec_action;
+  int8_t* rec_reward;
+  int32_t* err_count;
+} mzh_plan_args;
+
+int mzh_env_run_plan(const mzh_plan_args* args, mzh_stream stream);
+
 /* _move_allowed for all 6 moves (env/hanoi.py:117-139): bit a of mask[b] = move a legal. */
 int mzh_legal_mask(int n_disks, int B, const uint8_t* state, uint8_t* mask, mzh_stream stream);
 

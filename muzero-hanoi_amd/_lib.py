@@ -86,6 +86,15 @@ class IngestArgs(ctypes.Structure):
                 ("pi_probs", _vp), ("returns", _vp), ("prio", _vp), ("first", _vp), ("status", _vp)]
 
 
+class PlanArgs(ctypes.Structure):
+    """mirror of struct mzh_plan_args (include/mzh.h)"""
+    _fields_ = [("n_disks", _i32), ("goal_peg", _i32), ("max_steps", _i32), ("B", _i32), ("n", _i32),
+                ("max_plan_len", _i32), ("plan_stride", _i32),
+                ("env_index", _vp), ("plan", _vp), ("plan_len", _vp), ("state", _vp), ("step_ctr", _vp),
+                ("active", _vp), ("obs", _vp), ("executed", _vp), ("steps_total", _vp), ("illegal_total", _vp),
+                ("rec_action", _vp), ("rec_reward", _vp), ("err_count", _vp)]
+
+
 # name -> (restype, argtypes); every symbol include/mzh.h declares
 SIGNATURES = {
     "mzh_abi_version": (ctypes.c_int, []),
@@ -100,6 +109,7 @@ SIGNATURES = {
     "mzh_weights_size": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
     "mzh_load_weights": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t]),
     "mzh_env_step": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [_vp] * 10 + [_vp]),
+    "mzh_env_run_plan": (ctypes.c_int, [ctypes.POINTER(PlanArgs), _vp]),
     "mzh_legal_mask": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),
     "mzh_encode_obs": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),
     "mzh_hanoi_solver": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),

@@ -7,9 +7,12 @@ fused kernel launch, every env step the integer kernel).
   get_results          acting_experiments/acting_ablations.py:72-128 (error vs the optimal move count
                        per simulation budget; one MCTS instance, MinMaxStats carried throughout)
   illegal_move_rate    illegal_move_rate_comparison.py:27-50 (per-episode rates: mean, std error)
+  plan_multiple_actions  acting_experiments/planning_multiple_actions.py:111-183 (one search, then its
+                       latent path executed open loop; a new search only when the plan ran out)
 
 They run one decision at a time, exactly as the reference does (same RNG stream, same MinMaxStats
-chain); selfplay.evaluate is the batched form (sequential=True reproduces get_results).
+chain); selfplay.evaluate is the batched form (sequential=True reproduces get_results, and with
+max_plan_len plan_multiple_actions).
 """
 import logging
 
@@ -58,6 +61,54 @@ def get_results(env, start, networks, mcts, episode, n_mcts_simulations_range, t
         for _ in range(episode):
             s0, steps, _ = _episode(env, start is not None, networks, mcts, temperature)
             errors.append(steps - hanoi_solver(s0))
+        data.append([n, sum(errors) / len(errors)])
+    logging.info(data)
+    return data
+
+
+def _plan(mcts, c_state, networks, temperature, max_plan_len):
+    """one search; the plan is the last simulation's selection path, cut to max_plan_len moves.  The action
+    run_mcts returns is drawn (deterministic=False, as the script calls it) but not executed."""
+    mcts.run_mcts(c_state, networks, temperature=temperature, deterministic=False)
+    return [int(a.item()) if hasattr(a, "item") else int(a) for a in mcts.return_latent_actions()[:max_plan_len]]
+
+
+@torch.no_grad()
+def plan_multiple_actions(env, start, networks, mcts, episode, n_mcts_simulations_range, temperature, max_plan_len=7,
+                          trace=None):
+    """planning_multiple_actions.py:111-183 with get_results' arguments and return value: per episode one
+    search whose latent path (mcts.return_latent_actions()[:max_plan_len]) is executed open loop, illegal
+    moves included, with a new search from the current observation only when the plan ran out before the
+    episode ended; reaching the goal or max_steps inside a plan drops the rest of it.  One MCTS instance
+    (its MinMaxStats chain) serves every episode and budget.  Returns [[n_simulations, mean(steps - optimal
+    moves)]].  A budget below 1 would execute a stale path in the reference: ValueError.
+    trace: a list that receives (start state, executed actions, plan lengths) per episode."""
+    if int(max_plan_len) < 1:
+        raise ValueError(f"plan_multiple_actions: max_plan_len must be >= 1, got {max_plan_len}")
+    if any(int(n) < 1 for n in n_mcts_simulations_range):
+        raise ValueError("plan_multiple_actions: a plan needs n_simulations >= 1 in every budget")
+    data = []
+    for n in n_mcts_simulations_range:
+        mcts.n_simulations = n
+        errors = []
+        for _ in range(episode):
+            c_state = env.reset() if start is not None else env.random_reset()
+            s0 = tuple(env.current_state())
+            action_seq = _plan(mcts, c_state, networks, temperature, max_plan_len)
+            executed, plan_lens = [], [len(action_seq)]
+            done = False
+            t = 0
+            while not done:
+                c_state, _, done, _ = env.step(action_seq[t])
+                executed.append(action_seq[t])
+                t += 1
+                if t >= len(action_seq) and not done:
+                    action_seq = _plan(mcts, c_state, networks, temperature, max_plan_len)
+                    plan_lens.append(len(action_seq))
+                    t = 0
+            errors.append(len(executed) - hanoi_solver(s0))
+            if trace is not None:
+                trace.append((s0, executed, plan_lens))
         data.append([n, sum(errors) / len(errors)])
     logging.info(data)
     return data

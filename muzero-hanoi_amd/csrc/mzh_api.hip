@@ -240,6 +240,21 @@ extern "C" int mzh_env_step(int n_disks, int goal_peg, int max_steps, int B, uin
   return e == hipSuccess ? MZH_OK : hip_fail(e, "env_step launch");
 }
 
+extern "C" int mzh_env_run_plan(const mzh_plan_args* a, mzh_stream stream) {
+  if (!a) return fail(MZH_ERR_ARG, "env_run_plan: args is NULL");
+  if (a->n_disks < 1 || a->n_disks > 32 || a->goal_peg < 0 || a->goal_peg > 2)
+    return fail(MZH_ERR_ARG, "env_run_plan: bad n_disks=%d goal_peg=%d", a->n_disks, a->goal_peg);
+  if (a->n < 1 || a->B < 1 || (!a->env_index && a->B < a->n))
+    return fail(MZH_ERR_ARG, "env_run_plan: bad n=%d rows for B=%d envs", a->n, a->B);
+  if (a->max_plan_len < 1 || a->plan_stride < a->max_plan_len)
+    return fail(MZH_ERR_ARG, "env_run_plan: bad max_plan_len=%d plan_stride=%d", a->max_plan_len, a->plan_stride);
+  if (!a->plan || !a->plan_len || !a->state || !a->step_ctr || !a->active || !a->obs || !a->executed ||
+      !a->steps_total || !a->illegal_total)
+    return fail(MZH_ERR_ARG, "env_run_plan: required buffer is NULL");
+  hipError_t e = mzh_launch_env_run_plan(a, (hipStream_t)stream);
+  return e == hipSuccess ? MZH_OK : hip_fail(e, "env_run_plan launch");
+}
+
 extern "C" int mzh_legal_mask(int n_disks, int B, const uint8_t* state, uint8_t* mask, mzh_stream stream) {
   if (n_disks < 1 || n_disks > 32 || B < 0 || (B > 0 && (!state || !mask))) return fail(MZH_ERR_ARG, "legal_mask: bad args");
   if (B == 0) return MZH_OK;

@@ -4,9 +4,20 @@
 // A state is N bytes (peg of disc d, disc 0 smallest), the reference's tuple layout.  The legal
 // test _move_allowed (hanoi.py:123-139: from-peg non-empty and (to-peg empty or min(to) >
 // min(from))) is computed as top[f] < top[t] with top[p] = smallest disc on peg p (N if empty).
+//
+// mzh_env_step_kernel and mzh_env_run_plan_kernel share one transition (env_transition): the step
+// kernel applies it once per env, the plan kernel up to max_plan_len times per row with the state in
+// registers (acting_experiments/planning_multiple_actions.py:139-178: a search's latent path executed
+// open loop).  The plan kernel's reads of `plan` are a strided gather -- lane j reads
+// plan[j * plan_stride + k], plan_stride = n_sims + 1 ints for the search's `latent` output, so
+// consecutive lanes are plan_stride * 4 bytes apart and each lane touches at most max_plan_len
+// consecutive ints (one or two 64-byte lines at max_plan_len 7).  They are not staged through LDS: no
+// measurement says the gather matters next to the search that produced it.  Its record stores are laid
+// out [max_plan_len][n], so consecutive lanes store consecutive addresses.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/mzh.h"
 #include "mzh_env_kernels.h"
 
 #define MZH_MAXN 32
@@ -19,6 +30,55 @@ __device__ __forceinline__ void load_state(const uint8_t* src, int n, uint8_t* s
   for (int d = n - 1; d >= 0; --d) {
     st[d] = src[d];
     top[st[d]] = d;
+  }
+}
+
+// One TowersOfHanoi.step (hanoi.py:47-84) of an active env for a move a in 0..5.  st (in: c_state, out: the
+// moved state the returned observation encodes) and top (of c_state) are the lane's registers; c_state is the
+// env's row of `state` and active its reset_check byte, stored to where the reference assigns them; ctr
+// (step_counter) is the caller's to load and store.  Returns the reward code (0 -> 0, 1 -> 100,
+// -1 -> -100/1000) and sets dn / ill; advanced tells whether c_state moved (not on an illegal move, and not
+// on the goal step, hanoi.py:65-69).
+__device__ __forceinline__ int8_t env_transition(int n, int goal_peg, int max_steps, int a, uint8_t* st,
+                                                 const int top[3], uint8_t* c_state, uint8_t* active, int& ctr,
+                                                 uint8_t& dn, uint8_t& ill, bool& advanced) {
+  const int f = kMoveFrom[a], t = kMoveTo[a];
+  int8_t code;
+  dn = 0;
+  advanced = false;
+  ill = !(top[f] < top[t]);
+  ctr += 1;  // hanoi.py:61
+  if (!ill) {
+    const int disc = top[f];  // smallest disc on the from-peg (hanoi.py:148-150)
+    st[disc] = (uint8_t)t;
+    bool goal = true;
+    for (int d = 0; d < n; ++d) goal = goal && (st[d] == goal_peg);
+    if (!goal) {
+      code = 0;
+      c_state[disc] = (uint8_t)t;  // c_state = moved_state
+      advanced = true;
+    } else {
+      code = 1;  // rwd 100, done, reset_check False, counter 0; c_state NOT advanced (hanoi.py:65-69)
+      dn = 1;
+      *active = 0;
+      ctr = 0;
+    }
+  } else {
+    code = -1;  // rwd -100/1000, state unchanged (hanoi.py:70-74)
+  }
+  if (ctr == max_steps) {  // hanoi.py:77-80
+    dn = 1;
+    *active = 0;
+    ctr = 0;
+  }
+  return code;
+}
+
+__device__ __forceinline__ void store_obs(float* o, int n, const uint8_t* st) {
+  for (int d = 0; d < n; ++d) {
+    o[3 * d + 0] = st[d] == 0 ? 1.0f : 0.0f;
+    o[3 * d + 1] = st[d] == 1 ? 1.0f : 0.0f;
+    o[3 * d + 2] = st[d] == 2 ? 1.0f : 0.0f;
   }
 }
 
@@ -39,31 +99,10 @@ __global__ void mzh_env_step_kernel(int n, int goal_peg, int max_steps, int B, u
     code = -2;
     if (err_count) atomicAdd(err_count, 1);
   } else {
-    const int f = kMoveFrom[a], t = kMoveTo[a];
-    ill = !(top[f] < top[t]);
-    int ctr = step_ctr[b] + 1;  // hanoi.py:61
-    if (!ill) {
-      const int disc = top[f];  // smallest disc on the from-peg (hanoi.py:148-150)
-      st[disc] = (uint8_t)t;
-      bool goal = true;
-      for (int d = 0; d < n; ++d) goal = goal && (st[d] == goal_peg);
-      if (!goal) {
-        code = 0;
-        state[(size_t)b * n + disc] = (uint8_t)t;  // c_state = moved_state
-      } else {
-        code = 1;  // rwd 100, done, reset_check False, counter 0; c_state NOT advanced (hanoi.py:65-69)
-        dn = 1;
-        active[b] = 0;
-        ctr = 0;
-      }
-    } else {
-      code = -1;  // rwd -100/1000, state unchanged (hanoi.py:70-74)
-    }
-    if (ctr == max_steps) {  // hanoi.py:77-80
-      dn = 1;
-      active[b] = 0;
-      ctr = 0;
-    }
+    int ctr = step_ctr[b];
+    bool advanced;
+    code = env_transition(n, goal_peg, max_steps, a, st, top, state + (size_t)b * n, active + b, ctr, dn, ill,
+                          advanced);
     step_ctr[b] = ctr;
   }
   reward[b] = code;
@@ -71,13 +110,69 @@ __global__ void mzh_env_step_kernel(int n, int goal_peg, int max_steps, int B, u
   illegal[b] = ill;
   if (moved)
     for (int d = 0; d < n; ++d) moved[(size_t)b * n + d] = st[d];
-  if (obs) {
-    float* o = obs + (size_t)b * 3 * n;
-    for (int d = 0; d < n; ++d) {
-      o[3 * d + 0] = st[d] == 0 ? 1.0f : 0.0f;
-      o[3 * d + 1] = st[d] == 1 ? 1.0f : 0.0f;
-      o[3 * d + 2] = st[d] == 2 ? 1.0f : 0.0f;
+  if (obs) store_obs(obs + (size_t)b * 3 * n, n, st);
+}
+
+// Execute each row's plan open loop (planning_multiple_actions.py:139-178): row j is env env_index[j]
+// (j without env_index) of the full batch and applies plan[j * plan_stride + k] for
+// k < min(plan_len[j], max_plan_len) while its env is active.  Entries at or beyond plan_len[j] are never
+// read.  An env inactive on entry is left untouched (executed 0, no error).  Errors (plan_len < 1 on an
+// active env, an action outside 0..5 at a position that would execute, an env index outside the batch)
+// add to err_count and end the row's execution for the call.
+__global__ void mzh_env_run_plan_kernel(mzh_plan_args p) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= p.n) return;
+  const int n = p.n_disks, L = p.max_plan_len;
+  const int e = p.env_index ? p.env_index[j] : j;
+  int ex = 0;
+  bool err = false;
+  if (e < 0 || e >= p.B) {
+    err = true;
+  } else if (p.active[e]) {
+    const int len = p.plan_len[j];
+    if (len < 1) {
+      err = true;
+    } else {
+      const int k_max = len < L ? len : L;
+      const int32_t* pl = p.plan + (size_t)j * p.plan_stride;
+      uint8_t* sp = p.state + (size_t)e * n;
+      uint8_t st[MZH_MAXN];
+      int top[3];
+      load_state(sp, n, st, top);
+      int ctr = p.step_ctr[e], ill_n = 0;
+      uint8_t dn = 0;
+      while (ex < k_max && !dn) {
+        const int a = pl[ex];
+        if (a < 0 || a >= 6) {  // moves[action] IndexError
+          err = true;
+          break;
+        }
+        uint8_t ill;
+        bool advanced;
+        const int8_t code = env_transition(n, p.goal_peg, p.max_steps, a, st, top, sp, p.active + e, ctr, dn, ill,
+                                           advanced);
+        if (advanced) {
+          top[0] = top[1] = top[2] = n;
+          for (int d = n - 1; d >= 0; --d) top[st[d]] = d;
+        }
+        if (p.rec_action) p.rec_action[(size_t)ex * p.n + j] = a;
+        if (p.rec_reward) p.rec_reward[(size_t)ex * p.n + j] = code;
+        ill_n += ill;
+        ++ex;
+      }
+      if (ex > 0) {  // st: the last executed step's moved state, what env.step returned last
+        store_obs(p.obs + (size_t)e * 3 * n, n, st);
+        p.step_ctr[e] = ctr;
+        p.steps_total[e] += ex;
+        p.illegal_total[e] += ill_n;
+      }
     }
+  }
+  if (err && p.err_count) atomicAdd(p.err_count, 1);
+  p.executed[j] = ex;
+  for (int k = ex; k < L; ++k) {
+    if (p.rec_action) p.rec_action[(size_t)k * p.n + j] = -1;
+    if (p.rec_reward) p.rec_reward[(size_t)k * p.n + j] = 0;
   }
 }
 
@@ -124,6 +219,11 @@ hipError_t mzh_launch_env_step(int n, int goal_peg, int max_steps, int B, uint8_
                                int32_t* step_ctr, uint8_t* active, int32_t* err_count, hipStream_t s) {
   hipLaunchKernelGGL(mzh_env_step_kernel, dim3(nblocks(B, 256)), dim3(256), 0, s, n, goal_peg, max_steps, B, state,
                      action, moved, obs, reward, done, illegal, step_ctr, active, err_count);
+  return hipGetLastError();
+}
+
+hipError_t mzh_launch_env_run_plan(const mzh_plan_args* args, hipStream_t s) {
+  hipLaunchKernelGGL(mzh_env_run_plan_kernel, dim3(nblocks(args->n, 256)), dim3(256), 0, s, *args);
   return hipGetLastError();
 }
 

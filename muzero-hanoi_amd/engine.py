@@ -237,6 +237,34 @@ def env_step(n_disks, max_steps, state, action, step_ctr, active, goal_peg=2, mo
     return reward, done, illegal
 
 
+def env_run_plan(n_disks, max_steps, state, step_ctr, active, obs, plan, plan_len, max_plan_len, steps_total,
+                 illegal_total, *, env_index=None, goal_peg=2, err=None, record=False):
+    """mzh_env_run_plan on device tensors: row j (env env_index[j], or j) executes plan[j, :min(plan_len[j],
+    max_plan_len)] while its env is active.  state / step_ctr / active / obs / steps_total / illegal_total are the
+    full batch's, updated in place; plan [n, stride] int32 and plan_len [n] int32 are read where the search left
+    them.  Returns (executed [n], rec_action [L, n] | None, rec_reward [L, n] | None)."""
+    dev = state.device
+    n, L = int(plan_len.shape[0]), int(max_plan_len)
+    if plan.dtype != torch.int32 or plan_len.dtype != torch.int32 or plan.dim() != 2 or plan.stride(1) != 1:
+        raise ValueError("env_run_plan: plan [n, stride] and plan_len [n] must be int32 with unit inner stride")
+    if env_index is not None and (env_index.dtype != torch.int32 or not env_index.is_contiguous()
+                                  or env_index.shape[0] != n):
+        raise ValueError("env_run_plan: env_index must be a contiguous int32 [n]")
+    a = _lib.PlanArgs()
+    a.n_disks, a.goal_peg, a.max_steps = int(n_disks), int(goal_peg), int(max_steps)
+    a.B, a.n, a.max_plan_len, a.plan_stride = int(state.shape[0]), n, L, int(plan.stride(0))
+    executed = torch.empty(n, dtype=torch.int32, device=dev)
+    rec_a = torch.empty((L, n), dtype=torch.int32, device=dev) if record and L > 0 else None
+    rec_r = torch.empty((L, n), dtype=torch.int8, device=dev) if record and L > 0 else None
+    for k, t in (("env_index", env_index), ("plan", plan), ("plan_len", plan_len), ("state", state),
+                 ("step_ctr", step_ctr), ("active", active), ("obs", obs), ("executed", executed),
+                 ("steps_total", steps_total), ("illegal_total", illegal_total), ("rec_action", rec_a),
+                 ("rec_reward", rec_r), ("err_count", err)):
+        setattr(a, k, ptr(t))
+    check(_lib.lib().mzh_env_run_plan(ctypes.byref(a), _lib.stream_handle(dev)), "mzh_env_run_plan")
+    return executed, rec_a, rec_r
+
+
 def legal_mask(n_disks, state):
     mask = torch.empty(state.shape[0], dtype=torch.uint8, device=state.device)
     check(_lib.lib().mzh_legal_mask(n_disks, state.shape[0], ptr(state), ptr(mask), _lib.stream_handle(state.device)),

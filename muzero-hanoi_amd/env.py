@@ -145,6 +145,7 @@ class HanoiBatch:
         self.step_ctr = torch.zeros(B, dtype=torch.int32, device=self.device)
         self.active = torch.zeros(B, dtype=torch.uint8, device=self.device)
         self.err = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.last_obs = self.steps_total = self.illegal_total = None  # run_plan's per-env arrays, made on first use
 
     def reset(self, state_idx):
         """state_idx [B] -> reference state tuples (index = sum s[i] * 3^(N-1-i))."""
@@ -153,6 +154,7 @@ class HanoiBatch:
         self.state.copy_(((idx[:, None] // pw) % 3).to(torch.uint8))
         self.step_ctr.zero_()
         self.active.fill_(1)
+        self.last_obs = self.steps_total = self.illegal_total = None
         return self.obs()
 
     def obs(self):
@@ -163,6 +165,24 @@ class HanoiBatch:
         code, done, illegal = engine.env_step(self.N, self.max_steps, self.state, action.to(torch.int32).contiguous(),
                                               self.step_ctr, self.active, goal_peg=self.goal_peg, obs=obs, err=self.err)
         return obs, code, done, illegal
+
+    def run_plan(self, plan, plan_len, max_plan_len, env_index=None, record=False):
+        """Execute plan[j, :min(plan_len[j], max_plan_len)] on env env_index[j] (env j without env_index) open
+        loop, one mzh_env_run_plan launch (planning_multiple_actions.py:139-178): each row steps until its plan
+        runs out or its episode ends; finished envs are left untouched.  plan [n, stride] / plan_len [n] int32
+        device tensors (a search's `latent` / `latent_len`), env_index [n] int32.  Updates state, step_ctr, active,
+        last_obs (the observation env.step returned last), steps_total and illegal_total (per-env sums since
+        reset); errors are counted in self.err.  Returns dict(executed [n], action [L, n], reward [L, n] int8
+        codes -- the last two with record=True, -1 / 0 where nothing ran)."""
+        if self.last_obs is None:
+            self.last_obs = self.obs()
+            self.steps_total = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+            self.illegal_total = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+        executed, rec_a, rec_r = engine.env_run_plan(
+            self.N, self.max_steps, self.state, self.step_ctr, self.active, self.last_obs, plan, plan_len,
+            max_plan_len, self.steps_total, self.illegal_total, env_index=env_index, goal_peg=self.goal_peg,
+            err=self.err, record=record)
+        return dict(executed=executed, action=rec_a, reward=rec_r)
 
     def legal_mask(self):
         return engine.legal_mask(self.N, self.state)

@@ -8,6 +8,9 @@ BatchedSelfPlay    B envs resident on the GPU (HanoiBatch) stepping with search-
                    envs.  Each env is one agent with its own MCTS instance: its MinMaxStats
                    (MCTS/mcts.py:23, never reset) is carried from decision to decision
                    (minmax_out -> minmax_in), starting from the `minmax` handed in.
+                   play_plans is the plan-ahead form (acting_experiments/planning_multiple_actions.py):
+                   a search's latent path executed open loop by one mzh_env_run_plan launch, the next
+                   search only for the envs whose plan ran out.
 episode_records    the reference's per-episode bookkeeping (returns, priorities,
                    organise_transitions) of every env of a BatchedSelfPlay run.
 ingest_records     that bookkeeping, the success filter and Buffer.add for every env in one device call
@@ -18,7 +21,8 @@ evaluate           acting_ablations.get_results (acting_experiments/acting_ablat
                    standard error).  sequential=True is the reference's own schedule -- one MCTS
                    instance, episodes one after another, the global NumPy stream -- and reproduces
                    get_results exactly; otherwise a budget's episodes run as one batch, each with
-                   its own persistent MinMaxStats.
+                   its own persistent MinMaxStats.  max_plan_len= scores plan-ahead episodes
+                   (acting.plan_multiple_actions) in either schedule.
 
 RNG: with legacy_rng the draws come from NumPy's global stream (rng.predraw) in the order the
 reference consumes them when one env plays at a time (B = 1, or sequential=True); a batch of
@@ -211,6 +215,89 @@ class BatchedSelfPlay:
         res["minmax"] = mm
         return res
 
+    def play_plans(self, start_idx, max_plan_len, temperature=1.0, deterministic=False, seed=0, legacy_rng=False,
+                   minmax=None):
+        """Plan-ahead episodes (acting_experiments/planning_multiple_actions.py:111-183): every env searches
+        once and executes the last simulation's selection path (mcts.return_latent_actions()[:max_plan_len])
+        open loop, illegal moves included, and searches again only when that plan ran out before the episode
+        ended (goal or max_steps; the rest of a plan is dropped).  The search's `action` is drawn as in `play`
+        (the same draws and per-agent MinMaxStats carry) but not executed.
+
+        Per round: one search over the unfinished envs, one mzh_env_run_plan launch reading the search's
+        latent / latent_len where it left them and the envs' full-batch arrays through env_index, and one
+        host read (unfinished envs left, error count).  Returns device tensors: per env steps, illegal
+        (executed illegal moves), plans (searches), start_idx, minmax; per round r: action [R][L][B]
+        (executed moves, -1 where nothing ran), reward [R][L][B] (int8 codes of mzh_env_step, 0 where nothing
+        ran), root_q [R][B] and search_action [R][B] (0 / -1 for envs without a search that round)."""
+        L = int(max_plan_len)
+        if L < 1:
+            raise ValueError(f"play_plans: max_plan_len must be >= 1, got {max_plan_len}")
+        if self.S < 1:  # the reference would execute the previous search's path (mcts.py:79 is never reached)
+            raise ValueError("play_plans: a plan needs n_simulations >= 1")
+        start = torch.as_tensor(np.asarray(start_idx), dtype=torch.int64).reshape(-1)
+        B = int(start.shape[0])
+        if B < 1:
+            raise ValueError("play_plans: no start states")
+        eng, replay = self._engine(B)
+        dev = eng.device
+        env = HanoiBatch(self.N, self.max_steps, B, goal_peg=self.goal_peg, device=dev)
+        env.reset(start.to(dev))
+        gen = np.random.default_rng(seed)
+        mm = torch.empty((B, 2), dtype=torch.float64, device=dev)
+        if minmax is None:
+            mm[:, 0], mm[:, 1] = -float("inf"), float("inf")
+        else:
+            mm.copy_(torch.as_tensor(np.asarray(minmax, np.float64)).reshape(B, 2))
+        plans = torch.zeros(B, dtype=torch.int32, device=dev)
+        rec = dict(action=[], reward=[], root_q=[], search_action=[])
+        t = lambda a: None if a is None else torch.as_tensor(a).to(dev)
+        n, idx = B, torch.arange(B, device=dev)
+        while n:
+            if legacy_rng:
+                noise, tie, u = _rng.predraw(n, deterministic=deterministic, alpha=self.alpha, eps=self.eps)
+            else:
+                noise, tie, u = _rng.synthetic_draws(n, deterministic=deterministic, alpha=self.alpha, eps=self.eps,
+                                                     seed=int(gen.integers(2**31)))
+            rp = None
+            if replay:
+                call = self.network.next_call()
+                rp = {k: torch.as_tensor(np.asarray(call[k], np.float32)).to(dev)[None]
+                      for k in ("root_pi", "pi", "reward", "value")}
+            # the observation env.step returned last (the start's before the first plan): HanoiBatch.last_obs
+            obs = env.obs() if env.last_obs is None else env.last_obs
+            out = eng.search(self.S, obs=None if replay else obs.index_select(0, idx), replay=rp, tie_idx=t(tie),
+                             noise=t(noise), action_u=t(u), minmax_in=mm.index_select(0, idx),
+                             temperature=float(temperature), deterministic=bool(deterministic),
+                             discount=self.discount, eps=self.eps, np1_ucb=self.np1_ucb)
+            mm.index_copy_(0, idx, out["minmax"])
+            # a path has at most S + 1 moves (the row stride of `latent`): a longer max_plan_len cuts nothing more
+            r = env.run_plan(out["latent"], out["latent_len"], min(L, self.S + 1), env_index=idx.to(torch.int32),
+                             record=True)
+            plans.index_add_(0, idx, torch.ones_like(idx, dtype=torch.int32))
+            full = lambda v, fill: torch.full(tuple(v.shape[:-1]) + (B,), fill, dtype=v.dtype, device=dev).index_copy(
+                v.dim() - 1, idx, v)
+            pad = lambda v, fill: v if v.shape[0] == L else torch.cat(
+                [v, torch.full((L - v.shape[0], B), fill, dtype=v.dtype, device=dev)])
+            rec["action"].append(pad(full(r["action"], -1), -1))
+            rec["reward"].append(pad(full(r["reward"], 0), 0))
+            rec["root_q"].append(full(out["root_q"], 0.0))
+            rec["search_action"].append(full(out["action"], -1))
+            # the round's one host read: how many envs still need a plan, and the kernel's error count
+            left, err = (int(x) for x in torch.stack([env.active.sum(dtype=torch.int32), env.err[0]]).cpu())
+            if err:
+                raise RuntimeError(f"mzh_env_run_plan reported {err} error(s): a search returned an empty path or "
+                                   "an action outside 0..5")
+            n = left
+            # the unfinished envs in env order, without another host read (their count is known)
+            idx = torch.sort(env.active, descending=True, stable=True).indices[:n]
+        res = {k: torch.stack(v) for k, v in rec.items()}
+        res["steps"] = env.steps_total
+        res["illegal"] = env.illegal_total
+        res["plans"] = plans
+        res["start_idx"] = start.to(dev)
+        res["minmax"] = mm
+        return res
+
 
 def episode_records(res, *, discount=0.8, TD_return=True, n_step=10, unroll_n_steps=5, n_action=6):
     """Muzero._play_game's return value for every env of a BatchedSelfPlay.play(record_obs=True)
@@ -272,7 +359,7 @@ def _random_start(n_disks, goal_peg):
 
 def evaluate(network, n_disks, n_sims_range, *, episodes=1, start=None, start_idx=None, max_steps=200,
              temperature=1.0, deterministic=False, sequential=False, legacy_rng=None, seed=0, goal_peg=2, minmax=None,
-             np1_ucb=False):
+             np1_ucb=False, max_plan_len=None, dirichlet_alpha=0.25):
     """Episodes per simulation budget, scored like the reference's acting scripts.
 
     start: None -> random_reset starts (env/hanoi.py:103-109); "ES" / "MS" / "LS" or a state index
@@ -284,14 +371,26 @@ def evaluate(network, n_disks, n_sims_range, *, episodes=1, start=None, start_id
     Returns dict(data=[[n, mean error]] (get_results' value), illegal=[[n, mean rate, std error]]
     (illegal_move_rate's value per budget), errors / steps / illegal_rates per budget, minmax).
     minmax (in and out) is the carried chain of the sequential schedule only: with
-    sequential=False every agent starts fresh, `minmax` must be None and None is returned."""
+    sequential=False every agent starts fresh, `minmax` must be None and None is returned.
+    max_plan_len: None -> a search per step (get_results); an integer L >= 1 -> plan-ahead episodes
+    (planning_multiple_actions.py:111-183, BatchedSelfPlay.play_plans): a search's latent path, cut to L
+    moves, is executed open loop and the next search runs only when it ran out; every budget must be >= 1.
+    `illegal` then counts the executed illegal moves.
+    dirichlet_alpha: the agents' root_dirichlet_alpha (0: no root noise, the plan-ahead script's setting)."""
+    if max_plan_len is not None:
+        if int(max_plan_len) != max_plan_len or int(max_plan_len) < 1:
+            raise ValueError(f"evaluate: max_plan_len must be an integer >= 1, got {max_plan_len}")
+        if any(int(n) < 1 for n in n_sims_range):
+            raise ValueError("evaluate: a plan needs n_simulations >= 1 in every budget")
     if not sequential and minmax is not None:
         raise ValueError("evaluate: minmax applies to the sequential schedule only (batched agents start fresh)")
     legacy_rng = sequential if legacy_rng is None else legacy_rng
     data, illegal, errors_all, steps_all, rates_all = [], [], [], [], []
     mm = None if minmax is None else np.asarray(minmax, np.float64).reshape(1, 2)
     for n in n_sims_range:
-        sp = BatchedSelfPlay(network, n_disks, max_steps, int(n), goal_peg=goal_peg, np1_ucb=np1_ucb)
+        sp = BatchedSelfPlay(network, n_disks, max_steps, int(n), goal_peg=goal_peg, np1_ucb=np1_ucb,
+                             dirichlet_alpha=dirichlet_alpha)
+        play = sp.play if max_plan_len is None else (lambda s, **kw: sp.play_plans(s, int(max_plan_len), **kw))
         if sequential:
             steps, ill, starts = [], [], []
             for ep in range(episodes):
@@ -301,8 +400,8 @@ def evaluate(network, n_disks, n_sims_range, *, episodes=1, start=None, start_id
                     s0 = _random_start(n_disks, goal_peg)
                 else:
                     s0 = _start_index(start, n_disks)
-                res = sp.play([s0], temperature=temperature, deterministic=deterministic, legacy_rng=legacy_rng,
-                              minmax=mm, seed=seed + ep)
+                res = play([s0], temperature=temperature, deterministic=deterministic, legacy_rng=legacy_rng,
+                           minmax=mm, seed=seed + ep)
                 mm = res["minmax"].cpu().numpy()
                 steps.append(int(res["steps"][0]))
                 ill.append(int(res["illegal"][0]))
@@ -318,8 +417,8 @@ def evaluate(network, n_disks, n_sims_range, *, episodes=1, start=None, start_id
                 starts = starts + (starts >= goal)  # uniform over the non-goal states
             else:
                 starts = np.full(episodes, _start_index(start, n_disks), np.int64)
-            res = sp.play(starts, temperature=temperature, deterministic=deterministic, legacy_rng=legacy_rng,
-                          seed=seed)
+            res = play(starts, temperature=temperature, deterministic=deterministic, legacy_rng=legacy_rng,
+                       seed=seed)
             steps, ill = res["steps"].cpu().numpy(), res["illegal"].cpu().numpy()
         dev = torch.device("cuda", torch.cuda.current_device())
         st = torch.tensor([index_state(int(i), n_disks) for i in starts], dtype=torch.uint8, device=dev)
