@@ -57,6 +57,12 @@ class SearchArgs(ctypes.Structure):
     ]
 
 
+# SearchArgs output pointer -> the name its array has in a search's result (Engine.search, MCTS.run_mcts)
+SEARCH_OUTPUTS = (("visits", "visits"), ("root_q", "root_q"), ("minmax_out", "minmax"), ("extra_ties", "extra_ties"),
+                  ("action", "action"), ("pi", "pi"), ("latent", "latent"), ("latent_len", "latent_len"),
+                  ("sel_steps", "sel_steps"))
+
+
 class TrainArgs(ctypes.Structure):
     """mirror of struct mzh_train_args (include/mzh.h)"""
     _f32 = ctypes.c_float

@@ -178,15 +178,8 @@ class Engine:
         if replay is not None:
             a.rp_root_pi = ptr(dev(replay["root_pi"], torch.float32))
             a.rp_sim = ptr(dev(replay["sim"] if "sim" in replay else pack_replay(replay), torch.float32))
-        a.visits = ptr(out["visits"])
-        a.root_q = ptr(out.get("root_q"))
-        a.minmax_out = ptr(out.get("minmax"))
-        a.extra_ties = ptr(out.get("extra_ties"))
-        a.action = ptr(out.get("action"))
-        a.pi = ptr(out.get("pi"))
-        a.latent = ptr(out.get("latent"))
-        a.latent_len = ptr(out.get("latent_len"))
-        a.sel_steps = ptr(out.get("sel_steps"))
+        for k, f in _lib.SEARCH_OUTPUTS:  # visits is required, the others optional
+            setattr(a, k, ptr(out[f] if f == "visits" else out.get(f)))
         pt = self.pow_table(n_sims, float(temperature)) if (out.get("pi") is not None or
                                                               out.get("action") is not None) else None
         if pt is not None:

@@ -103,29 +103,25 @@ class TowersOfHanoi:
         return bool((int(mask.item()) >> self.moves.index(tuple(move))) & 1)
 
     # ------------------------------------------------------------------ helpers
+    def _step_fields(self):
+        """mzh_env_step's staging record: (the fields it updates in place or reads, the fields it only writes)"""
+        n = self.discs
+        return ([("state", torch.uint8, (1, n)), ("action", torch.int32, (1,)), ("ctr", torch.int32, (1,)),
+                 ("active", torch.uint8, (1,))],
+                [("moved", torch.uint8, (1, n)), ("obs", torch.float32, (1, 3 * n)), ("code", torch.int8, (1,)),
+                 ("done", torch.uint8, (1,)), ("illegal", torch.uint8, (1,))])
+
     def _packed(self):
         if self._pk is None:
-            n = self.discs
-            fields = [("state", torch.uint8, (1, n)), ("action", torch.int32, (1,)), ("ctr", torch.int32, (1,)),
-                      ("active", torch.uint8, (1,)), ("moved", torch.uint8, (1, n)), ("obs", torch.float32, (1, 3 * n)),
-                      ("code", torch.int8, (1,)), ("done", torch.uint8, (1,)), ("illegal", torch.uint8, (1,))]
-            try:  # the kernel reads and writes the pinned staging buffer itself: one launch + one sync per step
-                self._pk = Packed(fields, self._dev, zero_copy=True)
-            except RuntimeError:  # no device address for pinned memory here: one copy each way
-                self._pk = Packed(fields, self._dev)
+            inout, out = self._step_fields()
+            self._pk = Packed.mapped(inout + out, self._dev)
             self._ptrs = self._pk.dptr  # fixed: the call passes them as is
         return self._pk
 
     def _packed_out2(self):
         """a second record of the step's outputs (MCTS.play_episode alternates output records between decisions)"""
         if getattr(self, "_pk2", None) is None:
-            n = self.discs
-            fields = [("moved", torch.uint8, (1, n)), ("obs", torch.float32, (1, 3 * n)), ("code", torch.int8, (1,)),
-                      ("done", torch.uint8, (1,)), ("illegal", torch.uint8, (1,))]
-            try:
-                self._pk2 = Packed(fields, self._dev, zero_copy=True)
-            except RuntimeError:
-                self._pk2 = Packed(fields, self._dev)
+            self._pk2 = Packed.mapped(self._step_fields()[1], self._dev)
         return self._pk2
 
     def _encode(self, state):

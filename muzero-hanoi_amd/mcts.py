@@ -4,7 +4,8 @@
 return types, RNG consumption (global legacy NumPy stream, see rng.py), MinMaxStats persistence
 across calls on one instance (mcts.py:23) and `return_latent_actions`.  The whole search -- root
 inference, every simulation's select / MLP expansion / backup, and the play policy -- is one
-fused libmzh kernel launch on the GPU (mzh_search).
+fused libmzh kernel launch on the GPU (mzh_search).  Every one-root call (run_mcts, run_mcts_step,
+play_episode; a network or a RecordedNetwork) goes through one host path, `_OneRootSearch`.
 
 `MCTS.run_batch(states, ...)` runs B independent searches in one launch (each root with its own
 MinMaxStats, i.e. B fresh single-root searches), the form the bench and batched self-play use.
@@ -17,6 +18,7 @@ import torch
 
 from . import _lib
 from . import rng as _rng
+from .engine import Engine, pack_replay
 from .networks import engine_for
 from .staging import Packed
 
@@ -27,8 +29,6 @@ _REPLAY_ENGINES = {}
 
 
 def _replay_engine(n_disks, n_sims):
-    from .engine import Engine
-
     eng = _REPLAY_ENGINES.get(n_disks)
     if eng is None or eng.max_sims < n_sims:
         eng = Engine(n_disks, max(n_sims, 64), 1, 33)
@@ -70,6 +70,106 @@ class RecordedNetwork:
         self.cursor += 1
         return c
 
+    def next_replay(self, device):
+        """next_call() as Engine.search's `replay` tensors: fp32 [1, ...] on `device`"""
+        call = self.next_call()
+        return {k: torch.as_tensor(np.asarray(call[k], np.float32)).to(device)[None]
+                for k in ("root_pi", "pi", "reward", "value")}
+
+
+class _OneRootSearch:
+    """The host side of one one-root search: the staging records (the kernel reads its inputs from and writes
+    its outputs to pinned host memory where the device can address it -- a call is one launch and one
+    synchronisation -- else one copy each way), a SearchArgs with their device addresses filled in once, and the
+    staging addresses rng.predraw_into writes the draws to.  `launch` does not synchronise; `read` follows the
+    caller's synchronisation (pout.to_host() or an event)."""
+
+    def __init__(self, eng, S, in_dim):
+        self.eng, self.S = eng, S
+        self.pin = Packed.mapped([("obs", torch.float32, (1, in_dim)), ("noise", torch.float64, (1, 6)),
+                                  ("tie", torch.int32, (1,)), ("u", torch.float64, (1,)),
+                                  ("mm", torch.float64, (1, 2))], eng.device)
+        self.pout = Packed.mapped([("visits", torch.int32, (1, 6)), ("root_q", torch.float64, (1,)),
+                                   ("minmax", torch.float64, (1, 2)), ("extra_ties", torch.int32, (1,)),
+                                   ("action", torch.int32, (1,)), ("pi", torch.float64, (1, 6)),
+                                   ("latent", torch.int32, (1, S + 1)), ("latent_len", torch.int32, (1,)),
+                                   ("sel_steps", torch.int32, (1,))], eng.device)
+        a = self.args = _lib.SearchArgs()
+        a.B, a.n_sims = 1, S
+        a.tie_idx = self.pin.dptr["tie"]
+        for k, f in _lib.SEARCH_OUTPUTS:
+            setattr(a, k, self.pout.dptr[f])
+        # what every call uses, looked up once: the call itself, the draws' arrays and their addresses, views of
+        # the records and the inputs' device addresses
+        L = _lib.lib()
+        self._call = {False: L.mzh_search, True: L.mzh_search_replay}, ctypes.byref(a)
+        h, o, d = self.pin.h, self.pout.h, self.pin.dptr
+        self.draws = (h["noise"], h["tie"], h["u"])
+        self.addrs = tuple(x.ctypes.data for x in self.draws)
+        self.obs, self.mm = h["obs"][0], h["mm"][0]
+        self.d_obs, self.d_mm, self.d_noise, self.d_u = d["obs"], d["mm"], d["noise"], d["u"]
+        self.out = tuple(v.reshape(-1) for v in o.values())  # flat views, in the record's field order
+        self.bad_temperature = None
+        self._keep = None  # a replay's tensors, alive until the next launch
+
+    def launch(self, m, temperature, deterministic, state=None, replay=None, obs_ptr=None, minmax_ptr=None):
+        """Draw (reference order, straight into the staging record), stage and launch `m`'s search on the current
+        stream.  The observation is `state`, or what a device address holds (`obs_ptr`), or none for a
+        `replay` (RecordedNetwork.next_replay: the tree-only kernel); MinMaxStats come from `m` or from
+        `minmax_ptr` (MCTS.play_episode chains a decision to the previous one's device outputs)."""
+        # the reference raises for a bad temperature inside generate_play_policy (mcts.py:113, 163-166): after
+        # the whole search (Dirichlet draw, argmax tie draws, MinMaxStats updates, latent_actions) and before
+        # the action draw (mcts.py:120).  So the search runs, its state is kept, no action uniform is drawn,
+        # then the ValueError (in `read`).
+        bad_t = not 0.0 <= temperature <= 1.0
+        self.bad_temperature = temperature if bad_t else None
+        eps = m.root_exploration_eps
+        noisy, drew_u = _rng.predraw_into(*self.draws, deterministic=deterministic, alpha=m.root_dirichlet_alpha,
+                                          eps=eps, draw_action=not bad_t, addrs=self.addrs)
+        if bad_t:
+            deterministic, temperature = True, 0.0  # the kernel's policy output is discarded
+        temperature = float(temperature)
+        if state is not None:
+            self.obs[:] = state
+        if minmax_ptr is None:
+            mms, mm = m.min_max_stats, self.mm
+            mm[0] = mms.maximum
+            mm[1] = mms.minimum
+        self.pin.to_device()
+        a, eng = self.args, self.eng
+        a.discount = float(m.discount)
+        a.eps = float(eps)
+        a.temperature = temperature
+        a.deterministic = 1 if deterministic else 0
+        a.flags = _lib.MZH_FLAG_NP1_UCB if m.np1_ucb else 0
+        a.obs = None if replay is not None else (obs_ptr or self.d_obs)
+        a.minmax_in = minmax_ptr or self.d_mm
+        a.noise = self.d_noise if noisy else None
+        a.action_u = self.d_u if drew_u else None
+        pt = eng.pow_table(self.S, temperature)
+        a.pow_table = None if pt is None else pt.data_ptr()
+        if replay is not None:
+            self._keep = (replay["root_pi"].contiguous(), pack_replay(replay))
+            a.rp_root_pi, a.rp_sim = (t.data_ptr() for t in self._keep)
+        fns, aref = self._call
+        _lib.check(fns[replay is not None](eng._h, aref, _lib.stream_handle(eng.device)), "mzh_search")
+
+    def read(self, m):
+        """the launched search's results, once they are in the host record: MinMaxStats, the latent path and
+        extra_ties go back to `m`; returns (action int, pi np.float64[6], root Q float)"""
+        _, root_q, minmax, extra_ties, action, pi, latent, latent_len, _ = self.out
+        mms = m.min_max_stats
+        mms.maximum = float(minmax[0])
+        mms.minimum = float(minmax[1])
+        m._latent_host = latent[:int(latent_len[0])].tolist()  # tensors made on first access
+        ties = m.last_extra_ties = int(extra_ties[0])
+        if ties:
+            warnings.warn("search met an argmax tie beyond the root's first selection: the NumPy RNG stream "
+                          "now differs from the reference's", RuntimeWarning)
+        if self.bad_temperature is not None:
+            raise ValueError(f"Expect `temperature` to be in the range [0.0, 1.0], got {self.bad_temperature}")
+        return int(action[0]), pi.astype(np.float64), float(root_q[0])
+
 
 class MCTS:
     def __init__(self, discount, root_dirichlet_alpha, n_simulations, batch_s, device, h_dim=64, clip_grad=True,
@@ -86,119 +186,44 @@ class MCTS:
         self.latent_actions = []
         self.np1_ucb = False  # True: NumPy-1.x UCB rounding (the reference's numpy==1.25.2 pin)
         self.last_extra_ties = 0
+        self._one_key, self._one = None, []
 
     # ------------------------------------------------------------------ reference API
     def run_mcts(self, state, network, temperature, deterministic):
         """mcts.py:34-126 -> (action int, pi np.float64[6], root Q float)."""
         if self.pb_c_base != 19652 or self.pb_c_init != 1.25:
             raise NotImplementedError("libmzh bakes pb_c_base=19652, pb_c_init=1.25 (mcts.py:24-25)")
+        one = self._launch(state, network, temperature, deterministic)
+        one.pout.to_host()
+        return one.read(self)
+
+    def _one_root(self, eng, S, in_dim, n=1):
+        """n _OneRootSearch objects, cached per (engine, S, observation width)"""
+        key = (id(eng), S, in_dim)  # the cached objects hold `eng`: its id is not reused meanwhile
+        if self._one_key != key:
+            self._one_key, self._one = key, []
+        while len(self._one) < n:
+            self._one.append(_OneRootSearch(eng, S, in_dim))
+        return self._one
+
+    def _launch(self, state, network, temperature, deterministic):
+        """run_mcts up to the launch: a network's search on its engine, a RecordedNetwork's next call on the
+        replay engine (tree-only kernel; the observation is staged but not read)"""
         S = int(self.n_simulations)
-        # the reference raises for a bad temperature inside generate_play_policy (mcts.py:113,
-        # 163-166): after the whole search (Dirichlet draw, argmax tie draws, MinMaxStats updates,
-        # latent_actions) and before the action draw (mcts.py:120).  So the search runs, its state
-        # is kept, no action uniform is drawn, then the ValueError.
-        bad_t = not 0.0 <= temperature <= 1.0
-        if not isinstance(network, RecordedNetwork):
-            return self._run_mcts_fast(state, network, temperature, deterministic, S, bad_t)
-        noise, tie, u = _rng.predraw(1, deterministic=deterministic, alpha=self.root_dirichlet_alpha,
-                                     eps=self.root_exploration_eps, draw_action=not bad_t)
-        if bad_t:
-            deterministic, temperature_k = True, 0.0  # the kernel's policy output is discarded
-        else:
-            temperature_k = temperature
-        replay = None
+        x = np.asarray(state).reshape(-1)
         if isinstance(network, RecordedNetwork):
             eng = _replay_engine(network.n_disks, S)
-            call = network.next_call()
-            replay = {k: torch.as_tensor(np.asarray(call[k], np.float32)).to(eng.device)[None]
-                      for k in ("root_pi", "pi", "reward", "value")}
+            replay = network.next_replay(eng.device)
         else:
-            eng = engine_for(network, S, 1)
-        dev = eng.device
-        x = np.asarray(state).reshape(-1)
-        # inputs down in one copy, every output back in one copy (staging.Packed)
-        pin, pout = self._packed(eng, S, x.size, replay is not None)
-        h = pin.h
-        h["obs"][0] = x
-        h["mm"][0] = (self.min_max_stats.maximum, self.min_max_stats.minimum)
-        h["tie"][:] = tie
-        if noise is not None:
-            h["noise"][:] = noise
-        if u is not None:
-            h["u"][:] = u
-        pin.to_device()
-        d = pin.d
-        out = eng.search(S, obs=None if replay else d["obs"], replay=replay, tie_idx=d["tie"],
-                         noise=None if noise is None else d["noise"], action_u=None if u is None else d["u"],
-                         minmax_in=d["mm"], temperature=float(temperature_k), deterministic=bool(deterministic),
-                         discount=float(self.discount), eps=float(self.root_exploration_eps), np1_ucb=self.np1_ucb,
-                         out=dict(pout.d))
-        pout.to_host()
-        host = pout.h
-        self.min_max_stats.maximum = float(host["minmax"][0, 0])
-        self.min_max_stats.minimum = float(host["minmax"][0, 1])
-        L = int(host["latent_len"][0])
-        self._latent_host = [int(m) for m in host["latent"][0, :L]]  # tensors made on first access
-        self.last_extra_ties = int(host["extra_ties"][0])
-        if self.last_extra_ties:
-            warnings.warn("search met an argmax tie beyond the root's first selection: the NumPy RNG stream "
-                          "now differs from the reference's", RuntimeWarning)
-        if bad_t:
-            raise ValueError(f"Expect `temperature` to be in the range [0.0, 1.0], got {temperature}")
-        return int(host["action"][0]), host["pi"][0].astype(np.float64), float(host["root_q"][0])
+            eng, replay = engine_for(network, S, 1), None
+        one = self._one_root(eng, S, x.size)[0]
+        one.launch(self, temperature, deterministic, x, replay)
+        return one
 
-    def _run_mcts_fast(self, state, network, temperature, deterministic, S, bad_t):
-        """run_mcts for a network: the draws go straight into the pinned staging buffer (rng.predraw_into),
-        and the search arguments -- every device pointer of the staging buffers fixed -- are built once per
-        (engine, S, observation width) and only their scalars and optional pointers set per call"""
-        eng, pout = self._launch_fast(state, network, temperature, deterministic, S, bad_t)
-        pout.to_host()
-        return self._finish_fast(pout, temperature, bad_t)
-
-    def _launch_fast(self, state, network, temperature, deterministic, S, bad_t):
-        eng = engine_for(network, S, 1)
-        x = np.asarray(state).reshape(-1)
-        pin, pout, a, addrs = self._prepared(eng, S, x.size)
-        h = pin.h
-        noisy, drew_u = _rng.predraw_into(h["noise"], h["tie"], h["u"], deterministic=deterministic,
-                                          alpha=self.root_dirichlet_alpha, eps=self.root_exploration_eps,
-                                          draw_action=not bad_t, addrs=addrs)
-        if bad_t:
-            deterministic, temperature_k = True, 0.0  # the kernel's policy output is discarded
-        else:
-            temperature_k = temperature
-        h["obs"][0] = x
-        mm = h["mm"][0]
-        mm[0] = self.min_max_stats.maximum
-        mm[1] = self.min_max_stats.minimum
-        pin.to_device()
-        a.n_sims = S
-        a.discount = float(self.discount)
-        a.eps = float(self.root_exploration_eps)
-        a.temperature = float(temperature_k)
-        a.deterministic = 1 if deterministic else 0
-        a.flags = _lib.MZH_FLAG_NP1_UCB if self.np1_ucb else 0
-        d = self._pk_ptrs
-        a.noise = d["noise"] if noisy else None
-        a.action_u = d["u"] if drew_u else None
-        pt = eng.pow_table(S, float(temperature_k))
-        a.pow_table = None if pt is None else pt.data_ptr()
-        _lib.check(_lib.lib().mzh_search(eng._h, ctypes.byref(a), _lib.stream_handle(eng.device)), "mzh_search")
-        return eng, pout
-
-    def _finish_fast(self, pout, temperature, bad_t):
-        host = pout.h
-        self.min_max_stats.maximum = float(host["minmax"][0, 0])
-        self.min_max_stats.minimum = float(host["minmax"][0, 1])
-        L = int(host["latent_len"][0])
-        self._latent_host = [int(m) for m in host["latent"][0, :L]]  # tensors made on first access
-        self.last_extra_ties = int(host["extra_ties"][0])
-        if self.last_extra_ties:
-            warnings.warn("search met an argmax tie beyond the root's first selection: the NumPy RNG stream "
-                          "now differs from the reference's", RuntimeWarning)
-        if bad_t:
-            raise ValueError(f"Expect `temperature` to be in the range [0.0, 1.0], got {temperature}")
-        return int(host["action"][0]), host["pi"][0].astype(np.float64), float(host["root_q"][0])
+    def _chains(self, network, temperature, env):
+        """whether run_mcts_step / play_episode may chain a search to `env`'s step on the device"""
+        return (not isinstance(network, RecordedNetwork) and 0.0 <= temperature <= 1.0 and env.reset_check
+                and self.pb_c_base == 19652 and self.pb_c_init == 1.25)
 
     def run_mcts_step(self, state, network, temperature, deterministic, env):
         """run_mcts(state, ...) followed by env.step(action) (Muzero._play_game's pair of calls,
@@ -208,19 +233,17 @@ class MCTS:
         network, a temperature it refuses, an env not reset, other UCB constants) -- the caller then makes
         the two calls; with staging through copies or the env on another device the two run one after
         the other here."""
-        S = int(self.n_simulations)
-        if (isinstance(network, RecordedNetwork) or not 0.0 <= temperature <= 1.0 or not env.reset_check
-                or self.pb_c_base != 19652 or self.pb_c_init != 1.25):
+        if not self._chains(network, temperature, env):
             return None
-        eng, pout = self._launch_fast(state, network, temperature, deterministic, S, False)
-        pk = env._packed()
-        if pout.zero_copy and pk.zero_copy and torch.device(eng.device) == env._dev:
+        one = self._launch(state, network, temperature, deterministic)
+        pout, dev = one.pout, one.eng.device
+        if pout.zero_copy and env._packed().zero_copy and torch.device(dev) == env._dev:
             env._launch_step(action_ptr=pout.dptr["action"])
-            _lib.synchronize(eng.device)
-            action, pi, q = self._finish_fast(pout, temperature, False)
+            _lib.synchronize(dev)
+            action, pi, q = one.read(self)
             return action, pi, q, env._finish_step()
         pout.to_host()  # staging with copies: the two calls one after the other
-        action, pi, q = self._finish_fast(pout, temperature, False)
+        action, pi, q = one.read(self)
         return action, pi, q, env.step(action)
 
     def play_episode(self, env, network, temperature, deterministic):
@@ -234,24 +257,20 @@ class MCTS:
         (tests/test_selfplay.py).  Returns (steps, obs list, actions, rewards, pis, root Qs) or None where the
         pipeline does not apply (then the caller makes the per-decision calls)."""
         S = int(self.n_simulations)
-        rs = np.random.mtrand._rand
-        bg = rs._bit_generator
-        if (isinstance(network, RecordedNetwork) or not 0.0 <= temperature <= 1.0 or not env.reset_check
-                or self.pb_c_base != 19652 or self.pb_c_init != 1.25 or type(bg).__name__ != "MT19937"
+        bg = np.random.mtrand._rand._bit_generator
+        if (not self._chains(network, temperature, env) or type(bg).__name__ != "MT19937"
                 or (_rng.uses_noise(deterministic, self.root_dirichlet_alpha, self.root_exploration_eps)
                     and not 0.0 < float(self.root_dirichlet_alpha) <= 1.0)):
             return None
         eng = engine_for(network, S, 1)
         x0 = np.asarray(env.oneH_c_state if hasattr(env, "oneH_c_state") else None)
-        sets = self._prepared2(eng, S, env.discs * 3)
+        sets = self._one_root(eng, S, env.discs * 3, 2)  # alternating between decisions
         ek, eo = env._packed(), env._packed_out2()
-        if not all(p.zero_copy for st in sets for p in st[:2]) or not (ek.zero_copy and eo.zero_copy) \
+        if not all(p.zero_copy for one in sets for p in (one.pin, one.pout)) or not (ek.zero_copy and eo.zero_copy) \
                 or torch.device(eng.device) != env._dev or x0.shape != (env.discs * 3,):
             return None
         stream = _lib.stream_handle(eng.device)
         L = _lib.lib()
-        pt = eng.pow_table(S, float(temperature))
-        flags = _lib.MZH_FLAG_NP1_UCB if self.np1_ucb else 0
         outs = [(ek.h, ek.dptr), (eo.h, eo.dptr)]  # env output records, alternating
         q = ek.dptr  # state / ctr / active: one record, updated in place decision after decision
         eh = ek.h
@@ -264,26 +283,14 @@ class MCTS:
         evs = [torch.cuda.Event(), torch.cuda.Event()]
 
         def launch(k):
-            pin, pout, a, addrs = sets[k % 2]
-            h = pin.h
-            noisy, drew_u = _rng.predraw_into(h["noise"], h["tie"], h["u"], deterministic=deterministic,
-                                              alpha=self.root_dirichlet_alpha, eps=self.root_exploration_eps,
-                                              draw_action=True, addrs=addrs)
+            one = sets[k % 2]
             if k == 0:
-                h["obs"][0] = x0
-                h["mm"][0] = (self.min_max_stats.maximum, self.min_max_stats.minimum)
-                a.obs, a.minmax_in = pin.dptr["obs"], pin.dptr["mm"]
+                one.launch(self, temperature, deterministic, state=x0)
             else:  # the previous decision's env observation and search MinMaxStats, on the device
-                a.obs = outs[(k - 1) % 2][1]["obs"]
-                a.minmax_in = sets[(k - 1) % 2][1].dptr["minmax"]
-            a.n_sims, a.discount, a.eps = S, float(self.discount), float(self.root_exploration_eps)
-            a.temperature, a.deterministic, a.flags = float(temperature), 1 if deterministic else 0, flags
-            a.noise = pin.dptr["noise"] if noisy else None
-            a.action_u = pin.dptr["u"] if drew_u else None
-            a.pow_table = None if pt is None else pt.data_ptr()
-            _lib.check(L.mzh_search(eng._h, ctypes.byref(a), stream), "mzh_search")
+                one.launch(self, temperature, deterministic, obs_ptr=outs[(k - 1) % 2][1]["obs"],
+                           minmax_ptr=sets[(k - 1) % 2].pout.dptr["minmax"])
             o = outs[k % 2][1]
-            _lib.check(L.mzh_env_step(env.discs, env.goal_peg, env.max_steps, 1, q["state"], pout.dptr["action"],
+            _lib.check(L.mzh_env_step(env.discs, env.goal_peg, env.max_steps, 1, q["state"], one.pout.dptr["action"],
                                       o["moved"], o["obs"], o["code"], o["done"], o["illegal"], q["ctr"], q["active"],
                                       None, stream), "mzh_env_step")
             evs[k % 2].record(torch.cuda.current_stream(eng.device))
@@ -295,19 +302,11 @@ class MCTS:
             ctypes.memmove(saved, st_addr, 2500)  # the stream before the speculative next decision's draws
             launch(k + 1)
             evs[k % 2].synchronize()
-            pout = sets[k % 2][1]
-            ph, oh = pout.h, outs[k % 2][0]
-            self.min_max_stats.maximum = float(ph["minmax"][0, 0])
-            self.min_max_stats.minimum = float(ph["minmax"][0, 1])
-            n = int(ph["latent_len"][0])
-            self._latent_host = [int(m) for m in ph["latent"][0, :n]]
-            self.last_extra_ties = int(ph["extra_ties"][0])
-            if self.last_extra_ties:
-                warnings.warn("search met an argmax tie beyond the root's first selection: the NumPy RNG stream "
-                              "now differs from the reference's", RuntimeWarning)
-            act_l.append(int(ph["action"][0]))
-            pi_l.append(ph["pi"][0].astype(np.float64))
-            q_l.append(float(ph["root_q"][0]))
+            action, pi, root_q = sets[k % 2].read(self)
+            oh = outs[k % 2][0]
+            act_l.append(action)
+            pi_l.append(pi)
+            q_l.append(root_q)
             rwd_l.append(_ENV_REWARD[int(oh["code"][0])])
             done = bool(oh["done"][0])
             if done:
@@ -319,71 +318,6 @@ class MCTS:
         env.c_state = tuple(int(v) for v in eh["state"][0])
         env.step_counter, env.reset_check = int(eh["ctr"][0]), bool(eh["active"][0])
         return k + 1, obs_l, act_l, rwd_l, pi_l, q_l
-
-    def _prepared2(self, eng, S, in_dim):
-        """two sets of zero-copy staging buffers and SearchArgs (play_episode's pipeline alternates them)"""
-        key = (id(eng), S, in_dim)
-        if getattr(self, "_args2_key", None) != key:
-            sets = []
-            for _ in range(2):
-                fin = [("obs", torch.float32, (1, in_dim)), ("noise", torch.float64, (1, 6)),
-                       ("tie", torch.int32, (1,)), ("u", torch.float64, (1,)), ("mm", torch.float64, (1, 2))]
-                fout = [("visits", torch.int32, (1, 6)), ("root_q", torch.float64, (1,)),
-                        ("minmax", torch.float64, (1, 2)), ("extra_ties", torch.int32, (1,)),
-                        ("action", torch.int32, (1,)), ("pi", torch.float64, (1, 6)),
-                        ("latent", torch.int32, (1, S + 1)), ("latent_len", torch.int32, (1,)),
-                        ("sel_steps", torch.int32, (1,))]
-                try:
-                    pin, pout = Packed(fin, eng.device, zero_copy=True), Packed(fout, eng.device, zero_copy=True)
-                except RuntimeError:
-                    pin, pout = Packed(fin, eng.device), Packed(fout, eng.device)
-                a = _lib.SearchArgs()
-                a.B = 1
-                a.tie_idx = pin.dptr["tie"]
-                o = pout.dptr
-                for k, f in (("visits", "visits"), ("root_q", "root_q"), ("minmax_out", "minmax"),
-                             ("extra_ties", "extra_ties"), ("action", "action"), ("pi", "pi"), ("latent", "latent"),
-                             ("latent_len", "latent_len"), ("sel_steps", "sel_steps")):
-                    setattr(a, k, o[f])
-                h = pin.h
-                sets.append((pin, pout, a, (h["noise"].ctypes.data, h["tie"].ctypes.data, h["u"].ctypes.data)))
-            self._sets2 = sets
-            self._args2_key = key
-        return self._sets2
-
-    def _prepared(self, eng, S, in_dim):
-        """zero-copy staging buffers (the search kernel reads its inputs from and writes its outputs to pinned
-        host memory: a call is one launch and one synchronisation) and a SearchArgs holding their device
-        addresses, cached per (engine, S, observation width)"""
-        key = (id(eng), S, in_dim)
-        if getattr(self, "_args_key", None) != key:
-            fin = [("obs", torch.float32, (1, in_dim)), ("noise", torch.float64, (1, 6)), ("tie", torch.int32, (1,)),
-                   ("u", torch.float64, (1,)), ("mm", torch.float64, (1, 2))]
-            fout = [("visits", torch.int32, (1, 6)), ("root_q", torch.float64, (1,)), ("minmax", torch.float64, (1, 2)),
-                    ("extra_ties", torch.int32, (1,)), ("action", torch.int32, (1,)), ("pi", torch.float64, (1, 6)),
-                    ("latent", torch.int32, (1, S + 1)), ("latent_len", torch.int32, (1,)),
-                    ("sel_steps", torch.int32, (1,))]
-            try:
-                pin, pout = Packed(fin, eng.device, zero_copy=True), Packed(fout, eng.device, zero_copy=True)
-            except RuntimeError:  # no device address for pinned memory here: one copy each way
-                pin, pout = Packed(fin, eng.device), Packed(fout, eng.device)
-            d, o = pin.dptr, pout.dptr
-            self._pk_ptrs = d
-            a = _lib.SearchArgs()
-            a.B = 1
-            a.obs = d["obs"]
-            a.tie_idx = d["tie"]
-            a.minmax_in = d["mm"]
-            for k, f in (("visits", "visits"), ("root_q", "root_q"), ("minmax_out", "minmax"),
-                         ("extra_ties", "extra_ties"), ("action", "action"), ("pi", "pi"), ("latent", "latent"),
-                         ("latent_len", "latent_len"), ("sel_steps", "sel_steps")):
-                setattr(a, k, o[f])
-            h = pin.h
-            self._prep = (pin, pout)
-            self._args = a
-            self._addrs = (h["noise"].ctypes.data, h["tie"].ctypes.data, h["u"].ctypes.data)
-            self._args_key = key
-        return self._prep[0], self._prep[1], self._args, self._addrs
 
     def return_latent_actions(self):
         return self.latent_actions
@@ -400,21 +334,6 @@ class MCTS:
     def latent_actions(self, value):
         self._latent = value
         self._latent_host = None
-
-    def _packed(self, eng, S, in_dim, replay):
-        key = (id(eng), S, in_dim, replay)
-        if getattr(self, "_pk_key", None) != key:
-            dev = eng.device
-            self._pk_in = Packed([("obs", torch.float32, (1, in_dim)), ("noise", torch.float64, (1, 6)),
-                                  ("tie", torch.int32, (1,)), ("u", torch.float64, (1,)),
-                                  ("mm", torch.float64, (1, 2))], dev)
-            self._pk_out = Packed([("visits", torch.int32, (1, 6)), ("root_q", torch.float64, (1,)),
-                                   ("minmax", torch.float64, (1, 2)), ("extra_ties", torch.int32, (1,)),
-                                   ("action", torch.int32, (1,)), ("pi", torch.float64, (1, 6)),
-                                   ("latent", torch.int32, (1, S + 1)), ("latent_len", torch.int32, (1,)),
-                                   ("sel_steps", torch.int32, (1,))], dev)
-            self._pk_key = key
-        return self._pk_in, self._pk_out
 
     def add_dirichlet_noise(self, prob, eps=0.25, alpha=0.25):
         """mcts.py:132-152 (host form, for callers that use it directly)."""

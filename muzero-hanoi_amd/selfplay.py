@@ -36,6 +36,7 @@ from . import rng as _rng
 from .engine import env_step as _env_step
 from .engine import hanoi_solver_batch
 from .env import HanoiBatch
+from .mcts import RecordedNetwork, _replay_engine
 from .networks import engine_for
 from .utils import adjust_temperature, compute_MCreturns, compute_n_step_returns, organise_transitions
 
@@ -117,14 +118,43 @@ class BatchedSelfPlay:
         self.discount, self.alpha, self.eps, self.goal_peg = discount, dirichlet_alpha, root_exploration_eps, goal_peg
         self.np1_ucb = np1_ucb
 
-    def _engine(self, B):
-        from .mcts import RecordedNetwork, _replay_engine
+    def _setup(self, start_idx, minmax, seed):
+        """-> start [B] int64, the engine, whether it replays a RecordedNetwork, the envs reset to the starts and
+        their observations, the generator of the synthetic draws' seeds, and the agents' MinMaxStats [B, 2] (default: fresh)"""
+        start = torch.as_tensor(np.asarray(start_idx), dtype=torch.int64).reshape(-1)
+        B = int(start.shape[0])
+        replay = isinstance(self.network, RecordedNetwork)
+        if replay and B != 1:
+            raise ValueError("a RecordedNetwork replays one sequential stream of searches: B must be 1")
+        eng = _replay_engine(self.N, self.S) if replay else engine_for(self.network, self.S, B)
+        dev = eng.device
+        env = HanoiBatch(self.N, self.max_steps, B, goal_peg=self.goal_peg, device=dev)
+        obs = env.reset(start.to(dev))
+        mm = torch.empty((B, 2), dtype=torch.float64, device=dev)
+        if minmax is None:
+            mm[:, 0], mm[:, 1] = -float("inf"), float("inf")
+        else:
+            mm.copy_(torch.as_tensor(np.asarray(minmax, np.float64)).reshape(B, 2))
+        return start, eng, replay, env, obs, np.random.default_rng(seed), mm
 
-        if isinstance(self.network, RecordedNetwork):
-            if B != 1:
-                raise ValueError("a RecordedNetwork replays one sequential stream of searches: B must be 1")
-            return _replay_engine(self.N, self.S), True
-        return engine_for(self.network, self.S, B), False
+    def _draws(self, n, deterministic, legacy_rng, gen):
+        """a round's draws for n envs: the global NumPy stream, or synthetic ones seeded from `gen`"""
+        if legacy_rng:
+            return _rng.predraw(n, deterministic=deterministic, alpha=self.alpha, eps=self.eps)
+        return _rng.synthetic_draws(n, deterministic=deterministic, alpha=self.alpha, eps=self.eps,
+                                    seed=int(gen.integers(2**31)))
+
+    def _search(self, eng, replay, obs, idx, draws, mm, temperature, deterministic):
+        """one search over the envs `idx` (obs: their observations; or the RecordedNetwork's next call), their
+        MinMaxStats read from and carried into mm [B, 2]"""
+        noise, tie, u = (None if x is None else torch.as_tensor(x).to(eng.device) for x in draws)
+        out = eng.search(self.S, obs=None if replay else obs,
+                         replay=self.network.next_replay(eng.device) if replay else None, tie_idx=tie, noise=noise,
+                         action_u=u, minmax_in=mm.index_select(0, idx), temperature=float(temperature),
+                         deterministic=bool(deterministic), discount=self.discount, eps=self.eps,
+                         np1_ucb=self.np1_ucb)
+        mm.index_copy_(0, idx, out["minmax"])
+        return out
 
     def play(self, start_idx, temperature=1.0, deterministic=False, seed=0, legacy_rng=False, minmax=None,
              record_obs=False):
@@ -134,26 +164,14 @@ class BatchedSelfPlay:
         -inf / +inf); the final values come back as res["minmax"].  Returns device tensors:
         per step t (rows of envs that were still playing): action, reward, pi, root_q, active,
         obs (record_obs); per env: steps, illegal (count), start_idx, minmax."""
-        start = torch.as_tensor(np.asarray(start_idx), dtype=torch.int64).reshape(-1)
-        B = int(start.shape[0])
-        eng, replay = self._engine(B)
-        dev = eng.device
-        env = HanoiBatch(self.N, self.max_steps, B, goal_peg=self.goal_peg, device=dev)
-        obs = env.reset(start.to(dev))
-        gen = np.random.default_rng(seed)
-        mm = torch.empty((B, 2), dtype=torch.float64, device=dev)
-        if minmax is None:
-            mm[:, 0], mm[:, 1] = -float("inf"), float("inf")
-        else:
-            mm.copy_(torch.as_tensor(np.asarray(minmax, np.float64)).reshape(B, 2))
+        start, eng, replay, env, obs, gen, mm = self._setup(start_idx, minmax, seed)
+        B, dev = int(start.shape[0]), eng.device
         active = torch.ones(B, dtype=torch.bool, device=dev)
         steps = torch.zeros(B, dtype=torch.int32, device=dev)
         illegal_n = torch.zeros(B, dtype=torch.int32, device=dev)
         rec = dict(action=[], reward=[], pi=[], root_q=[], active=[])
         if record_obs:
             rec["obs"] = []
-        t = lambda a: None if a is None else torch.as_tensor(a).to(dev)
-        cut = lambda a, m: None if a is None else a[:m]
         # synthetic draws: a move's batch is drawn on the host while the GPU still runs the previous move, for
         # that move's count of envs (an upper bound), and cut to the count left once it is known (the draws
         # of n envs are the first n rows of a larger draw, rng.synthetic_draws)
@@ -163,25 +181,11 @@ class BatchedSelfPlay:
             n = int(idx.numel())
             if n == 0:
                 break
-            if legacy_rng:
-                noise, tie, u = _rng.predraw(n, deterministic=deterministic, alpha=self.alpha, eps=self.eps)
-            else:
-                if pre is None:
-                    pre = _rng.synthetic_draws(n, deterministic=deterministic, alpha=self.alpha, eps=self.eps,
-                                               seed=int(gen.integers(2**31)))
-                noise, tie, u = (cut(x, n) for x in pre)
-                pre = None
-            rp = None
-            if replay:
-                call = self.network.next_call()
-                rp = {k: torch.as_tensor(np.asarray(call[k], np.float32)).to(dev)[None]
-                      for k in ("root_pi", "pi", "reward", "value")}
+            draws = self._draws(n, deterministic, legacy_rng, gen) if pre is None else pre
+            pre = None
             sub_obs_in = obs.index_select(0, idx)
-            out = eng.search(self.S, obs=None if replay else sub_obs_in, replay=rp, tie_idx=t(tie), noise=t(noise),
-                             action_u=t(u), minmax_in=mm.index_select(0, idx), temperature=float(temperature),
-                             deterministic=bool(deterministic), discount=self.discount, eps=self.eps,
-                             np1_ucb=self.np1_ucb)
-            mm.index_copy_(0, idx, out["minmax"])
+            out = self._search(eng, replay, sub_obs_in, idx, [None if x is None else x[:n] for x in draws], mm,
+                               temperature, deterministic)
             # step only the unfinished envs (gather -> one env kernel -> scatter)
             sub_state = env.state.index_select(0, idx).contiguous()
             sub_ctr = env.step_ctr.index_select(0, idx).contiguous()
@@ -206,8 +210,7 @@ class BatchedSelfPlay:
             obs = obs.index_copy(0, idx, sub_obs)
             active = active.index_copy(0, idx, done == 0)
             if not legacy_rng and not replay:  # the next move's draws, overlapping this move's kernels
-                pre = _rng.synthetic_draws(n, deterministic=deterministic, alpha=self.alpha, eps=self.eps,
-                                           seed=int(gen.integers(2**31)))
+                pre = self._draws(n, deterministic, False, gen)
         res = {k: torch.stack(v) if v else torch.empty(0, device=dev) for k, v in rec.items()}
         res["steps"] = steps
         res["illegal"] = illegal_n
@@ -234,42 +237,18 @@ class BatchedSelfPlay:
             raise ValueError(f"play_plans: max_plan_len must be >= 1, got {max_plan_len}")
         if self.S < 1:  # the reference would execute the previous search's path (mcts.py:79 is never reached)
             raise ValueError("play_plans: a plan needs n_simulations >= 1")
-        start = torch.as_tensor(np.asarray(start_idx), dtype=torch.int64).reshape(-1)
-        B = int(start.shape[0])
-        if B < 1:
+        if np.asarray(start_idx).size < 1:
             raise ValueError("play_plans: no start states")
-        eng, replay = self._engine(B)
-        dev = eng.device
-        env = HanoiBatch(self.N, self.max_steps, B, goal_peg=self.goal_peg, device=dev)
-        env.reset(start.to(dev))
-        gen = np.random.default_rng(seed)
-        mm = torch.empty((B, 2), dtype=torch.float64, device=dev)
-        if minmax is None:
-            mm[:, 0], mm[:, 1] = -float("inf"), float("inf")
-        else:
-            mm.copy_(torch.as_tensor(np.asarray(minmax, np.float64)).reshape(B, 2))
+        start, eng, replay, env, _, gen, mm = self._setup(start_idx, minmax, seed)
+        B, dev = int(start.shape[0]), eng.device
         plans = torch.zeros(B, dtype=torch.int32, device=dev)
         rec = dict(action=[], reward=[], root_q=[], search_action=[])
-        t = lambda a: None if a is None else torch.as_tensor(a).to(dev)
         n, idx = B, torch.arange(B, device=dev)
         while n:
-            if legacy_rng:
-                noise, tie, u = _rng.predraw(n, deterministic=deterministic, alpha=self.alpha, eps=self.eps)
-            else:
-                noise, tie, u = _rng.synthetic_draws(n, deterministic=deterministic, alpha=self.alpha, eps=self.eps,
-                                                     seed=int(gen.integers(2**31)))
-            rp = None
-            if replay:
-                call = self.network.next_call()
-                rp = {k: torch.as_tensor(np.asarray(call[k], np.float32)).to(dev)[None]
-                      for k in ("root_pi", "pi", "reward", "value")}
+            draws = self._draws(n, deterministic, legacy_rng, gen)
             # the observation env.step returned last (the start's before the first plan): HanoiBatch.last_obs
             obs = env.obs() if env.last_obs is None else env.last_obs
-            out = eng.search(self.S, obs=None if replay else obs.index_select(0, idx), replay=rp, tie_idx=t(tie),
-                             noise=t(noise), action_u=t(u), minmax_in=mm.index_select(0, idx),
-                             temperature=float(temperature), deterministic=bool(deterministic),
-                             discount=self.discount, eps=self.eps, np1_ucb=self.np1_ucb)
-            mm.index_copy_(0, idx, out["minmax"])
+            out = self._search(eng, replay, obs.index_select(0, idx), idx, draws, mm, temperature, deterministic)
             # a path has at most S + 1 moves (the row stride of `latent`): a longer max_plan_len cuts nothing more
             r = env.run_plan(out["latent"], out["latent_len"], min(L, self.S + 1), env_index=idx.to(torch.int32),
                              record=True)

@@ -40,6 +40,15 @@ class Packed:
             self.d = {k: self._view(self.dev, k) for k in self.layout}  # device tensors
             self.dptr = {k: v.data_ptr() for k, v in self.d.items()}
 
+    @classmethod
+    def mapped(cls, fields, device):
+        """zero-copy where the device can address pinned host memory (a call is then one launch and one
+        synchronisation), else the form with one copy each way"""
+        try:
+            return cls(fields, device, zero_copy=True)
+        except RuntimeError:  # mzh_host_device_pointer: no device address for pinned memory here
+            return cls(fields, device)
+
     def _view(self, buf, k):
         off, dt, shape, n = self.layout[k]
         return buf[off:off + n].view(dt).view(shape)

@@ -106,3 +106,36 @@ def test_predraw_speed(rng):
         rng.predraw(65536, deterministic=False, alpha=0.25, rng=rs)
         best = min(best, time.perf_counter() - t0)
     assert best < 0.1, best
+
+
+@pytest.mark.parametrize("kw", [
+    dict(alpha=0.25, deterministic=False),
+    dict(alpha=0.25, deterministic=True),
+    dict(alpha=0.25, deterministic=False, draw_action=False),
+    dict(alpha=0.25, deterministic=False, eps=0.0),  # no root noise
+    dict(alpha=2.5, deterministic=False),  # the general path: the gamma sampler uses the Gaussian cache
+], ids=["stochastic", "deterministic", "no_action_draw", "eps0", "alpha2.5"])
+@pytest.mark.parametrize("with_addrs", [False, True])
+def test_predraw_into_equals_predraw(rng, kw, with_addrs):
+    """rng.predraw_into (the drop-in's one source of draws, written into the caller's arrays from the global
+    stream) == rng.predraw(1, ...) from the same seed, call after call, with the global stream left where
+    predraw leaves it; an array that is not drawn is left untouched"""
+    saved = np.random.get_state()
+    try:
+        np.random.seed(31)
+        np.random.standard_normal()  # a cached Gaussian before the first call
+        want_rs = np.random.RandomState(31)
+        want_rs.standard_normal()
+        for call in range(4):
+            noise, tie, u = np.full((1, 6), -7.0), np.full(1, -7, np.int32), np.full(1, -7.0)
+            addrs = (noise.ctypes.data, tie.ctypes.data, u.ctypes.data) if with_addrs else None
+            noisy, drew_u = rng.predraw_into(noise, tie, u, addrs=addrs, **kw)
+            w_noise, w_tie, w_u = rng.predraw(1, rng=want_rs, **kw)
+            assert noisy == (w_noise is not None) and drew_u == (w_u is not None), call
+            assert np.array_equal(noise, w_noise if noisy else np.full((1, 6), -7.0)), call
+            assert np.array_equal(tie, w_tie) and tie.dtype == w_tie.dtype, call
+            assert np.array_equal(u, w_u if drew_u else np.full(1, -7.0)), call
+            assert _same_state(np.random.mtrand._rand, want_rs), call
+        assert np.random.standard_normal() == want_rs.standard_normal()
+    finally:
+        np.random.set_state(saved)

@@ -1,7 +1,7 @@
 """Latency kernel vs cooperative kernel by batch size (the crossover behind mzh_api.hip kOneMaxRoots), and the
 drop-in run_mcts call broken into kernel and host time.
 
-    python tools/one_probe.py [--out profiles/r06_one_probe.json]
+    python tools/one_probe.py [--out profiles/r06_one_probe.json] [--run-mcts-only]
 
 Per (disks, sims, roots): HIP-event time of one mzh_search launch (median of 7 after 2 warm-ups) for the
 latency kernel ("one") and the cooperative kernel ("coop"), random non-goal roots, T=1 stochastic draws,
@@ -37,13 +37,14 @@ def timed(fn, reps=7, warm=2):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
+    ap.add_argument("--run-mcts-only", action="store_true", help="only the drop-in section (seconds)")
     a = ap.parse_args()
     import bench
     from muzero_hanoi_amd import engine, rng
     from muzero_hanoi_amd.networks import MuZeroNet
 
     rows = []
-    for n, S in ((3, 25), (4, 50)):
+    for n, S in () if a.run_mcts_only else ((3, 25), (4, 50)):
         torch.manual_seed(0)
         net = MuZeroNet(3 * n, 6, 0.002, "cpu", TD_return=True)
         flat = engine.flat_weights(net.state_dict())
