@@ -96,6 +96,16 @@ int mzh_weights_size(int n_disks, int support, size_t* n_floats);
  * Replaces reading MuZeroNet parameters at inference time (networks.py:71-150). Synchronous. */
 int mzh_load_weights(mzh_engine* eng, const float* flat_host, size_t n_floats);
 
+/* Upload a SET of M networks of the engine's shape (1 <= M <= 256) for mzh_search_multi: flat_host holds M
+ * canonical vectors of n_floats each, [M][n_floats].  The reference's ablation sweeps (acting_ablations.py,
+ * multi_run_ablation_eval.py, permutation_importance.py get_ablated_network) evaluate up to 8 re-initialised
+ * variants of one checkpoint one after the other; a set lets one launch search roots of all of them.
+ * Each vector is packed exactly as mzh_load_weights packs it; the M blobs lie in one device allocation of
+ * the set's own at a constant stride (one blob rounded up to 256 bytes).  The engine's single network
+ * (mzh_load_weights) and every call that uses it are untouched by a set.  Loading a set replaces the previous
+ * one.  Synchronous.  MZH_ERR_ARG: M outside [1, 256], n_floats != mzh_weights_size, a NULL pointer. */
+int mzh_load_weight_set(mzh_engine* eng, const float* flat_host, size_t n_floats, int M);
+
 /* ---------------------------------------------------------------------------------------------
  * Environment: TowersOfHanoi (env/hanoi.py), batched over B independent envs.
  * state[B][n] uint8 peg of disc d (disc 0 = smallest), the reference's tuple c_state layout.
@@ -259,6 +269,30 @@ int mzh_search_replay(mzh_engine* eng, const mzh_search_args* args, mzh_stream s
  * arguments (has_minmax_in: args.minmax_in != NULL).  Host-only: needs no device and no engine. */
 int mzh_search_plan_query(int support, int B, int n_sims, uint32_t flags, int replay, int has_minmax_in,
                           mzh_search_plan* out);
+
+/* Search roots of several networks in one launch: root b is searched under network net_index[b] of the set
+ * loaded by mzh_load_weight_set, with the result mzh_search gives on an engine holding that network alone
+ * (bit for bit).  `args` is mzh_search's, unchanged: every input and output is indexed by root.  The roots of
+ * one network must be consecutive (net_index non-decreasing); a network without roots is fine.  Two launches:
+ * a one-workgroup prologue checks net_index on the device and cuts the batch into tiles of up to 16 or 32
+ * roots of one network, then mzh_search_multi_kernel searches one tile per workgroup on a grid of
+ * ceil(B / tile) + min(n_networks, B) - 1 workgroups (the most tiles B roots can make; workgroups beyond the
+ * tiles made return at once).  args.lockstep_levels is indexed by tile, args.plan_out names the launched
+ * instantiation with that grid.
+ *   MZH_FLAG_NP1_UCB, MZH_FLAG_COOP_TILE16 / 32 (default: by B as in mzh_search) and MZH_FLAG_KERNEL_COOP
+ *   are honoured; only the cooperative kernel has a multi-network form.
+ * Refused before anything is launched: no set loaded (MZH_ERR_STATE); n_networks outside [1, M of the set],
+ * a NULL net_index, replay inputs (rp_sim / rp_root_pi), or any of MZH_FLAG_KERNEL_WAVE / _WAVE16 /
+ * _KERNEL_ONE / _COOP_OCC2 (MZH_ERR_ARG: a forced kernel that cannot serve the search is an error, never a
+ * fallback); B or n_sims beyond the engine (MZH_ERR_CAPACITY); the temperature as in mzh_search.
+ * Refused on the device: a net_index that decreases or has an entry outside [0, n_networks) -- no root is
+ * searched, no output of args is written, and status[0] = 1. */
+typedef struct mzh_multi_args {
+  int32_t n_networks;        /* M of the loaded set this call may index */
+  const int32_t* net_index;  /* [B] device: network of root b, non-decreasing, each in [0, M) */
+  int32_t* status;           /* [2] device, nullable: [0] 0 = searched, 1 = net_index refused; [1] tiles launched */
+} mzh_multi_args;
+int mzh_search_multi(mzh_engine* eng, const mzh_search_args* args, const mzh_multi_args* multi, mzh_stream stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Reference-order host pre-draw (HOST pointers only; no device, no engine).  Replaces the NumPy

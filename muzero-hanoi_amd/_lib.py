@@ -57,6 +57,11 @@ class SearchArgs(ctypes.Structure):
     ]
 
 
+class MultiArgs(ctypes.Structure):
+    """mirror of struct mzh_multi_args (include/mzh.h)"""
+    _fields_ = [("n_networks", _i32), ("net_index", _vp), ("status", _vp)]
+
+
 # SearchArgs output pointer -> the name its array has in a search's result (Engine.search, MCTS.run_mcts)
 SEARCH_OUTPUTS = (("visits", "visits"), ("root_q", "root_q"), ("minmax_out", "minmax"), ("extra_ties", "extra_ties"),
                   ("action", "action"), ("pi", "pi"), ("latent", "latent"), ("latent_len", "latent_len"),
@@ -114,6 +119,7 @@ SIGNATURES = {
     "mzh_destroy": (ctypes.c_int, [_vp]),
     "mzh_weights_size": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
     "mzh_load_weights": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t]),
+    "mzh_load_weight_set": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_int]),
     "mzh_env_step": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [_vp] * 10 + [_vp]),
     "mzh_env_run_plan": (ctypes.c_int, [ctypes.POINTER(PlanArgs), _vp]),
     "mzh_legal_mask": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),
@@ -123,6 +129,7 @@ SIGNATURES = {
     "mzh_recurrent_inference": (ctypes.c_int, [_vp, ctypes.c_int] + [_vp] * 9 + [_vp]),
     "mzh_search": (ctypes.c_int, [_vp, ctypes.POINTER(SearchArgs), _vp]),
     "mzh_search_replay": (ctypes.c_int, [_vp, ctypes.POINTER(SearchArgs), _vp]),
+    "mzh_search_multi": (ctypes.c_int, [_vp, ctypes.POINTER(SearchArgs), ctypes.POINTER(MultiArgs), _vp]),
     "mzh_search_plan_query": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int,
                                              ctypes.c_int, ctypes.POINTER(SearchPlan)]),
     "mzh_rng_predraw": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int,

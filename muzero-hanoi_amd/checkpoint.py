@@ -8,6 +8,8 @@ re-packs the weights into the MFMA layout the next time the network is used (net
 tracks parameter versions).  Loading uses torch.load(weights_only=True): nothing in the file is
 executed.
 """
+import copy
+
 import torch
 
 from .networks import MuZeroNet
@@ -42,3 +44,27 @@ def ablate_networks(reset_latent_policy, reset_latent_values, reset_latent_rwds,
     if reset_latent_rwds:
         networks.rwd_net.apply(networks.reset_param)
     return networks
+
+
+def ablation_label(reset_latent_policy, reset_latent_values, reset_latent_rwds):
+    """acting_ablations.py:149-162 (save_results_to_file): the result file's label of a switch combination"""
+    label = (("ResetLatentPol_" if reset_latent_policy else "") + ("ResetLatentVal_" if reset_latent_values else "")
+             + ("ResetLatentRwd_" if reset_latent_rwds else ""))
+    return label or "Muzero_"
+
+
+def ablation_variants(net):
+    """The 8 combinations of ablate_networks' three switches, each applied to a deep copy of `net`:
+    [(label, network)] with the reference's labels (ablation_label), `net` itself untouched.
+
+    Order: the switches count up as a 3-bit number (policy, values, rwds) with rwds the fastest --
+    "Muzero_", "ResetLatentRwd_", "ResetLatentVal_", "ResetLatentVal_ResetLatentRwd_", "ResetLatentPol_", ... --
+    and the variants draw from the global torch RNG one after the other in that order, each through
+    ablate_networks (policy_net, value_net, rwd_net; per head layer 0 then layer 2, weight then bias).  So
+    variant i equals ablate_networks on a copy after the variants before it took their draws."""
+    out = []
+    for pol in (False, True):
+        for val in (False, True):
+            for rwd in (False, True):
+                out.append((ablation_label(pol, val, rwd), ablate_networks(pol, val, rwd, copy.deepcopy(net))))
+    return out

@@ -64,6 +64,14 @@ struct mzh_engine {
   float* htree = nullptr;
   uint16_t* pathx = nullptr;
   double* table = nullptr;
+  // the network set of mzh_load_weight_set (its own allocation; the single-network calls never read it)
+  void* setbuf = nullptr;      // [M] blobs at set_stride bytes, then [M][2] floats (MzhPackedSet)
+  int set_m = 0;               // 0: no set loaded
+  size_t set_stride = 0;
+  MzhNet setnet{};             // network 0 of the set: the template mzh_search_multi_kernel offsets
+  const float* set_scal = nullptr;
+  MzhTile* mtiles = nullptr;   // tile table workspace of mzh_search_multi, allocated with the first set
+  int32_t* mntiles = nullptr;
 };
 
 extern "C" int mzh_abi_version(void) { return MZH_ABI_VERSION; }
@@ -149,7 +157,39 @@ extern "C" int mzh_destroy(mzh_engine* eng) {
   if (eng->pathx) (void)hipFree(eng->pathx);
   if (eng->table) (void)hipFree(eng->table);
   if (eng->wbuf) (void)hipFree(eng->wbuf);
+  if (eng->setbuf) (void)hipFree(eng->setbuf);
+  if (eng->mtiles) (void)hipFree(eng->mtiles);
+  if (eng->mntiles) (void)hipFree(eng->mntiles);
   delete eng;
+  return MZH_OK;
+}
+
+// the cooperative kernels' view of a packed blob uploaded at `base` (MzhPacked's offsets as pointers)
+static int make_net(const MzhPacked& pk, const float* base, int sup, int in, MzhNet* out) {
+  auto mk = [&](const PackedLayer& pl) {
+    MzhLayer m;
+    m.w = reinterpret_cast<const float4*>(base + pl.woff);
+    m.b = base + pl.boff;
+    m.kb = pl.kb;
+    m.nt = pl.nt;
+    m.woff = (int)(pl.woff * sizeof(float));
+    m.boff = (int)(pl.boff * sizeof(float));
+    return m;
+  };
+  MzhNet n{};
+  n.wbase = base;
+  n.rep0 = mk(pk.L[MZH_REP0]); n.rep2 = mk(pk.L[MZH_REP2]); n.dyn0 = mk(pk.L[MZH_DYN0]); n.dyn2 = mk(pk.L[MZH_DYN2]);
+  n.rwd0 = mk(pk.L[MZH_RWD0]); n.rwd2 = mk(pk.L[MZH_RWD2]); n.pol0 = mk(pk.L[MZH_POL0]); n.pol2 = mk(pk.L[MZH_POL2]);
+  n.val0 = mk(pk.L[MZH_VAL0]); n.val2 = mk(pk.L[MZH_VAL2]);
+  if (n.val0.w != n.pol0.w + (size_t)n.pol0.nt * n.pol0.kb * 64)
+    return fail(MZH_ERR_STATE, "pol0/val0 weights not contiguous");
+  n.dyn0_onehot = base + pk.onehot;
+  // the wave layout's bin-32 arrays serve both kernels (null and 0 without a 33-bin head)
+  auto w32 = [&](const PackedW& pw) { return pw.w32off ? reinterpret_cast<const float4*>(base + pw.w32off) : nullptr; };
+  n.rwd32 = w32(pk.W[2]); n.val32 = w32(pk.W[4]); n.rwd32b = pk.W[2].b32; n.val32b = pk.W[4].b32;
+  n.support = sup;
+  n.in_dim = in;
+  *out = n;
   return MZH_OK;
 }
 
@@ -171,26 +211,8 @@ extern "C" int mzh_load_weights(mzh_engine* eng, const float* flat, size_t n_flo
   HIP_OK(hipMalloc(&eng->wbuf, pk.blob.size() * sizeof(float)));
   HIP_OK(hipMemcpy(eng->wbuf, pk.blob.data(), pk.blob.size() * sizeof(float), hipMemcpyHostToDevice));
   const float* base = static_cast<const float*>(eng->wbuf);
-  auto mk = [&](const PackedLayer& pl) {
-    MzhLayer m;
-    m.w = reinterpret_cast<const float4*>(base + pl.woff);
-    m.b = base + pl.boff;
-    m.kb = pl.kb;
-    m.nt = pl.nt;
-    m.woff = (int)(pl.woff * sizeof(float));
-    m.boff = (int)(pl.boff * sizeof(float));
-    return m;
-  };
-  MzhNet& n = eng->net;
-  n.wbase = base;
-  n.rep0 = mk(pk.L[MZH_REP0]); n.rep2 = mk(pk.L[MZH_REP2]); n.dyn0 = mk(pk.L[MZH_DYN0]); n.dyn2 = mk(pk.L[MZH_DYN2]);
-  n.rwd0 = mk(pk.L[MZH_RWD0]); n.rwd2 = mk(pk.L[MZH_RWD2]); n.pol0 = mk(pk.L[MZH_POL0]); n.pol2 = mk(pk.L[MZH_POL2]);
-  n.val0 = mk(pk.L[MZH_VAL0]); n.val2 = mk(pk.L[MZH_VAL2]);
-  if (n.val0.w != n.pol0.w + (size_t)n.pol0.nt * n.pol0.kb * 64)
-    return fail(MZH_ERR_STATE, "pol0/val0 weights not contiguous");
-  n.dyn0_onehot = base + pk.onehot;
-  n.support = sup;
-  n.in_dim = in;
+  const int nst = make_net(pk, base, sup, in, &eng->net);
+  if (nst) return nst;
   auto mkw = [&](const PackedW& pw) {
     MzhWMlp m;
     m.s = reinterpret_cast<const float4*>(base + pw.soff);
@@ -209,8 +231,6 @@ extern "C" int mzh_load_weights(mzh_engine* eng, const float* flat, size_t n_flo
   MzhWNet& w = eng->wnet;
   w.wbase = base;
   w.rep = mkw(pk.W[0]); w.dyn = mkw(pk.W[1]); w.rwd = mkw(pk.W[2]); w.pol = mkw(pk.W[3]); w.val = mkw(pk.W[4]);
-  // the wave layout's bin-32 arrays serve both kernels (null and 0 without a 33-bin head)
-  n.rwd32 = w.rwd.w32; n.val32 = w.val.w32; n.rwd32b = w.rwd.b32; n.val32b = w.val.b32;
   w.oh = base + pk.wonehot;
   w.support = sup;
   w.in_dim = in;
@@ -223,6 +243,37 @@ extern "C" int mzh_load_weights(mzh_engine* eng, const float* flat, size_t n_flo
   o.rep2b = base + pk.one.rep2b;
   o.l2 = reinterpret_cast<const float4*>(base + pk.one.l2);
   eng->loaded = true;
+  return MZH_OK;
+}
+
+extern "C" int mzh_load_weight_set(mzh_engine* eng, const float* flat, size_t n_floats, int M) {
+  if (!eng || !flat) return fail(MZH_ERR_ARG, "engine or weights NULL");
+  if (M < 1 || M > MZH_MULTI_MAX_NETS)
+    return fail(MZH_ERR_ARG, "weight set: M must be in [1,%d], got %d", MZH_MULTI_MAX_NETS, M);
+  const int in = eng->in_dim, sup = eng->support;
+  const size_t want = mzh_canon_view(nullptr, in, sup).total;
+  if (n_floats != want) return fail(MZH_ERR_ARG, "weight set: expected %zu floats per network, got %zu", want, n_floats);
+  const MzhPackedSet ps = mzh_pack_network_set(flat, M, in, sup);
+
+  DeviceGuard g(eng->device);
+  if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+  if (eng->setbuf) {
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipFree(eng->setbuf));
+    eng->setbuf = nullptr;
+    eng->set_m = 0;
+  }
+  if (!eng->mtiles)
+    HIP_OK(hipMalloc(&eng->mtiles, sizeof(MzhTile) * (size_t)mzh_multi_max_tiles(eng->max_roots, 16, MZH_MULTI_MAX_NETS)));
+  if (!eng->mntiles) HIP_OK(hipMalloc(&eng->mntiles, sizeof(int32_t)));
+  HIP_OK(hipMalloc(&eng->setbuf, ps.blob.size() * sizeof(float)));
+  HIP_OK(hipMemcpy(eng->setbuf, ps.blob.data(), ps.blob.size() * sizeof(float), hipMemcpyHostToDevice));
+  const float* base = static_cast<const float*>(eng->setbuf);
+  const int nst = make_net(ps.layout, base, sup, in, &eng->setnet);
+  if (nst) return nst;
+  eng->set_stride = ps.stride * sizeof(float);
+  eng->set_scal = base + ps.scal;
+  eng->set_m = M;
   return MZH_OK;
 }
 
@@ -471,6 +522,21 @@ extern "C" int mzh_search_plan_query(int support, int B, int n_sims, uint32_t fl
   return MZH_OK;
 }
 
+// the kernels' parameter block of a search call on this engine
+static MzhSearchParams search_params(const mzh_engine* eng, const mzh_search_args* a) {
+  MzhSearchParams p{};
+  p.B = a->B; p.S = a->n_sims; p.E = eng->E; p.in_dim = eng->in_dim; p.kin = eng->kin;
+  p.deterministic = a->deterministic; p.np1 = (a->flags & MZH_FLAG_NP1_UCB) ? 1 : 0;
+  p.discount = a->discount; p.eps = a->eps; p.temperature = a->temperature;
+  p.obs = a->obs; p.noise = a->noise; p.tie_idx = a->tie_idx; p.action_u = a->action_u; p.minmax_in = a->minmax_in;
+  p.rp_root_pi = a->rp_root_pi; p.rp_sim = a->rp_sim;
+  p.tree = eng->tree; p.htree = eng->htree; p.pathx = eng->pathx; p.table = eng->table;
+  p.visits = a->visits; p.root_q = a->root_q; p.minmax_out = a->minmax_out; p.extra_ties = a->extra_ties;
+  p.action = a->action; p.pi = a->pi; p.latent = a->latent; p.latent_len = a->latent_len; p.sel_steps = a->sel_steps; p.lockstep_levels = a->lockstep_levels;
+  p.pow_table = a->pow_table;
+  return p;
+}
+
 static int search_common(mzh_engine* eng, const mzh_search_args* a, mzh_stream stream, bool replay) {
   if (!eng || !a) return fail(MZH_ERR_ARG, "engine or args NULL");
   if (a->B < 0 || a->n_sims < 0) return fail(MZH_ERR_ARG, "B=%d n_sims=%d", a->B, a->n_sims);
@@ -501,16 +567,7 @@ static int search_common(mzh_engine* eng, const mzh_search_args* a, mzh_stream s
   if (a->plan_out) plan_info(pl, a->B, a->n_sims, a->plan_out);
   DeviceGuard g(eng->device);
   if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
-  MzhSearchParams p{};
-  p.B = a->B; p.S = a->n_sims; p.E = eng->E; p.in_dim = eng->in_dim; p.kin = eng->kin;
-  p.deterministic = a->deterministic; p.np1 = (a->flags & MZH_FLAG_NP1_UCB) ? 1 : 0;
-  p.discount = a->discount; p.eps = a->eps; p.temperature = a->temperature;
-  p.obs = a->obs; p.noise = a->noise; p.tie_idx = a->tie_idx; p.action_u = a->action_u; p.minmax_in = a->minmax_in;
-  p.rp_root_pi = a->rp_root_pi; p.rp_sim = a->rp_sim;
-  p.tree = eng->tree; p.htree = eng->htree; p.pathx = eng->pathx; p.table = eng->table;
-  p.visits = a->visits; p.root_q = a->root_q; p.minmax_out = a->minmax_out; p.extra_ties = a->extra_ties;
-  p.action = a->action; p.pi = a->pi; p.latent = a->latent; p.latent_len = a->latent_len; p.sel_steps = a->sel_steps; p.lockstep_levels = a->lockstep_levels;
-  p.pow_table = a->pow_table;
+  const MzhSearchParams p = search_params(eng, a);
   hipError_t e = pl.one ? mzh_launch_one(pl, eng->net, eng->onet, p, (hipStream_t)stream)
                  : pl.wave ? mzh_launch_wave_search(pl, eng->wnet, p, (hipStream_t)stream)
                            : mzh_launch_search(pl, eng->net, p, (hipStream_t)stream);
@@ -523,6 +580,68 @@ extern "C" int mzh_search(mzh_engine* eng, const mzh_search_args* args, mzh_stre
 
 extern "C" int mzh_search_replay(mzh_engine* eng, const mzh_search_args* args, mzh_stream stream) {
   return search_common(eng, args, stream, true);
+}
+
+// Search over the loaded network set: root b under network net_index[b].  Cooperative kernel only (16- or
+// 32-root tiles of one network each); every refusal below returns before anything is launched.
+extern "C" int mzh_search_multi(mzh_engine* eng, const mzh_search_args* a, const mzh_multi_args* m, mzh_stream stream) {
+  if (!eng || !a || !m) return fail(MZH_ERR_ARG, "engine or args NULL");
+  if (eng->set_m == 0) return fail(MZH_ERR_STATE, "no weight set loaded (mzh_load_weight_set)");
+  if (m->n_networks < 1 || m->n_networks > eng->set_m)
+    return fail(MZH_ERR_ARG, "n_networks=%d outside [1, %d], the loaded set", m->n_networks, eng->set_m);
+  if (!m->net_index) return fail(MZH_ERR_ARG, "net_index is NULL");
+  if (a->rp_sim || a->rp_root_pi) return fail(MZH_ERR_ARG, "a multi-network search has no replay (tree-only) form");
+  if (a->flags & (MZH_FLAG_KERNEL_WAVE | MZH_FLAG_KERNEL_WAVE16 | MZH_FLAG_KERNEL_ONE | MZH_FLAG_COOP_OCC2))
+    return fail(MZH_ERR_ARG, "a multi-network search runs the cooperative kernel only (flags=0x%x)", a->flags);
+  if (a->B < 0 || a->n_sims < 0) return fail(MZH_ERR_ARG, "B=%d n_sims=%d", a->B, a->n_sims);
+  if (a->B > eng->max_roots) return fail(MZH_ERR_CAPACITY, "B=%d > max_roots=%d", a->B, eng->max_roots);
+  if (a->n_sims > eng->max_sims) return fail(MZH_ERR_CAPACITY, "n_sims=%d > max_sims=%d", a->n_sims, eng->max_sims);
+  if (!(a->temperature >= 0.0 && a->temperature <= 1.0))
+    return fail(MZH_ERR_TEMPERATURE, "Expect `temperature` to be in the range [0.0, 1.0], got %g", a->temperature);
+  if (a->B == 0) {
+    if (a->plan_out) {
+      memset(a->plan_out, 0, sizeof(*a->plan_out));
+      snprintf(a->plan_out->kernel, sizeof(a->plan_out->kernel), "none");
+    }
+    return MZH_OK;
+  }
+  if (!a->visits) return fail(MZH_ERR_ARG, "visits output is required");
+  if (!a->obs) return fail(MZH_ERR_ARG, "obs is required");
+  if (!a->deterministic && !a->action_u && a->action)
+    return fail(MZH_ERR_ARG, "stochastic action selection needs action_u");
+  const int S = a->n_sims;
+  MzhSearchPlan pl{};
+  pl.R = pick_tile(a->B, a->flags);
+  if (mzh_search_smem_bytes(pl.R, S, false) > kMaxLds) pl.R = 16;
+  if (mzh_search_smem_bytes(pl.R, S, false) > kMaxLds)
+    return fail(MZH_ERR_CAPACITY, "n_sims=%d exceeds the LDS path budget", S);
+  pl.ohl = mzh_search_smem_bytes(pl.R, S, true) <= kMaxLds;
+  pl.sup33 = eng->support == 33;
+  pl.mmin = 1;
+  if (a->plan_out) {
+    const char* tf[2] = {"false", "true"};
+    mzh_search_plan* o = a->plan_out;
+    memset(o, 0, sizeof(*o));
+    o->roots_per_wave = pl.R / 4;
+    o->threads_per_workgroup = MZH_THREADS;
+    o->roots_per_workgroup = pl.R;
+    o->smem_bytes = (int64_t)mzh_search_smem_bytes(pl.R, S, pl.ohl);
+    o->workgroups = mzh_multi_max_tiles(a->B, pl.R, m->n_networks);
+    snprintf(o->kernel, sizeof(o->kernel), "mzh_search_multi_kernel<%d, %s, %s>", pl.R, tf[pl.ohl], tf[pl.sup33]);
+  }
+  DeviceGuard g(eng->device);
+  if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+  const MzhSearchParams p = search_params(eng, a);
+  MzhMultiParams mp{};
+  mp.net_index = m->net_index;
+  mp.M = m->n_networks;
+  mp.tiles = eng->mtiles;
+  mp.ntiles = eng->mntiles;
+  mp.status = m->status;
+  mp.stride = eng->set_stride;
+  mp.scal = eng->set_scal;
+  hipError_t e = mzh_launch_search_multi(pl, eng->setnet, p, mp, (hipStream_t)stream);
+  return e == hipSuccess ? MZH_OK : hip_fail(e, "multi search launch");
 }
 
 // ---------------------------------------------------------------------------------------------

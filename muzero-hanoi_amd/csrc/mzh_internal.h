@@ -160,6 +160,28 @@ struct MzhSearchPlan {
   int grid;    // one: workgroups (each loops over roots b, b + grid, ...)
 };
 
+// Search over a set of networks (mzh_search_multi; the kernels are in mzh_search.hip).  A set is M packed
+// blobs of one layout (mzh_pack_network_set) at `stride` bytes in one allocation; a tile is up to R
+// consecutive roots of one network, the unit one workgroup of mzh_search_multi_kernel searches.
+#define MZH_MULTI_MAX_NETS 256
+struct MzhTile {
+  int32_t root0, n, net, pad;
+};
+struct MzhMultiParams {
+  const int32_t* net_index;  // [B] caller's, read only by mzh_multi_tiles_kernel
+  int M;                     // networks this call may index
+  MzhTile* tiles;            // [mzh_multi_max_tiles(max_roots, 16, MZH_MULTI_MAX_NETS)] engine workspace
+  int32_t* ntiles;           // [1] engine workspace: tiles of this call (0: net_index refused)
+  int32_t* status;           // [2] caller's (nullable)
+  size_t stride;             // bytes between two networks' blobs
+  const float* scal;         // [M][2] {rwd32b, val32b} of each network (MzhNet carries them by value)
+};
+// upper bound of the tiles B roots of M networks make at R roots per tile: every network with roots has at
+// most one ragged tile, sum ceil(c_m / R) <= floor((B - K) / R) + K <= ceil(B / R) + K - 1 for K >= 1 of them
+static inline int mzh_multi_max_tiles(int B, int R, int M) { return (B + R - 1) / R + (M < B ? M : B) - 1; }
+hipError_t mzh_launch_search_multi(const MzhSearchPlan& pl, const MzhNet& net, const MzhSearchParams& p,
+                                   const MzhMultiParams& mp, hipStream_t stream);
+
 size_t mzh_one_smem_bytes(int S, bool latl);
 hipError_t mzh_launch_one(const MzhSearchPlan& pl, const MzhNet& net, const MzhOneNet& on, const MzhSearchParams& p,
                           hipStream_t stream);

@@ -225,3 +225,25 @@ MzhPacked mzh_pack_network(const MzhCanon& c) {
   P.one = pack_one(buf, c);
   return P;
 }
+
+MzhPackedSet mzh_pack_network_set(const float* flat, int M, int in_dim, int support) {
+  MzhPackedSet S;
+  S.M = M;
+  const size_t n = mzh_canon_view(nullptr, in_dim, support).total;
+  for (int m = 0; m < M; ++m) {
+    MzhPacked P = mzh_pack_network(mzh_canon_view(flat + (size_t)m * n, in_dim, support));
+    if (m == 0) {
+      S.stride = (P.blob.size() + 63) & ~(size_t)63;
+      S.scal = (size_t)M * S.stride;
+      S.blob.assign(S.scal + 2 * (size_t)M, 0.0f);
+    }
+    for (size_t i = 0; i < P.blob.size(); ++i) S.blob[(size_t)m * S.stride + i] = P.blob[i];
+    S.blob[S.scal + 2 * m] = P.W[2].b32;
+    S.blob[S.scal + 2 * m + 1] = P.W[4].b32;
+    if (m == 0) {
+      P.blob.clear();
+      S.layout = P;
+    }
+  }
+  return S;
+}

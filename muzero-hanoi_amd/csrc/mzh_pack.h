@@ -48,6 +48,20 @@ struct MzhPacked {
 };
 MzhPacked mzh_pack_network(const MzhCanon& c);
 
+// A set of M networks of one shape (mzh_load_weight_set): each canonical vector packed by mzh_pack_network,
+// unchanged, and the M blobs laid at a constant stride -- one blob rounded up to 256 bytes -- in one buffer.
+// The offsets depend only on in_dim and support, so `layout` (network 0's, its blob moved into `blob`)
+// describes every member.  The two scalars MzhNet carries by value follow the blobs as [M][2] floats.
+struct MzhPackedSet {
+  std::vector<float> blob;  // [M] blobs at `stride` floats (zero between them), then scal [M][2]
+  size_t stride = 0;        // floats between two networks' blobs (a multiple of 64: 256 bytes)
+  size_t scal = 0;          // float offset of [M][2] {W[2].b32 (reward bin 32 bias), W[4].b32 (value)}
+  int M = 0;
+  MzhPacked layout;         // offsets of one member; layout.blob is empty
+};
+// flat: [M][n] canonical vectors, n = mzh_canon_view(nullptr, in_dim, support).total
+MzhPackedSet mzh_pack_network_set(const float* flat, int M, int in_dim, int support);
+
 // the latency layout's LDS image `l2`: offsets in float4 units
 #define MZH_ONE_D2 0                        // dynamic_net.2 [64 k4][64 lanes]
 #define MZH_ONE_A2 (64 * 64)                // rwd_net.2 bins 0-31 (lanes 0-31) | value_net.2 bins 0-31 (lanes 32-63)

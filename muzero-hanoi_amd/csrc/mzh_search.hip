@@ -34,8 +34,17 @@ constexpr int search_dc() { return R == 32 ? 16 : 32; }  // LDS-cached path dept
 // subnormal: the selection then checks for that (MzhTree::select)
 // C8: the two-workgroups-per-CU form (mzh_search_occ2_kernel): 16-root tile, <= 256 registers, the MLP
 // on 8-fragment weight chunks (mzh_mlp_recurrent_c8), DC = 16 cached path depths, no one-hot in LDS
-template <int R, int DC, bool C8, bool REPLAY, bool OHL, bool SUP33, bool MMIN>
-__device__ __forceinline__ void mzh_search_body(const MzhNet& net, const MzhSearchParams& p) {
+// TILE: where the workgroup's roots [root0, root0 + nvalid), nvalid <= R, come from -- MzhGridTile (workgroup b
+// owns the R roots from b * R: the single-network kernels) or a tile table entry (mzh_search_multi_kernel)
+struct MzhGridTile {
+  template <int R>
+  __device__ __forceinline__ int root0() const { return blockIdx.x * R; }
+  template <int R>
+  __device__ __forceinline__ int nvalid(int B, int root0) const { return min(R, B - root0); }
+};
+
+template <int R, int DC, bool C8, bool REPLAY, bool OHL, bool SUP33, bool MMIN, class TILE = MzhGridTile>
+__device__ __forceinline__ void mzh_search_body(const MzhNet& net, const MzhSearchParams& p, const TILE tile = TILE{}) {
   static_assert(!C8 || (R == 16 && !OHL), "the 8-fragment MLP is the 16-root tile's");
   constexpr int NF = C8 ? 8 : 16;  // fragments per weight buffer
   using Smem = SearchSmem<R, DC>;
@@ -56,8 +65,8 @@ __device__ __forceinline__ void mzh_search_body(const MzhNet& net, const MzhSear
   float* ohl = reinterpret_cast<float*>(path + ((R * (p.S + 1) + 7) & ~7));
 
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int root0 = blockIdx.x * R;
-  const int nvalid = min(R, p.B - root0);
+  const int root0 = tile.template root0<R>();
+  const int nvalid = tile.template nvalid<R>(p.B, root0);
   const int S = p.S;
   const int PL = S + 1;  // path row length
   const double disc = p.discount;
@@ -232,6 +241,128 @@ __global__ __launch_bounds__(MZH_THREADS, 2) void mzh_search_occ2_kernel(MzhNet 
 }
 
 // ------------------------------------------------------------------------------------------
+// Search over a set of networks (mzh_search_multi): root b is searched under network net_index[b].  The
+// roots of one network are consecutive, so a one-workgroup prologue cuts the batch into tiles of up to R
+// roots of one network each (MzhTile), and the search kernel's workgroup t reads tile t: which blob of the
+// set it streams its weights from is decided once, before its first barrier.
+// ------------------------------------------------------------------------------------------
+// the int32 form of the wave scan of mzh_replay.hip / mzh_ingest.hip: row_shr 1, 2, 4, 8 within rows of 16,
+// then row_bcast 15 / 31 (inclusive sums over the wave's 64 lanes; every lane active)
+template <int CTRL, int ROWS>
+__device__ __forceinline__ int mzh_dpp_i32(int v) {
+  if (ROWS == 0xF) return __builtin_amdgcn_mov_dpp(v, CTRL, ROWS, 0xF, true);
+  return __builtin_amdgcn_update_dpp(0, v, CTRL, ROWS, 0xF, false);
+}
+__device__ __forceinline__ int mzh_wave_scan_i32(int v) {
+  v += mzh_dpp_i32<0x111, 0xF>(v);
+  v += mzh_dpp_i32<0x112, 0xF>(v);
+  v += mzh_dpp_i32<0x114, 0xF>(v);
+  v += mzh_dpp_i32<0x118, 0xF>(v);
+  v += mzh_dpp_i32<0x142, 0xA>(v);
+  v += mzh_dpp_i32<0x143, 0xC>(v);
+  return v;
+}
+
+// One workgroup: check net_index [B] (each entry in [0, M), non-decreasing), find every network's segment,
+// give network m ceil(count_m / R) tiles in network order and write them with their count.  A refused
+// net_index leaves tile count 0 (the search kernel's workgroups all return) and status[0] = 1.  An entry
+// indexes LDS only after it passed the range and order checks, and nothing else ever uses it: the search
+// kernel takes the network from the table.
+__global__ __launch_bounds__(MZH_MULTI_MAX_NETS) void mzh_multi_tiles_kernel(MzhMultiParams mp, int B, int R) {
+  constexpr int T = MZH_MULTI_MAX_NETS;
+  __shared__ int start[T + 1];  // start[m]: first root of network m (B where it has none left); start[M] = B
+  __shared__ int toff[T + 1];   // toff[m]: first tile of network m; toff[M] = tiles
+  __shared__ int wtot[T / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int M = mp.M;
+  // boundary i (0 <= i <= B) lies between entries i - 1 and i, with -1 before the first and M after the last:
+  // networks prev + 1 .. v start at root i
+  int bad = 0;
+  for (int i = tid; i <= B; i += T) {
+    const int prev = i > 0 ? mp.net_index[i - 1] : -1;
+    const int v = i < B ? mp.net_index[i] : M;
+    if (prev >= (i > 0 ? 0 : -1) && prev <= v && v < M + (i == B ? 1 : 0)) {
+      for (int m = prev + 1; m <= v; ++m) start[m] = i;  // m in [0, M]
+    } else {
+      bad = 1;
+    }
+  }
+  bad = __syncthreads_or(bad);
+  if (bad) {  // start[] is incomplete: nothing below reads it
+    if (tid == 0) {
+      *mp.ntiles = 0;
+      if (mp.status) {
+        mp.status[0] = 1;
+        mp.status[1] = 0;
+      }
+    }
+    return;
+  }
+  const int nt = tid < M ? (start[tid + 1] - start[tid] + R - 1) / R : 0;
+  const int inc = mzh_wave_scan_i32(nt);
+  if (lane == 63) wtot[wave] = inc;
+  __syncthreads();
+  int pre = 0;
+  for (int w = 0; w < wave; ++w) pre += wtot[w];
+  toff[tid] = pre + inc - nt;  // exclusive
+  if (tid == T - 1) toff[T] = pre + inc;
+  __syncthreads();
+  // at most ceil(B / R) + min(M, B) - 1 tiles (the launcher's grid and the table's capacity)
+  for (int m = 0; m < M; ++m) {
+    const int s0 = start[m], cnt = start[m + 1] - s0, t0 = toff[m];
+    for (int k = tid; k * R < cnt; k += T) mp.tiles[t0 + k] = MzhTile{s0 + k * R, min(R, cnt - k * R), m, 0};
+  }
+  if (tid == 0) {
+    *mp.ntiles = toff[T];
+    if (mp.status) {
+      mp.status[0] = 0;
+      mp.status[1] = toff[T];
+    }
+  }
+}
+
+// the set's network `net` from the template MzhNet of network 0: every blob of a set has the same layout, at
+// a constant byte stride, so each pointer moves by net * stride (the layers' woff / boff are relative to wbase
+// and stay); the two bin-32 biases MzhNet carries by value come from the set's [M][2] array
+__device__ __forceinline__ void mzh_net_select(MzhNet& n, const MzhMultiParams& mp, int net, bool sup33) {
+  const size_t off = (size_t)net * mp.stride;
+  auto mv = [off](auto*& q) { q = reinterpret_cast<std::remove_reference_t<decltype(q)>>(reinterpret_cast<const char*>(q) + off); };
+  auto layer = [&](MzhLayer& l) {
+    mv(l.w);
+    mv(l.b);
+  };
+  layer(n.rep0); layer(n.rep2); layer(n.dyn0); layer(n.dyn2); layer(n.rwd0); layer(n.rwd2);
+  layer(n.pol0); layer(n.pol2); layer(n.val0); layer(n.val2);
+  mv(n.wbase);
+  mv(n.dyn0_onehot);
+  if (sup33) {  // null without a 33-bin head
+    mv(n.rwd32);
+    mv(n.val32);
+    n.rwd32b = mp.scal[2 * net];
+    n.val32b = mp.scal[2 * net + 1];
+  }
+}
+
+struct MzhTableTile {
+  MzhTile t;
+  template <int R>
+  __device__ __forceinline__ int root0() const { return t.root0; }
+  template <int R>
+  __device__ __forceinline__ int nvalid(int, int) const { return t.n; }
+};
+
+// MMIN = true always: it only adds the subnormal max - min check, and is bit-identical with fresh bounds.
+// A workgroup at or above the tile count (the grid is the upper bound ceil(B / R) + min(M, B) - 1) returns
+// before its first barrier.  blockIdx.x is the tile index (p.lockstep_levels is indexed by tile).
+template <int R, bool OHL, bool SUP33>
+__global__ __launch_bounds__(MZH_THREADS, 1) void mzh_search_multi_kernel(MzhNet net, MzhSearchParams p, MzhMultiParams mp) {
+  if ((int)blockIdx.x >= *mp.ntiles) return;
+  const MzhTableTile t{mp.tiles[blockIdx.x]};
+  mzh_net_select(net, mp, t.t.net, SUP33);
+  mzh_search_body<R, search_dc<R>(), false, false, OHL, SUP33, true>(net, p, t);
+}
+
+// ------------------------------------------------------------------------------------------
 // standalone batched inference kernels (MuZeroNet.initial_inference / recurrent_inference)
 // ------------------------------------------------------------------------------------------
 template <int R>
@@ -335,6 +466,33 @@ hipError_t mzh_launch_search(const MzhSearchPlan& pl, const MzhNet& net, const M
   if (pl.replay) return launch_search_t<16, true, false>(pl, net, p, stream);
   if (pl.ohl) return launch_search_t<16, false, true>(pl, net, p, stream);
   return launch_search_t<16, false, false>(pl, net, p, stream);
+}
+
+template <int R, bool OHL, bool SUP33>
+static hipError_t launch_multi_t(int grid, const MzhNet& net, const MzhSearchParams& p, const MzhMultiParams& mp,
+                                 hipStream_t stream) {
+  const size_t smem = search_smem_bytes<R>(p.S, OHL);
+  const void* fn = reinterpret_cast<const void*>(&mzh_search_multi_kernel<R, OHL, SUP33>);
+  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(mzh_multi_tiles_kernel, dim3(1), dim3(MZH_MULTI_MAX_NETS), 0, stream, mp, p.B, R);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((mzh_search_multi_kernel<R, OHL, SUP33>), dim3(grid), dim3(MZH_THREADS), smem, stream, net, p, mp);
+  return hipGetLastError();
+}
+
+// the tile table of the batch, then mzh_search_multi_kernel<pl.R, pl.ohl, pl.sup33> on the table's upper bound
+// of workgroups; net is the set's network 0
+hipError_t mzh_launch_search_multi(const MzhSearchPlan& pl, const MzhNet& net, const MzhSearchParams& p,
+                                   const MzhMultiParams& mp, hipStream_t stream) {
+  const int grid = mzh_multi_max_tiles(p.B, pl.R, mp.M);
+  if (pl.R == 32) {
+    if (pl.ohl) return pl.sup33 ? launch_multi_t<32, true, true>(grid, net, p, mp, stream) : launch_multi_t<32, true, false>(grid, net, p, mp, stream);
+    return pl.sup33 ? launch_multi_t<32, false, true>(grid, net, p, mp, stream) : launch_multi_t<32, false, false>(grid, net, p, mp, stream);
+  }
+  if (pl.ohl) return pl.sup33 ? launch_multi_t<16, true, true>(grid, net, p, mp, stream) : launch_multi_t<16, true, false>(grid, net, p, mp, stream);
+  return pl.sup33 ? launch_multi_t<16, false, true>(grid, net, p, mp, stream) : launch_multi_t<16, false, false>(grid, net, p, mp, stream);
 }
 
 template <int R>

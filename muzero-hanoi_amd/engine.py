@@ -81,6 +81,21 @@ class Engine:
               "mzh_load_weights")
         self.weights_loaded = True
 
+    def load_weight_set(self, flats):
+        """a set of networks for search_multi (mzh_load_weight_set): a sequence of canonical flat vectors of this
+        engine's shape.  The engine's own network (load_weights) is a separate allocation and stays as it is."""
+        n = ctypes.c_size_t()
+        check(_lib.lib().mzh_weights_size(self.n_disks, self.support, ctypes.byref(n)), "mzh_weights_size")
+        flats = [np.ascontiguousarray(f, np.float32).reshape(-1) for f in flats]
+        if not flats or any(f.size != n.value for f in flats):
+            raise ValueError(f"expected a non-empty sequence of vectors of {n.value} weights, got sizes "
+                             f"{[f.size for f in flats]}")
+        flat = np.ascontiguousarray(np.stack(flats))
+        torch.cuda.synchronize(self.device)
+        check(_lib.lib().mzh_load_weight_set(self._h, flat.ctypes.data_as(ctypes.c_void_p), n.value, len(flats)),
+              "mzh_load_weight_set")
+        self.set_size = len(flats)
+
     # ---------------------------------------------------------------- inference
     def _f32(self, *shape):
         return torch.empty(shape, dtype=torch.float32, device=self.device)
@@ -150,6 +165,44 @@ class Engine:
         kernel = None (automatic by batch size) | "coop" | "occ2" | "wave" | "wave16" | "one" (all give identical
         results; "one" = the latency kernel, MLP searches only);
         tile = None | 16 | 32: the cooperative kernel's roots per workgroup (default by batch size)."""
+        a, out = self._search_args(n_sims, obs=obs, replay=replay, tie_idx=tie_idx, noise=noise, action_u=action_u,
+                                   minmax_in=minmax_in, temperature=temperature, deterministic=deterministic,
+                                   discount=discount, eps=eps, out=out, flags=search_flags(kernel, tile, np1_ucb))
+        fn = _lib.lib().mzh_search_replay if replay is not None else _lib.lib().mzh_search
+        check(fn(self._h, ctypes.byref(a), self._stream()), "mzh_search")
+        out["_plan"] = out.pop("_plan_struct").as_dict()  # the instantiation the library launched
+        return out
+
+    def search_multi(self, n_sims, *, net_index, obs, tie_idx, noise=None, action_u=None, minmax_in=None,
+                     temperature=1.0, deterministic=False, discount=0.8, eps=0.25, np1_ucb=False, out=None, tile=None):
+        """Batched search over the loaded weight set (load_weight_set): root b under network net_index[b], the
+        roots of one network consecutive (net_index [B] non-decreasing, each in [0, set size)).  The other
+        arguments and the result are search's; only the cooperative kernel has this form (tile = None | 16 | 32).
+        out["_status"] is the device's [2] int32 verdict: [0] = 1 where it refused net_index (nothing was
+        searched, no output written), [1] the tiles searched."""
+        if getattr(self, "set_size", 0) < 1:
+            raise RuntimeError("search_multi: no weight set loaded (load_weight_set)")
+        a, out = self._search_args(n_sims, obs=obs, replay=None, tie_idx=tie_idx, noise=noise, action_u=action_u,
+                                   minmax_in=minmax_in, temperature=temperature, deterministic=deterministic,
+                                   discount=discount, eps=eps, out=out, flags=search_flags(None, tile, np1_ucb))
+        ni = net_index.to(self.device, torch.int32).contiguous()
+        if ni.dim() != 1 or ni.shape[0] != a.B:
+            raise ValueError(f"search_multi: net_index must have one entry per root ({a.B}), got {tuple(ni.shape)}")
+        status = torch.zeros(2, dtype=torch.int32, device=self.device)
+        out["_keep"].append(ni)
+        m = _lib.MultiArgs()
+        m.n_networks = self.set_size
+        m.net_index = ptr(ni)
+        m.status = ptr(status)
+        check(_lib.lib().mzh_search_multi(self._h, ctypes.byref(a), ctypes.byref(m), self._stream()), "mzh_search_multi")
+        out["_plan"] = out.pop("_plan_struct").as_dict()
+        out["_status"] = status
+        return out
+
+    def _search_args(self, n_sims, *, obs, replay, tie_idx, noise, action_u, minmax_in, temperature, deterministic,
+                     discount, eps, out, flags):
+        """the mzh_search_args of a search / search_multi call and its result dict (outputs allocated unless given;
+        "_keep": the inputs, alive until the caller is done with the asynchronous call)"""
         B = int(tie_idx.shape[0])
         if out is None:
             out = self.alloc_search_outputs(B, n_sims)
@@ -169,7 +222,7 @@ class Engine:
         a.eps = float(eps)
         a.temperature = float(temperature)
         a.deterministic = 1 if deterministic else 0
-        a.flags = search_flags(kernel, tile, np1_ucb)
+        a.flags = flags
         a.obs = ptr(dev(obs, torch.float32))
         a.noise = ptr(dev(noise, torch.float64))
         a.tie_idx = ptr(dev(tie_idx, torch.int32))
@@ -188,11 +241,9 @@ class Engine:
         a.lockstep_levels = ptr(out.get("lockstep_levels"))
         plan = _lib.SearchPlan()
         a.plan_out = ctypes.pointer(plan)
-        fn = _lib.lib().mzh_search_replay if replay is not None else _lib.lib().mzh_search
-        check(fn(self._h, ctypes.byref(a), self._stream()), "mzh_search")
-        out["_keep"] = keep  # inputs stay alive until the caller is done with the async call
-        out["_plan"] = plan.as_dict()  # the instantiation the library launched
-        return out
+        out["_keep"] = keep
+        out["_plan_struct"] = plan
+        return a, out
 
 
 def search_flags(kernel=None, tile=None, np1_ucb=False):

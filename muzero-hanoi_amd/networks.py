@@ -199,3 +199,64 @@ def engine_for(net, max_sims, max_roots, device=None):
         eng.load_weights(_engine.flat_weights(net.state_dict()))
         cache["sig"] = sig
     return eng
+
+
+def _check_shape(net):
+    """(in_dim, support) of a module with MuZeroNet's state_dict keys and the shape libmzh supports"""
+    sd_keys = set(net.state_dict().keys())
+    missing = [k for k in _engine.WEIGHT_KEYS if k not in sd_keys]
+    if missing:
+        raise TypeError(f"network lacks MuZeroNet parameters {missing}")
+    in_dim = net.representation_net[0].in_features
+    support = net.value_net[2].out_features
+    if (in_dim % 3 or net.representation_net[2].out_features != 64 or net.representation_net[0].out_features != 256
+            or net.policy_net[2].out_features != 6 or support not in (1, 33)):
+        raise NotImplementedError("libmzh supports the Hanoi MuZeroNet shape (3N -> 256 -> 64, 6 actions, "
+                                  "support 33 or 1)")
+    return in_dim, support
+
+
+class NetworkSet:
+    """Networks of one shape searched together (Engine.search_multi, selfplay.evaluate_networks): the variants
+    of an ablation sweep (checkpoint.ablation_variants), checkpoints of one run, seeds.  Root b of a search is
+    searched under nets[net_index[b]]."""
+
+    def __init__(self, nets):
+        nets = list(nets)
+        if not nets:
+            raise TypeError("NetworkSet: no networks")
+        if not all(isinstance(n, nn.Module) for n in nets):
+            raise TypeError("NetworkSet: every member must be a torch module with MuZeroNet's state_dict keys")
+        shapes = [_check_shape(n) for n in nets]
+        if len(set(shapes)) != 1:
+            raise TypeError(f"NetworkSet: members differ in (3 * n_disks, support): {shapes}")
+        self.nets = nets
+        self.in_dim, self.support = shapes[0]
+
+    def __len__(self):
+        return len(self.nets)
+
+    def __getitem__(self, i):
+        return self.nets[i]
+
+
+def engine_for_set(nset, max_sims, max_roots, device=None):
+    """engine_for for a NetworkSet: the libmzh engine bound to the set with capacity >= (max_sims, max_roots) and
+    every member's CURRENT weights loaded as its weight set; reloaded when any member's parameter storage or
+    version counter changed (the signature scheme of engine_for)."""
+    cache = nset.__dict__.setdefault("_cache", {})
+    eng = cache.get("engine")
+    if eng is None or eng.max_sims < max_sims or eng.max_roots < max_roots:
+        if eng is not None:
+            eng.close()
+        eng = _engine.Engine(nset.in_dim // 3, max(max_sims, 64 if eng is None else eng.max_sims),
+                             max(max_roots, 1 if eng is None else eng.max_roots), nset.support, device=device)
+        cache["engine"] = eng
+        cache["sig"] = None
+    if "refs" not in cache:
+        cache["refs"] = [_param_refs(n) for n in nset.nets]
+    sig = tuple(_fast_signature(r) for r in cache["refs"])
+    if cache.get("sig") != sig:
+        eng.load_weight_set([_engine.flat_weights(n.state_dict()) for n in nset.nets])
+        cache["sig"] = sig
+    return eng

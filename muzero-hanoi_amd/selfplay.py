@@ -15,6 +15,8 @@ episode_records    the reference's per-episode bookkeeping (returns, priorities,
                    organise_transitions) of every env of a BatchedSelfPlay run.
 ingest_records     that bookkeeping, the success filter and Buffer.add for every env in one device call
                    (Buffer.add_episodes, csrc/mzh_ingest.hip): the same ring, priorities and RNG stream.
+evaluate_networks  evaluate's batched schedule for a set of networks (an ablation sweep's variants): one batch
+                   of len(networks) x episodes envs per budget, one mzh_search_multi launch per move.
 evaluate           acting_ablations.get_results (acting_experiments/acting_ablations.py:72-128)
                    and illegal_move_rate (illegal_move_rate_comparison.py:27-50) over episodes:
                    error = steps - hanoi_solver(start), per-episode illegal-move rates (mean and
@@ -37,7 +39,7 @@ from .engine import env_step as _env_step
 from .engine import hanoi_solver_batch
 from .env import HanoiBatch
 from .mcts import RecordedNetwork, _replay_engine
-from .networks import engine_for
+from .networks import NetworkSet, engine_for, engine_for_set
 from .utils import adjust_temperature, compute_MCreturns, compute_n_step_returns, organise_transitions
 
 # acting_experiments/acting_ablations.py:49-68: the named 3-disk starts (distance to goal 7 / 3 / 1)
@@ -109,7 +111,11 @@ def _bookkeeping(episode_state, episode_rwd, episode_action, episode_piProb, epi
 
 
 class BatchedSelfPlay:
-    """B independent agents in lockstep on one GPU, one MCTS instance (MinMaxStats) each."""
+    """B independent agents in lockstep on one GPU, one MCTS instance (MinMaxStats) each.
+
+    network: one network for every agent, or a networks.NetworkSet -- then play / play_plans take net_index
+    [B] (non-decreasing: the agents of one network are consecutive) and agent b searches under
+    network[net_index[b]], all of them in one mzh_search_multi launch per move."""
 
     def __init__(self, network, n_disks, max_steps, n_simulations, *, discount=0.8, dirichlet_alpha=0.25,
                  root_exploration_eps=0.25, goal_peg=2, np1_ucb=False):
@@ -118,7 +124,7 @@ class BatchedSelfPlay:
         self.discount, self.alpha, self.eps, self.goal_peg = discount, dirichlet_alpha, root_exploration_eps, goal_peg
         self.np1_ucb = np1_ucb
 
-    def _setup(self, start_idx, minmax, seed):
+    def _setup(self, start_idx, minmax, seed, net_index=None):
         """-> start [B] int64, the engine, whether it replays a RecordedNetwork, the envs reset to the starts and
         their observations, the generator of the synthetic draws' seeds, and the agents' MinMaxStats [B, 2] (default: fresh)"""
         start = torch.as_tensor(np.asarray(start_idx), dtype=torch.int64).reshape(-1)
@@ -126,7 +132,18 @@ class BatchedSelfPlay:
         replay = isinstance(self.network, RecordedNetwork)
         if replay and B != 1:
             raise ValueError("a RecordedNetwork replays one sequential stream of searches: B must be 1")
-        eng = _replay_engine(self.N, self.S) if replay else engine_for(self.network, self.S, B)
+        multi = isinstance(self.network, NetworkSet)
+        if multi != (net_index is not None):
+            raise ValueError("net_index [B] is required with a NetworkSet and only accepted with one")
+        if multi:
+            ni = np.asarray(net_index, np.int64).reshape(-1)
+            if ni.shape[0] != B or (B and (ni.min() < 0 or ni.max() >= len(self.network) or np.any(np.diff(ni) < 0))):
+                raise ValueError(f"net_index must be {B} non-decreasing indices into the set of {len(self.network)}")
+            eng = engine_for_set(self.network, self.S, B)
+            self._net_index = torch.as_tensor(ni, dtype=torch.int32).to(eng.device)
+        else:
+            eng = _replay_engine(self.N, self.S) if replay else engine_for(self.network, self.S, B)
+            self._net_index = None
         dev = eng.device
         env = HanoiBatch(self.N, self.max_steps, B, goal_peg=self.goal_peg, device=dev)
         obs = env.reset(start.to(dev))
@@ -148,23 +165,27 @@ class BatchedSelfPlay:
         """one search over the envs `idx` (obs: their observations; or the RecordedNetwork's next call), their
         MinMaxStats read from and carried into mm [B, 2]"""
         noise, tie, u = (None if x is None else torch.as_tensor(x).to(eng.device) for x in draws)
-        out = eng.search(self.S, obs=None if replay else obs,
-                         replay=self.network.next_replay(eng.device) if replay else None, tie_idx=tie, noise=noise,
-                         action_u=u, minmax_in=mm.index_select(0, idx), temperature=float(temperature),
-                         deterministic=bool(deterministic), discount=self.discount, eps=self.eps,
-                         np1_ucb=self.np1_ucb)
+        kw = dict(tie_idx=tie, noise=noise, action_u=u, minmax_in=mm.index_select(0, idx),
+                  temperature=float(temperature), deterministic=bool(deterministic), discount=self.discount,
+                  eps=self.eps, np1_ucb=self.np1_ucb)
+        if self._net_index is not None:  # a NetworkSet: idx is increasing, so the networks' envs stay consecutive
+            out = eng.search_multi(self.S, net_index=self._net_index.index_select(0, idx), obs=obs, **kw)
+        else:
+            out = eng.search(self.S, obs=None if replay else obs,
+                             replay=self.network.next_replay(eng.device) if replay else None, **kw)
         mm.index_copy_(0, idx, out["minmax"])
         return out
 
     def play(self, start_idx, temperature=1.0, deterministic=False, seed=0, legacy_rng=False, minmax=None,
-             record_obs=False):
+             record_obs=False, net_index=None):
         """Play every env from start_idx[b] until done (goal or max_steps).
 
         minmax: [B, 2] (maximum, minimum) of each agent's MinMaxStats at the start (default: fresh,
-        -inf / +inf); the final values come back as res["minmax"].  Returns device tensors:
+        -inf / +inf); the final values come back as res["minmax"].  net_index: [B] with a NetworkSet (the
+        class docstring), else None.  Returns device tensors:
         per step t (rows of envs that were still playing): action, reward, pi, root_q, active,
         obs (record_obs); per env: steps, illegal (count), start_idx, minmax."""
-        start, eng, replay, env, obs, gen, mm = self._setup(start_idx, minmax, seed)
+        start, eng, replay, env, obs, gen, mm = self._setup(start_idx, minmax, seed, net_index)
         B, dev = int(start.shape[0]), eng.device
         active = torch.ones(B, dtype=torch.bool, device=dev)
         steps = torch.zeros(B, dtype=torch.int32, device=dev)
@@ -219,7 +240,7 @@ class BatchedSelfPlay:
         return res
 
     def play_plans(self, start_idx, max_plan_len, temperature=1.0, deterministic=False, seed=0, legacy_rng=False,
-                   minmax=None):
+                   minmax=None, net_index=None):
         """Plan-ahead episodes (acting_experiments/planning_multiple_actions.py:111-183): every env searches
         once and executes the last simulation's selection path (mcts.return_latent_actions()[:max_plan_len])
         open loop, illegal moves included, and searches again only when that plan ran out before the episode
@@ -239,7 +260,7 @@ class BatchedSelfPlay:
             raise ValueError("play_plans: a plan needs n_simulations >= 1")
         if np.asarray(start_idx).size < 1:
             raise ValueError("play_plans: no start states")
-        start, eng, replay, env, _, gen, mm = self._setup(start_idx, minmax, seed)
+        start, eng, replay, env, _, gen, mm = self._setup(start_idx, minmax, seed, net_index)
         B, dev = int(start.shape[0]), eng.device
         plans = torch.zeros(B, dtype=torch.int32, device=dev)
         rec = dict(action=[], reward=[], root_q=[], search_action=[])
@@ -364,7 +385,7 @@ def evaluate(network, n_disks, n_sims_range, *, episodes=1, start=None, start_id
     if not sequential and minmax is not None:
         raise ValueError("evaluate: minmax applies to the sequential schedule only (batched agents start fresh)")
     legacy_rng = sequential if legacy_rng is None else legacy_rng
-    data, illegal, errors_all, steps_all, rates_all = [], [], [], [], []
+    score = _new_score()
     mm = None if minmax is None else np.asarray(minmax, np.float64).reshape(1, 2)
     for n in n_sims_range:
         sp = BatchedSelfPlay(network, n_disks, max_steps, int(n), goal_peg=goal_peg, np1_ucb=np1_ucb,
@@ -387,28 +408,83 @@ def evaluate(network, n_disks, n_sims_range, *, episodes=1, start=None, start_id
                 starts.append(s0)
             steps, ill, starts = np.array(steps), np.array(ill), np.array(starts)
         else:
-            if start_idx is not None:
-                starts = np.asarray(start_idx, np.int64).reshape(-1)
-            elif start is None:
-                g = np.random.default_rng(seed)
-                goal = state_index((goal_peg,) * n_disks)
-                starts = g.integers(0, 3 ** n_disks - 1, size=episodes)
-                starts = starts + (starts >= goal)  # uniform over the non-goal states
-            else:
-                starts = np.full(episodes, _start_index(start, n_disks), np.int64)
+            starts = _batch_starts(n_disks, episodes, start, start_idx, seed, goal_peg)
             res = play(starts, temperature=temperature, deterministic=deterministic, legacy_rng=legacy_rng,
                        seed=seed)
             steps, ill = res["steps"].cpu().numpy(), res["illegal"].cpu().numpy()
-        dev = torch.device("cuda", torch.cuda.current_device())
-        st = torch.tensor([index_state(int(i), n_disks) for i in starts], dtype=torch.uint8, device=dev)
-        opt = hanoi_solver_batch(n_disks, st, goal_peg).cpu().numpy()
-        err = steps - opt
-        rates = ill / np.maximum(steps, 1)
-        data.append([int(n), float(sum(int(e) for e in err) / len(err))])
-        sem = float(np.std(rates, ddof=1) / np.sqrt(len(rates))) if len(rates) > 1 else float("nan")
-        illegal.append([int(n), float(np.mean(rates)), sem])
-        errors_all.append(err)
-        steps_all.append(steps)
-        rates_all.append(rates)
-    return dict(data=data, illegal=illegal, errors=errors_all, steps=steps_all, illegal_rates=rates_all,
-                minmax=mm if sequential else None)
+        _score_budget(score, int(n), n_disks, goal_peg, starts, steps, ill)
+    return dict(**score, minmax=mm if sequential else None)
+
+
+def _new_score():
+    return dict(data=[], illegal=[], errors=[], steps=[], illegal_rates=[])
+
+
+def _score_budget(score, n, n_disks, goal_peg, starts, steps, ill):
+    """one budget's episodes scored into evaluate's result lists: error = steps - hanoi_solver(start)
+    (get_results), per-episode illegal-move rates with mean and standard error (illegal_move_rate)"""
+    dev = torch.device("cuda", torch.cuda.current_device())
+    st = torch.tensor([index_state(int(i), n_disks) for i in starts], dtype=torch.uint8, device=dev)
+    opt = hanoi_solver_batch(n_disks, st, goal_peg).cpu().numpy()
+    err = steps - opt
+    rates = ill / np.maximum(steps, 1)
+    score["data"].append([n, float(sum(int(e) for e in err) / len(err))])
+    sem = float(np.std(rates, ddof=1) / np.sqrt(len(rates))) if len(rates) > 1 else float("nan")
+    score["illegal"].append([n, float(np.mean(rates)), sem])
+    score["errors"].append(err)
+    score["steps"].append(steps)
+    score["illegal_rates"].append(rates)
+
+
+def _batch_starts(n_disks, episodes, start, start_idx, seed, goal_peg):
+    """the start indices of one budget's batch of episodes (evaluate's batched schedule)"""
+    if start_idx is not None:
+        return np.asarray(start_idx, np.int64).reshape(-1)
+    if start is None:
+        g = np.random.default_rng(seed)
+        goal = state_index((goal_peg,) * n_disks)
+        starts = g.integers(0, 3 ** n_disks - 1, size=episodes)
+        return starts + (starts >= goal)  # uniform over the non-goal states
+    return np.full(episodes, _start_index(start, n_disks), np.int64)
+
+
+def evaluate_networks(networks, n_disks, n_sims_range, *, episodes=1, start=None, start_idx=None, max_steps=200,
+                      temperature=1.0, deterministic=False, seed=0, goal_peg=2, np1_ucb=False, max_plan_len=None,
+                      dirichlet_alpha=0.25, max_roots=65536):
+    """evaluate's batched schedule for several networks at once -- the variants of an ablation sweep
+    (checkpoint.ablation_variants; the reference runs acting_ablations.py once per variant): per budget one
+    batch of len(networks) * episodes envs, network m's episodes consecutive and every network given the same
+    starts (start / start_idx / the seed's random starts, as in evaluate), searched by one mzh_search_multi
+    launch per move.  A batch above max_roots envs is played as several.  Every episode is its own agent with
+    a fresh MinMaxStats and its own synthetic draws (the draws of env b of the batch: not those evaluate
+    would give network m's episode alone).
+    networks: a networks.NetworkSet or a sequence of networks.  Returns a list with, per network, the dict
+    evaluate returns (minmax None), scored by the same code."""
+    nset = networks if isinstance(networks, NetworkSet) else NetworkSet(networks)
+    if max_plan_len is not None:
+        if int(max_plan_len) != max_plan_len or int(max_plan_len) < 1:
+            raise ValueError(f"evaluate_networks: max_plan_len must be an integer >= 1, got {max_plan_len}")
+        if any(int(n) < 1 for n in n_sims_range):
+            raise ValueError("evaluate_networks: a plan needs n_simulations >= 1 in every budget")
+    if int(max_roots) < 1:
+        raise ValueError(f"evaluate_networks: max_roots must be >= 1, got {max_roots}")
+    M = len(nset)
+    scores = [_new_score() for _ in range(M)]
+    for n in n_sims_range:
+        sp = BatchedSelfPlay(nset, n_disks, max_steps, int(n), goal_peg=goal_peg, np1_ucb=np1_ucb,
+                             dirichlet_alpha=dirichlet_alpha)
+        play = sp.play if max_plan_len is None else (lambda s, **kw: sp.play_plans(s, int(max_plan_len), **kw))
+        starts = _batch_starts(n_disks, episodes, start, start_idx, seed, goal_peg)
+        E = len(starts)
+        all_starts, net_index = np.tile(starts, M), np.repeat(np.arange(M), E)
+        steps, ill = [], []
+        for k, lo in enumerate(range(0, M * E, int(max_roots))):
+            sl = slice(lo, min(M * E, lo + int(max_roots)))
+            res = play(all_starts[sl], temperature=temperature, deterministic=deterministic, seed=seed + k,
+                       net_index=net_index[sl])
+            steps.append(res["steps"].cpu().numpy())
+            ill.append(res["illegal"].cpu().numpy())
+        steps, ill = np.concatenate(steps), np.concatenate(ill)
+        for m in range(M):
+            _score_budget(scores[m], int(n), n_disks, goal_peg, starts, steps[m * E:(m + 1) * E], ill[m * E:(m + 1) * E])
+    return [dict(**sc, minmax=None) for sc in scores]
