@@ -172,6 +172,56 @@ typedef struct mzh_plan_args {
 
 int mzh_env_run_plan(const mzh_plan_args* args, mzh_stream stream);
 
+/* Acting on a perturbed observation (noise_injection_comparison.py:17-37, permutation_importance.py:27-76):
+ * the agent searches from an observation that differs from the true state, its action is applied to the true
+ * env, and an episode counts as solved when a step returns reward 100.  One launch for n rows of a sub-batch:
+ * row j is env env_index[j] of the full batch of B envs (env j where env_index is NULL; the indices of one
+ * call must be distinct).  Per row, for an env that is active on entry (an inactive one is left untouched,
+ * reward = done = 0, no error: the caller's rows may include finished episodes):
+ *   1. with `action`: one TowersOfHanoi.step (env/hanoi.py:47-84) of the true env, c_state not advanced on the
+ *      goal step and the episode ended at max_steps as in mzh_env_step; steps_total += 1, illegal_total += 1
+ *      on an illegal move, solved = 1 on reward code 1 (`if reward == 100: return True`,
+ *      noise_injection_comparison.py:33-34, permutation_importance.py:71-72);
+ *   2. if the env is still active: obs = the observation the next search reads -- c_state with disc
+ *      perm_disc's peg replaced by perm_peg[j] (permutation_importance.py:55-59), one-hot encoded
+ *      (utils.py:9-25), plus noise[j] where given (noise_injection_comparison.py:25-27), each element
+ *      (float)((double)onehot + noise): the reference's float64 sum, rounded once by
+ *      torch.from_numpy(...).to(float32) (MCTS/mcts.py:49).  An env whose step ended the episode keeps its
+ *      obs row.
+ * action = NULL is an observe-only call (the first observation of an episode, taken before any step:
+ * noise_injection_comparison.py:24-27): nothing is stepped, no tally changes.
+ * Errors add 1 to *err_count and leave the row's env, tallies and obs untouched (reward = done = 0): an env
+ * index outside [0, B); on an active env an action outside 0..5 (moves[action] IndexError), a perm_disc
+ * outside [-1, n_disks), a perm_peg outside 0..2 where the env's perm_disc >= 0.
+ * MZH_ERR_ARG, before any launch: a NULL required pointer (state, step_ctr, active, steps_total,
+ * illegal_total, solved, obs; perm_peg where perm_disc is given), n < 1, B < 1 (B < n without env_index),
+ * n_disks outside [1, 32], goal_peg outside [0, 2]. */
+typedef struct mzh_observe_args {
+  int32_t n_disks, goal_peg, max_steps; /* TowersOfHanoi(N, max_steps), env/hanoi.py:13-45 */
+  int32_t B;                /* envs of the full batch */
+  int32_t n;                /* rows of this call */
+  const int32_t* env_index; /* [n] or NULL */
+  const int32_t* action;    /* [n] index into moves (env/hanoi.py:39-41), or NULL: observe only */
+  uint8_t* state;           /* [B][n_disks] in/out c_state, as in mzh_env_step */
+  int32_t* step_ctr;        /* [B] in/out step_counter (hanoi.py:50-80) */
+  uint8_t* active;          /* [B] in/out reset_check (hanoi.py:49) */
+  int32_t* steps_total;     /* [B] in/out executed steps (the play_game loops' iterations) */
+  int32_t* illegal_total;   /* [B] in/out executed illegal moves (env.step's fourth value, hanoi.py:70-74) */
+  uint8_t* solved;          /* [B] in/out 1 once a step returned reward 100 (hanoi.py:65-69); never cleared */
+  const int32_t* perm_disc; /* [B] or NULL: permute_feature, the disc whose peg the model does not see, -1 =
+                               none; constant over an episode (permutation_importance.py:55-59) */
+  const int32_t* perm_peg;  /* [n] this decision's np.random.randint(0, n_pegs) (permutation_importance.py:58);
+                               read only where the row's env has perm_disc >= 0 */
+  const double* noise;      /* [n][3 n_disks] or NULL: this decision's np.random.normal(0, noise_std, shape),
+                               already scaled by the caller (noise_injection_comparison.py:25-27) */
+  float* obs;               /* [B][3 n_disks] in/out: state_one_hot as run_mcts rounds it (MCTS/mcts.py:49) */
+  int8_t* reward;           /* [n] nullable: this call's step codes as in mzh_env_step (0 without a step) */
+  uint8_t* done;            /* [n] nullable: this call's done flags (hanoi.py:65-80) */
+  int32_t* err_count;       /* nullable device int32 accumulator */
+} mzh_observe_args;
+
+int mzh_env_step_observe(const mzh_observe_args* args, mzh_stream stream);
+
 /* _move_allowed for all 6 moves (env/hanoi.py:117-139): bit a of mask[b] = move a legal. */
 int mzh_legal_mask(int n_disks, int B, const uint8_t* state, uint8_t* mask, mzh_stream stream);
 

@@ -106,6 +106,14 @@ class PlanArgs(ctypes.Structure):
                 ("rec_action", _vp), ("rec_reward", _vp), ("err_count", _vp)]
 
 
+class ObserveArgs(ctypes.Structure):
+    """mirror of struct mzh_observe_args (include/mzh.h)"""
+    _fields_ = [("n_disks", _i32), ("goal_peg", _i32), ("max_steps", _i32), ("B", _i32), ("n", _i32),
+                ("env_index", _vp), ("action", _vp), ("state", _vp), ("step_ctr", _vp), ("active", _vp),
+                ("steps_total", _vp), ("illegal_total", _vp), ("solved", _vp), ("perm_disc", _vp), ("perm_peg", _vp),
+                ("noise", _vp), ("obs", _vp), ("reward", _vp), ("done", _vp), ("err_count", _vp)]
+
+
 # name -> (restype, argtypes); every symbol include/mzh.h declares
 SIGNATURES = {
     "mzh_abi_version": (ctypes.c_int, []),
@@ -122,6 +130,7 @@ SIGNATURES = {
     "mzh_load_weight_set": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_int]),
     "mzh_env_step": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [_vp] * 10 + [_vp]),
     "mzh_env_run_plan": (ctypes.c_int, [ctypes.POINTER(PlanArgs), _vp]),
+    "mzh_env_step_observe": (ctypes.c_int, [ctypes.POINTER(ObserveArgs), _vp]),
     "mzh_legal_mask": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),
     "mzh_encode_obs": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),
     "mzh_hanoi_solver": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),

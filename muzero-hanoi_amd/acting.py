@@ -10,10 +10,17 @@ fused kernel launch, every env step the integer kernel).
   plan_multiple_actions  acting_experiments/planning_multiple_actions.py:111-183 (one search, then its
                        latent path executed open loop; a new search only when the plan ran out)
 
+  noise_play_game / noise_run_evaluation              noise_injection_comparison.py:17-37 / 40-46 (solve rate with
+                       Gaussian noise added to the observation the agent searches from)
+  permutation_play_game / permutation_run_evaluation  permutation_importance.py:27-76 / 79-91 (solve rate with one
+                       disc's peg replaced by a random peg in that observation)
+  get_ablated_network  permutation_importance.py:17-24 (a copy with re-initialised heads)
+
 They run one decision at a time, exactly as the reference does (same RNG stream, same MinMaxStats
 chain); selfplay.evaluate is the batched form (sequential=True reproduces get_results, and with
-max_plan_len plan_multiple_actions).
+max_plan_len plan_multiple_actions; selfplay.evaluate_perturbed batches the two perturbation scripts).
 """
+import copy
 import logging
 
 import numpy as np
@@ -22,6 +29,7 @@ import torch
 from .checkpoint import ablate_networks  # noqa: F401  (acting_ablations.py:29-45; one implementation)
 from .hanoi_utils import hanoi_solver
 from .selfplay import START_STATES
+from .utils import oneHot_encoding
 
 _LABELS = {0: "ES", 1: "MS", 2: "LS"}
 
@@ -124,3 +132,74 @@ def illegal_move_rate(env, networks, mcts, episodes=100, temperature=0.0, fixed_
     if not rates:
         return 0.0, 0.0
     return float(np.mean(rates)), float(np.std(rates, ddof=1) / np.sqrt(len(rates)))
+
+
+def get_ablated_network(networks, ablate_policy=False, ablate_value=False):
+    """permutation_importance.py:17-24: a deep copy of `networks` with the policy and / or value head
+    re-initialised (ablate_networks on the copy: the same draws from the global torch RNG)."""
+    return ablate_networks(ablate_policy, ablate_value, False, copy.deepcopy(networks))
+
+
+def _start_game(env, start_state):
+    """both play_game functions' first lines: reset, then put the env on start_state"""
+    env.reset()
+    env.c_state = start_state
+    env.oneH_c_state = oneHot_encoding(env.c_state, n_integers=env.n_pegs)
+
+
+def noise_play_game(networks, env, start_state, max_game_steps, mcts, noise_std=0.0):
+    """noise_injection_comparison.py:17-37: one game from start_state; before every search the one-hot
+    observation gets np.random.normal(0, noise_std) added (drawn only for noise_std > 0, before the search's
+    own draws), the action is applied to the true env.  True if a step returned reward 100."""
+    _start_game(env, start_state)
+    for _ in range(max_game_steps):
+        state_one_hot = oneHot_encoding(env.c_state, n_integers=env.n_pegs)
+        if noise_std > 0:
+            noise = np.random.normal(0.0, noise_std, size=state_one_hot.shape)
+            state_one_hot = state_one_hot + noise
+        action, _, _ = mcts.run_mcts(state_one_hot, networks, temperature=0, deterministic=True)
+        _, reward, done, _ = env.step(action)
+        if reward == 100:
+            return True
+        if done:
+            return False
+    return False
+
+
+def noise_run_evaluation(networks, env, test_states, max_game_steps, mcts, noise_std=0.0):
+    """noise_injection_comparison.py:40-46: the solve rate of `networks` over test_states under noise."""
+    solved = 0
+    for start_state in test_states:
+        if noise_play_game(networks, env, start_state, max_game_steps, mcts, noise_std):
+            solved += 1
+    return solved / len(test_states)
+
+
+def permutation_play_game(networks, env, start_state, max_game_steps, mcts, permute_feature=None):
+    """permutation_importance.py:27-76: one game from start_state; with permute_feature the agent searches from
+    the state with that disc's peg replaced by np.random.randint(0, n_pegs) (drawn before the search's own
+    draws), the action is applied to the true env.  True if a step returned reward 100."""
+    _start_game(env, start_state)
+    for _ in range(max_game_steps):
+        state_to_feed_model = env.c_state
+        if permute_feature is not None:
+            permuted_state_list = list(env.c_state)
+            permuted_state_list[permute_feature] = np.random.randint(0, env.n_pegs)
+            state_to_feed_model = tuple(permuted_state_list)
+        state_one_hot = oneHot_encoding(state_to_feed_model, n_integers=env.n_pegs)
+        action, _, _ = mcts.run_mcts(state_one_hot, networks, temperature=0, deterministic=True)
+        _, reward, done, _ = env.step(action)
+        if reward == 100:
+            return True
+        if done:
+            return False
+    return False
+
+
+def permutation_run_evaluation(networks, env, test_states, max_game_steps, mcts, permute_feature=None):
+    """permutation_importance.py:79-91: the solve rate of `networks` over test_states with a permuted disc."""
+    solved_count = 0
+    for start_state in test_states:
+        if permutation_play_game(networks, env, start_state, max_game_steps, mcts, permute_feature):
+            solved_count += 1
+    return solved_count / len(test_states)

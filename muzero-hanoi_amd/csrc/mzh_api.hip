@@ -306,6 +306,19 @@ extern "C" int mzh_env_run_plan(const mzh_plan_args* a, mzh_stream stream) {
   return e == hipSuccess ? MZH_OK : hip_fail(e, "env_run_plan launch");
 }
 
+extern "C" int mzh_env_step_observe(const mzh_observe_args* a, mzh_stream stream) {
+  if (!a) return fail(MZH_ERR_ARG, "env_step_observe: args is NULL");
+  if (a->n_disks < 1 || a->n_disks > 32 || a->goal_peg < 0 || a->goal_peg > 2)
+    return fail(MZH_ERR_ARG, "env_step_observe: bad n_disks=%d goal_peg=%d", a->n_disks, a->goal_peg);
+  if (a->n < 1 || a->B < 1 || (!a->env_index && a->B < a->n))
+    return fail(MZH_ERR_ARG, "env_step_observe: bad n=%d rows for B=%d envs", a->n, a->B);
+  if (!a->state || !a->step_ctr || !a->active || !a->steps_total || !a->illegal_total || !a->solved || !a->obs ||
+      (a->perm_disc && !a->perm_peg))
+    return fail(MZH_ERR_ARG, "env_step_observe: required buffer is NULL");
+  hipError_t e = mzh_launch_env_step_observe(a, (hipStream_t)stream);
+  return e == hipSuccess ? MZH_OK : hip_fail(e, "env_step_observe launch");
+}
+
 extern "C" int mzh_legal_mask(int n_disks, int B, const uint8_t* state, uint8_t* mask, mzh_stream stream) {
   if (n_disks < 1 || n_disks > 32 || B < 0 || (B > 0 && (!state || !mask))) return fail(MZH_ERR_ARG, "legal_mask: bad args");
   if (B == 0) return MZH_OK;

@@ -14,6 +14,9 @@
 // consecutive ints (one or two 64-byte lines at max_plan_len 7).  They are not staged through LDS: no
 // measurement says the gather matters next to the search that produced it.  Its record stores are laid
 // out [max_plan_len][n], so consecutive lanes store consecutive addresses.
+//
+// mzh_env_step_observe_kernel applies the same transition once per row and then writes the observation the
+// model is to see instead of the true one (noise_injection_comparison.py:17-37, permutation_importance.py:27-76).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -176,6 +179,68 @@ __global__ void mzh_env_run_plan_kernel(mzh_plan_args p) {
   }
 }
 
+// Step the true env and write the observation the model is to see (noise_injection_comparison.py:17-37,
+// permutation_importance.py:27-76): row j is env env_index[j] (j without env_index) of the full batch.  An env
+// inactive on entry is left untouched.  With `action` the env takes one step (tallied in steps_total /
+// illegal_total / solved); if it is still active afterwards its obs row becomes one-hot(c_state with disc
+// perm_disc's peg replaced by perm_peg[j]) + noise[j], the float64 sum rounded once to float32.  An error (env
+// index outside the batch; on an active env a bad action, perm_disc, or needed perm_peg) adds to err_count and
+// skips the row.  The obs stores of consecutive lanes are 12 * n_disks bytes apart at scattered envs; they are
+// not staged through LDS: no measurement says they matter next to the search that reads them.
+__global__ void mzh_env_step_observe_kernel(mzh_observe_args p) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= p.n) return;
+  const int n = p.n_disks;
+  const int e = p.env_index ? p.env_index[j] : j;
+  int8_t code = 0;
+  uint8_t dn = 0;
+  bool err = false;
+  if (e < 0 || e >= p.B) {
+    err = true;
+  } else if (p.active[e]) {
+    const int pd = p.perm_disc ? p.perm_disc[e] : -1;
+    const int a = p.action ? p.action[j] : 0;
+    int pp = 0;
+    if (pd < -1 || pd >= n) {
+      err = true;
+    } else if (pd >= 0) {
+      pp = p.perm_peg[j];
+      err = pp < 0 || pp > 2;
+    }
+    err = err || a < 0 || a >= 6;  // moves[action] IndexError
+    if (!err) {
+      uint8_t* sp = p.state + (size_t)e * n;
+      uint8_t st[MZH_MAXN];
+      int top[3];
+      load_state(sp, n, st, top);
+      if (p.action) {
+        int ctr = p.step_ctr[e];
+        uint8_t ill;
+        bool advanced;
+        code = env_transition(n, p.goal_peg, p.max_steps, a, st, top, sp, p.active + e, ctr, dn, ill, advanced);
+        p.step_ctr[e] = ctr;
+        p.steps_total[e] += 1;
+        p.illegal_total[e] += ill;
+        if (code == 1) p.solved[e] = 1;
+      }
+      if (!dn) {  // st == c_state here: it differs from c_state only on the goal step, which ends the episode
+        float* o = p.obs + (size_t)e * 3 * n;
+        const double* z = p.noise ? p.noise + (size_t)j * 3 * n : nullptr;
+        for (int d = 0; d < n; ++d) {
+          const int peg = d == pd ? pp : st[d];
+          for (int k = 0; k < 3; ++k) {
+            const double hot = peg == k ? 1.0 : 0.0;
+            o[3 * d + k] = z ? (float)(hot + z[3 * d + k]) : (float)hot;
+          }
+        }
+      }
+    }
+  }
+  if (err && p.err_count) atomicAdd(p.err_count, 1);
+  if (p.reward) p.reward[j] = code;
+  if (p.done) p.done[j] = dn;
+}
+
 __global__ void mzh_legal_mask_kernel(int n, int B, const uint8_t* state, uint8_t* mask) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
@@ -224,6 +289,11 @@ hipError_t mzh_launch_env_step(int n, int goal_peg, int max_steps, int B, uint8_
 
 hipError_t mzh_launch_env_run_plan(const mzh_plan_args* args, hipStream_t s) {
   hipLaunchKernelGGL(mzh_env_run_plan_kernel, dim3(nblocks(args->n, 256)), dim3(256), 0, s, *args);
+  return hipGetLastError();
+}
+
+hipError_t mzh_launch_env_step_observe(const mzh_observe_args* args, hipStream_t s) {
+  hipLaunchKernelGGL(mzh_env_step_observe_kernel, dim3(nblocks(args->n, 256)), dim3(256), 0, s, *args);
   return hipGetLastError();
 }
 

@@ -309,6 +309,37 @@ def env_run_plan(n_disks, max_steps, state, step_ctr, active, obs, plan, plan_le
     return executed, rec_a, rec_r
 
 
+def env_step_observe(n_disks, max_steps, state, step_ctr, active, obs, steps_total, illegal_total, solved, *,
+                     action=None, env_index=None, perm_disc=None, perm_peg=None, noise=None, goal_peg=2, err=None,
+                     reward=None, done=None):
+    """mzh_env_step_observe on device tensors: row j (env env_index[j], or j) takes action[j] on its true env
+    (action None: no step) and, while the env is still active, its row of obs becomes the observation the model
+    is to see: disc perm_disc[env]'s peg replaced by perm_peg[j], one-hot, plus noise[j] (float64, pre-scaled).
+    state / step_ctr / active / obs / steps_total / illegal_total / solved (and perm_disc) are the full batch's,
+    updated in place; action, perm_peg, noise are per row.  Returns (reward codes [n] int8, done [n] uint8)."""
+    dev = state.device
+    B, no = int(state.shape[0]), 3 * int(n_disks)
+    n = next((int(t.shape[0]) for t in (env_index, action, perm_peg, noise) if t is not None), B)
+    for name, t, dt, shape in (("env_index", env_index, torch.int32, (n,)), ("action", action, torch.int32, (n,)),
+                               ("perm_disc", perm_disc, torch.int32, (B,)), ("perm_peg", perm_peg, torch.int32, (n,)),
+                               ("noise", noise, torch.float64, (n, no)), ("obs", obs, torch.float32, (B, no)),
+                               ("steps_total", steps_total, torch.int32, (B,)),
+                               ("illegal_total", illegal_total, torch.int32, (B,)), ("solved", solved, torch.uint8, (B,))):
+        if t is not None and (t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev):
+            raise ValueError(f"env_step_observe: {name} must be a contiguous {dt} {shape} tensor on {dev}")
+    reward = torch.empty(n, dtype=torch.int8, device=dev) if reward is None else reward
+    done = torch.empty(n, dtype=torch.uint8, device=dev) if done is None else done
+    a = _lib.ObserveArgs()
+    a.n_disks, a.goal_peg, a.max_steps, a.B, a.n = int(n_disks), int(goal_peg), int(max_steps), B, n
+    for k, t in (("env_index", env_index), ("action", action), ("state", state), ("step_ctr", step_ctr),
+                 ("active", active), ("steps_total", steps_total), ("illegal_total", illegal_total), ("solved", solved),
+                 ("perm_disc", perm_disc), ("perm_peg", perm_peg), ("noise", noise), ("obs", obs), ("reward", reward),
+                 ("done", done), ("err_count", err)):
+        setattr(a, k, ptr(t))
+    check(_lib.lib().mzh_env_step_observe(ctypes.byref(a), _lib.stream_handle(dev)), "mzh_env_step_observe")
+    return reward, done
+
+
 def legal_mask(n_disks, state):
     mask = torch.empty(state.shape[0], dtype=torch.uint8, device=state.device)
     check(_lib.lib().mzh_legal_mask(n_disks, state.shape[0], ptr(state), ptr(mask), _lib.stream_handle(state.device)),

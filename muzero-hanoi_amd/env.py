@@ -142,6 +142,7 @@ class HanoiBatch:
         self.active = torch.zeros(B, dtype=torch.uint8, device=self.device)
         self.err = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.last_obs = self.steps_total = self.illegal_total = None  # run_plan's per-env arrays, made on first use
+        self.solved = self.perm_disc = None  # step_observe's, likewise
 
     def reset(self, state_idx):
         """state_idx [B] -> reference state tuples (index = sum s[i] * 3^(N-1-i))."""
@@ -150,7 +151,7 @@ class HanoiBatch:
         self.state.copy_(((idx[:, None] // pw) % 3).to(torch.uint8))
         self.step_ctr.zero_()
         self.active.fill_(1)
-        self.last_obs = self.steps_total = self.illegal_total = None
+        self.last_obs = self.steps_total = self.illegal_total = self.solved = self.perm_disc = None
         return self.obs()
 
     def obs(self):
@@ -170,15 +171,50 @@ class HanoiBatch:
         last_obs (the observation env.step returned last), steps_total and illegal_total (per-env sums since
         reset); errors are counted in self.err.  Returns dict(executed [n], action [L, n], reward [L, n] int8
         codes -- the last two with record=True, -1 / 0 where nothing ran)."""
-        if self.last_obs is None:
-            self.last_obs = self.obs()
-            self.steps_total = torch.zeros(self.B, dtype=torch.int32, device=self.device)
-            self.illegal_total = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+        self._tallies()
         executed, rec_a, rec_r = engine.env_run_plan(
             self.N, self.max_steps, self.state, self.step_ctr, self.active, self.last_obs, plan, plan_len,
             max_plan_len, self.steps_total, self.illegal_total, env_index=env_index, goal_peg=self.goal_peg,
             err=self.err, record=record)
         return dict(executed=executed, action=rec_a, reward=rec_r)
+
+    def _tallies(self):
+        """the per-env arrays of run_plan and step_observe (since reset), made on first use"""
+        if self.last_obs is None:
+            self.last_obs = self.obs()
+            self.steps_total = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+            self.illegal_total = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+        if self.solved is None:
+            self.solved = torch.zeros(self.B, dtype=torch.uint8, device=self.device)
+
+    def set_perturbation(self, perm_disc):
+        """perm_disc [B] (or a scalar for every env): the disc whose peg the model does not see, -1 / None for
+        none (permutation_importance.py:55-59); holds until reset.  Values outside [-1, N) are the kernel's to
+        refuse (self.err)."""
+        if perm_disc is None:
+            self.perm_disc = None
+            return
+        pd = torch.as_tensor(perm_disc, dtype=torch.int32).to(self.device).reshape(-1)
+        self.perm_disc = (pd.expand(self.B) if pd.numel() == 1 else pd).contiguous()
+        if self.perm_disc.shape[0] != self.B:
+            raise ValueError(f"set_perturbation: perm_disc must be a scalar or [{self.B}], got {tuple(pd.shape)}")
+
+    def step_observe(self, action, env_index=None, *, perm_peg=None, noise=None):
+        """Step the true envs and write the observation the model is to see, one mzh_env_step_observe launch
+        (noise_injection_comparison.py:17-37, permutation_importance.py:27-76): row j is env env_index[j] (env j
+        without env_index), takes action[j] (action None: an observe-only call, the first observation of an
+        episode) and, while still active, gets last_obs[env] = one-hot(state with disc perm_disc[env]'s peg
+        replaced by perm_peg[j]) + noise[j] (float64 [n, 3N], already scaled; rounded once to float32).
+        Finished envs are left untouched.  action / env_index / perm_peg are int32 device tensors [n]; perm_peg
+        is required where set_perturbation gave a disc.  Updates state, step_ctr, active, last_obs, steps_total,
+        illegal_total and solved (per-env, since reset); errors are counted in self.err.  Returns dict(reward
+        [n] int8 codes, done [n] uint8)."""
+        self._tallies()
+        reward, done = engine.env_step_observe(
+            self.N, self.max_steps, self.state, self.step_ctr, self.active, self.last_obs, self.steps_total,
+            self.illegal_total, self.solved, action=action, env_index=env_index, perm_disc=self.perm_disc,
+            perm_peg=perm_peg, noise=noise, goal_peg=self.goal_peg, err=self.err)
+        return dict(reward=reward, done=done)
 
     def legal_mask(self):
         return engine.legal_mask(self.N, self.state)

@@ -187,3 +187,20 @@ def synthetic_draws(n_roots, *, deterministic, alpha, eps=0.25, seed=0):
     tie = gt.integers(0, 6, size=n_roots, dtype=np.int32)
     u = None if deterministic else gu.random(n_roots)
     return noise, tie, u
+
+
+def perturbation_draws(n, n_obs, seed=0):
+    """One decision's observation-perturbation draws for n rows: perm_peg [n] int32, the replacement peg in 0..2
+    (np.random.randint(0, env.n_pegs), permutation_importance.py:58), and z [n, n_obs] float64 standard normal
+    (np.random.normal(0, std, shape) = std * z, noise_injection_comparison.py:26; the caller scales).
+    Like synthetic_draws they are not stream-compatible with the legacy global RNG, each quantity comes from its
+    own child stream of `seed`, and the draws for n rows are the first n rows of the draws for any larger count."""
+    gp, gz = (np.random.default_rng(s) for s in np.random.SeedSequence(seed).spawn(2))
+    return gp.integers(0, 3, size=n, dtype=np.int32), gz.standard_normal((n, n_obs))
+
+
+def perturbation_seeds(seed=0):
+    """the generator BatchedSelfPlay.play_perturbed takes its per-decision perturbation_draws seeds from
+    (int(g.integers(2**31)) per decision): a child of `seed`'s seed sequence, so a stream apart from the search
+    draws' seeds, which come from default_rng(seed) itself"""
+    return np.random.default_rng(np.random.SeedSequence(int(seed)).spawn(1)[0])

@@ -299,6 +299,103 @@ class BatchedSelfPlay:
         return res
 
 
+    def play_perturbed(self, start_idx, *, noise_std=None, permute_disc=None, temperature=0.0, deterministic=True,
+                       seed=0, minmax=None, net_index=None, draw_index=None):
+        """Episodes on perturbed observations (noise_injection_comparison.py:17-37, permutation_importance.py:27-76):
+        every agent searches from an observation that differs from its env's true state -- Gaussian noise of
+        standard deviation noise_std added to the one-hot encoding, and / or disc permute_disc's peg replaced by
+        a fresh random peg at every decision -- the chosen action is applied to the true env, and the episode is
+        solved if a step returned reward 100 (else it ends at max_steps).  noise_std / permute_disc: None, a
+        scalar, or [B] (None / 0 and None / -1: that env is not perturbed), so one batch mixes conditions.
+        The defaults are the scripts' `temperature=0, deterministic=True` searches.
+
+        Per move: one search over the unfinished envs (as in `play`: the same synthetic draws from the same
+        generator in the same order, the same per-agent MinMaxStats carry), one mzh_env_step_observe launch
+        through env_index that steps the true envs and writes the next perturbed observations, and one host read
+        (unfinished envs left, error count).  The perturbation draws of decision t (0: the first observation)
+        are rng.perturbation_draws(rows, 3N, seed_t) with seed_t the t-th int(g.integers(2**31)) of
+        g = rng.perturbation_seeds(seed): row j of them serves the j-th env that was unfinished before move
+        t - 1 (every env at t = 0), noise = std[env] * z[j].  Without any perturbation the result equals play's.
+        draw_index [B] (optional): env b takes row draw_index[b] of every draw, search draws included, instead
+        of the row of its rank among the unfinished envs -- then an env's episode does not depend on which other
+        envs share its batch (evaluate_perturbed plays one batch in slices with it).
+        Returns device tensors per env: steps, illegal, solved (uint8), start_idx, minmax."""
+        if isinstance(self.network, RecordedNetwork):
+            raise ValueError("play_perturbed: a RecordedNetwork replays recorded observations; use the acting drop-ins")
+        if np.asarray(start_idx).size < 1:
+            raise ValueError("play_perturbed: no start states")
+        start, eng, _, env, _, gen, mm = self._setup(start_idx, minmax, seed, net_index)
+        B, dev, no = int(start.shape[0]), eng.device, 3 * self.N
+        std, disc = perturbation_arrays(B, self.N, noise_std, permute_disc)
+        pgen = _rng.perturbation_seeds(seed)
+        std_dev = None if std is None else torch.from_numpy(std).to(dev)[:, None]
+        env.set_perturbation(disc)
+        rows_of, total = None, None
+        if draw_index is not None:
+            di = np.asarray(draw_index, np.int64).reshape(-1)
+            if di.shape[0] != B or di.min() < 0:
+                raise ValueError(f"play_perturbed: draw_index must be {B} non-negative rows")
+            rows_of, total = torch.from_numpy(di).to(dev), int(di.max()) + 1
+
+        def take(x, idx, n):
+            """a draw's rows for the envs idx: the first n, or the envs' own rows of a draw of `total`"""
+            if x is None:
+                return None
+            x = torch.as_tensor(x).to(dev)
+            return x[:n] if rows_of is None else x.index_select(0, rows_of.index_select(0, idx))
+
+        def perturbation(idx, n):
+            if std is None and disc is None:
+                return None, None
+            peg, z = _rng.perturbation_draws(n if total is None else total, no, int(pgen.integers(2**31)))
+            peg = None if disc is None else take(peg, idx, n).contiguous()
+            noise = None if std is None else (std_dev.index_select(0, idx) * take(z, idx, n)).contiguous()
+            return peg, noise
+
+        n, idx = B, torch.arange(B, device=dev)
+        peg, noise = perturbation(idx, n)
+        env.step_observe(None, perm_peg=peg, noise=noise)  # the first observations
+        while n:
+            draws = self._draws(n if total is None else total, deterministic, False, gen)
+            out = self._search(eng, False, env.last_obs.index_select(0, idx), idx, [take(x, idx, n) for x in draws], mm,
+                               temperature, deterministic)
+            peg, noise = perturbation(idx, n)
+            env.step_observe(out["action"], idx.to(torch.int32), perm_peg=peg, noise=noise)
+            # the move's one host read: how many envs are still playing, and the kernel's error count
+            left, err = (int(x) for x in torch.stack([env.active.sum(dtype=torch.int32), env.err[0]]).cpu())
+            if err:
+                raise RuntimeError(f"mzh_env_step_observe reported {err} error(s): an action outside 0..5 or a "
+                                   "perturbation outside its range")
+            n = left
+            idx = torch.sort(env.active, descending=True, stable=True).indices[:n]
+        return dict(steps=env.steps_total, illegal=env.illegal_total, solved=env.solved, start_idx=start.to(dev),
+                    minmax=mm)
+
+
+def perturbation_arrays(B, n_disks, noise_std, permute_disc):
+    """play_perturbed's per-env conditions, checked on the host: noise_std (None | scalar | [B]) -> float64 [B]
+    or None where no env has noise; permute_disc (None | scalar | [B], None / -1 = no disc) -> int32 [B] or None
+    where no env has one.  ValueError for a std < 0 (or NaN) and a disc outside [-1, n_disks)."""
+    std = disc = None
+    if noise_std is not None:
+        std = np.asarray(noise_std, np.float64).reshape(-1)
+        std = np.full(B, std[0]) if std.size == 1 else std
+        if std.shape[0] != B or not np.all(std >= 0):
+            raise ValueError(f"noise_std must be a scalar or [{B}] of values >= 0, got {noise_std!r}")
+        std = std if np.any(std > 0) else None
+    if permute_disc is not None:
+        pd = np.asarray([-1 if d is None else d for d in np.asarray(permute_disc, object).reshape(-1)])
+        if np.any(pd != pd.astype(np.int64)):
+            raise ValueError(f"permute_disc must hold integers, got {permute_disc!r}")
+        pd = pd.astype(np.int32)
+        pd = np.full(B, pd[0], np.int32) if pd.size == 1 else pd
+        if pd.shape[0] != B or pd.min() < -1 or pd.max() >= n_disks:
+            raise ValueError(f"permute_disc must be a scalar or [{B}] of discs in [0, {n_disks}) (None / -1: none), "
+                             f"got {permute_disc!r}")
+        disc = pd if np.any(pd >= 0) else None
+    return std, disc
+
+
 def episode_records(res, *, discount=0.8, TD_return=True, n_step=10, unroll_n_steps=5, n_action=6):
     """Muzero._play_game's return value for every env of a BatchedSelfPlay.play(record_obs=True)
     result, in env order: (steps, states, rwds, actions, pi_probs, returns, priorities)."""
@@ -488,3 +585,103 @@ def evaluate_networks(networks, n_disks, n_sims_range, *, episodes=1, start=None
         for m in range(M):
             _score_budget(scores[m], int(n), n_disks, goal_peg, starts, steps[m * E:(m + 1) * E], ill[m * E:(m + 1) * E])
     return [dict(**sc, minmax=None) for sc in scores]
+
+
+# ------------------------------------------------------------------------------------------------
+# evaluation on perturbed observations (noise_injection_comparison.py, permutation_importance.py)
+# ------------------------------------------------------------------------------------------------
+def perturbed_layout(n_networks, conditions, start_idx, n_disks):
+    """evaluate_perturbed's batch, on the host: one row per (network, condition, start), network-major then
+    condition then start, so net_index is non-decreasing and every (network, condition) pair has the same starts.
+    conditions: a list of ("baseline",), ("noise", std) and ("permute", disc).  Returns dict(net_index,
+    cond_index, start_idx (int64 [R]), noise_std (float64 [R], 0 = none), permute_disc (int32 [R], -1 = none))
+    with R = n_networks * len(conditions) * len(start_idx).  ValueError: an unknown condition, std < 0, a disc
+    outside [0, n_disks), no conditions, no starts, n_networks < 1."""
+    starts = np.asarray(start_idx, np.int64).reshape(-1)
+    M, C, E = int(n_networks), len(conditions), int(starts.shape[0])
+    if M < 1 or C < 1 or E < 1:
+        raise ValueError(f"evaluate_perturbed: needs networks, conditions and starts, got {M}, {C}, {E}")
+    if starts.min() < 0 or starts.max() >= 3 ** n_disks:
+        raise ValueError(f"evaluate_perturbed: start indices must be in [0, {3 ** n_disks})")
+    std, disc = np.zeros(C, np.float64), np.full(C, -1, np.int32)
+    for c, cond in enumerate(conditions):
+        cond = tuple(cond) if isinstance(cond, (tuple, list)) else (cond,)
+        kind = cond[0] if cond else None
+        if kind == "baseline" and len(cond) == 1:
+            continue
+        if kind == "noise" and len(cond) == 2:
+            if not float(cond[1]) >= 0:
+                raise ValueError(f"evaluate_perturbed: noise std must be >= 0, got {cond[1]!r}")
+            std[c] = float(cond[1])
+        elif kind == "permute" and len(cond) == 2:
+            if int(cond[1]) != cond[1] or not 0 <= int(cond[1]) < n_disks:
+                raise ValueError(f"evaluate_perturbed: permuted disc must be in [0, {n_disks}), got {cond[1]!r}")
+            disc[c] = int(cond[1])
+        else:
+            raise ValueError(f"evaluate_perturbed: unknown condition {cond!r}: (\"baseline\",), (\"noise\", std) "
+                             "or (\"permute\", disc)")
+    cond_index = np.tile(np.repeat(np.arange(C), E), M)
+    return dict(net_index=np.repeat(np.arange(M), C * E), cond_index=cond_index, start_idx=np.tile(starts, M * C),
+                noise_std=std[cond_index], permute_disc=disc[cond_index])
+
+
+def perturbed_scores(solved, n_networks, conditions):
+    """solve_rate [M][C] (run_evaluation's solved / len(test_states)) and importance [M][C] from the per-row
+    solved flags of a perturbed_layout batch: for a ("permute", disc) condition the network's first baseline
+    rate minus its rate (permutation_importance.py:170-182); NaN for other conditions and without a baseline."""
+    M, C = int(n_networks), len(conditions)
+    rate = np.asarray(solved).reshape(M, C, -1).astype(np.float64).mean(axis=2)
+    kinds = [(tuple(c) if isinstance(c, (tuple, list)) else (c,))[0] for c in conditions]
+    importance = np.full((M, C), np.nan)
+    if "baseline" in kinds:
+        for c, k in enumerate(kinds):
+            if k == "permute":
+                importance[:, c] = rate[:, kinds.index("baseline")] - rate[:, c]
+    return rate, importance
+
+
+def evaluate_perturbed(networks, n_disks, *, conditions, starts=None, start_idx=None, episodes=None, n_sims=25,
+                       max_steps=50, seed=0, goal_peg=2, max_roots=65536):
+    """The solve rates of noise_injection_comparison.py (main: rate per noise std) and permutation_importance.py
+    (main: per network a baseline rate and one per permuted disc, importance = baseline - permuted) as one batch
+    of len(networks) * len(conditions) * len(starts) episodes (perturbed_layout), played by
+    BatchedSelfPlay.play_perturbed in slices of max_roots rows: searches at temperature 0, deterministic, 25
+    simulations and at most 50 steps by default, as the scripts run them.
+    networks: one network, a sequence of networks or a networks.NetworkSet (e.g. the base network and
+    acting.get_ablated_network's variants).  conditions: ("baseline",), ("noise", std), ("permute", disc).
+    The starts, the same for every (network, condition): starts = state tuples (permutation_importance.py:143-156),
+    or start_idx = state indices, or episodes = that many random non-goal states of `seed`.
+    Every episode is its own agent with a fresh MinMaxStats (the scripts carry one MCTS instance through all
+    games: acting.noise_run_evaluation / permutation_run_evaluation are that schedule) and takes row r of every
+    draw, r its row of the batch, so the slicing does not change any episode.
+    Returns dict(solve_rate [M][C], importance [M][C], solved [R] uint8, steps [R] int32, illegal [R] int32 and the
+    layout's net_index / cond_index / start_idx [R]) as host arrays."""
+    if isinstance(networks, NetworkSet):
+        nset = networks
+    else:
+        nset = NetworkSet(list(networks) if isinstance(networks, (list, tuple)) else [networks])
+    if nset.in_dim != 3 * n_disks:
+        raise ValueError(f"evaluate_perturbed: the networks read {nset.in_dim} inputs, n_disks={n_disks} gives {3 * n_disks}")
+    if int(max_roots) < 1:
+        raise ValueError(f"evaluate_perturbed: max_roots must be >= 1, got {max_roots}")
+    if starts is not None:
+        start_idx = [state_index(s) for s in starts]
+    elif start_idx is None:
+        if episodes is None or int(episodes) < 1:
+            raise ValueError("evaluate_perturbed: no starts (give starts, start_idx or episodes >= 1)")
+        start_idx = _batch_starts(n_disks, int(episodes), None, None, seed, goal_peg)
+    lay = perturbed_layout(len(nset), conditions, start_idx, n_disks)
+    R = int(lay["net_index"].shape[0])
+    sp = BatchedSelfPlay(nset, n_disks, max_steps, int(n_sims), goal_peg=goal_peg)
+    got = dict(solved=[], steps=[], illegal=[])
+    for lo in range(0, R, int(max_roots)):
+        sl = slice(lo, min(R, lo + int(max_roots)))
+        res = sp.play_perturbed(lay["start_idx"][sl], noise_std=lay["noise_std"][sl],
+                                permute_disc=lay["permute_disc"][sl], seed=seed, net_index=lay["net_index"][sl],
+                                draw_index=np.arange(sl.start, sl.stop))
+        for k in got:
+            got[k].append(res[k].cpu().numpy())
+    got = {k: np.concatenate(v) for k, v in got.items()}
+    rate, importance = perturbed_scores(got["solved"], len(nset), conditions)
+    return dict(solve_rate=rate, importance=importance, **got, net_index=lay["net_index"],
+                cond_index=lay["cond_index"], start_idx=lay["start_idx"])
