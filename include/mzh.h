@@ -344,6 +344,45 @@ typedef struct mzh_multi_args {
 } mzh_multi_args;
 int mzh_search_multi(mzh_engine* eng, const mzh_search_args* args, const mzh_multi_args* multi, mzh_stream stream);
 
+/* Action probe (acting_experiments/legal_illegal_preds.py evaluate_network, lines 26-80): what the model
+ * predicts for each of the six moves from a state -- h = represent(obs) (networks.py:71-94), then
+ * recurrent_inference(h, one_hot(a)) for a = 0..5 (networks.py:96-138) -- which the script files under legal or
+ * illegal by env._move_allowed (env/hanoi.py:117-139).  One launch for n rows of a sub-batch: row j is env
+ * env_index[j] of the full batch of B envs (env j where env_index is NULL; the indices of one call must be
+ * distinct).  A workgroup keeps its 16 or 32 root latents in LDS across the six lookaheads; each row's outputs
+ * are bit-identical to mzh_initial_inference followed by mzh_recurrent_inference on that row.  Every array
+ * but env_index (and multi's net_index) is indexed by env; rows outside the call are left untouched.
+ * With `multi`: row j is probed under network net_index[j] of the set loaded by mzh_load_weight_set
+ * (non-decreasing over the rows), with the result this call gives on an engine holding that network alone;
+ * the tile table is made by this call (two launches, as mzh_search_multi), on a grid of
+ * ceil(n / tile) + min(n_networks, n) - 1 workgroups.
+ * MZH_ERR_ARG, before any launch and before a device or an engine is needed: a NULL required pointer (args,
+ * obs, reward, value; state where legal is given), n < 1, B < 1 (B < n without env_index), a flag other than
+ * MZH_FLAG_COOP_TILE16 / 32 (default tile: 16 rows while n <= 4096, else 32); with multi a NULL net_index or
+ * n_networks outside [1, 256]; then a NULL engine, and n_networks above the loaded set's M.
+ * MZH_ERR_STATE: weights not loaded (without multi), no set loaded (with multi).  MZH_ERR_CAPACITY: n > max_roots.
+ * On the device: a row whose env index is outside [0, B) is skipped and adds 1 to *err_count; a refused
+ * net_index writes nothing and sets multi->status[0] = 1, as in mzh_search_multi. */
+typedef struct mzh_probe_args {
+  int32_t B;                /* envs of the full batch */
+  int32_t n;                /* rows of this call */
+  uint32_t flags;           /* MZH_FLAG_COOP_TILE16 / 32 only */
+  const int32_t* env_index; /* [n] or NULL: row j is env env_index[j] (distinct), else env j */
+  const float* obs;         /* [B][3 n_disks], indexed by env */
+  const uint8_t* state;     /* [B][n_disks] nullable: c_state, for `legal` */
+  float* reward;            /* [B][6] indexed by env: recurrent_inference(represent(obs), a)'s reward */
+  float* value;             /* [B][6] */
+  uint8_t* legal;           /* [B] nullable (needs state): bit a = move a allowed, as mzh_legal_mask */
+  float* h0;                /* [B][64]   nullable: root latent                 */
+  float* pi0;               /* [B][6]    nullable: root policy                 */
+  float* value0;            /* [B]       nullable: root value                  */
+  float* h1;                /* [B][6][64] nullable: the six next latents       */
+  float* pi1;               /* [B][6][6]  nullable                             */
+  int32_t* err_count;       /* nullable: += 1 per row whose env_index is outside [0, B); the row is skipped */
+} mzh_probe_args;
+int mzh_probe_actions(mzh_engine* eng, const mzh_probe_args* args, const mzh_multi_args* multi /* nullable */,
+                      mzh_stream stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Reference-order host pre-draw (HOST pointers only; no device, no engine).  Replaces the NumPy
  * calls B sequential run_mcts calls make on the global legacy stream, in their order per call:

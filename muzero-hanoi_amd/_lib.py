@@ -114,6 +114,13 @@ class ObserveArgs(ctypes.Structure):
                 ("noise", _vp), ("obs", _vp), ("reward", _vp), ("done", _vp), ("err_count", _vp)]
 
 
+class ProbeArgs(ctypes.Structure):
+    """mirror of struct mzh_probe_args (include/mzh.h)"""
+    _fields_ = [("B", _i32), ("n", _i32), ("flags", ctypes.c_uint32),
+                ("env_index", _vp), ("obs", _vp), ("state", _vp), ("reward", _vp), ("value", _vp), ("legal", _vp),
+                ("h0", _vp), ("pi0", _vp), ("value0", _vp), ("h1", _vp), ("pi1", _vp), ("err_count", _vp)]
+
+
 # name -> (restype, argtypes); every symbol include/mzh.h declares
 SIGNATURES = {
     "mzh_abi_version": (ctypes.c_int, []),
@@ -139,6 +146,7 @@ SIGNATURES = {
     "mzh_search": (ctypes.c_int, [_vp, ctypes.POINTER(SearchArgs), _vp]),
     "mzh_search_replay": (ctypes.c_int, [_vp, ctypes.POINTER(SearchArgs), _vp]),
     "mzh_search_multi": (ctypes.c_int, [_vp, ctypes.POINTER(SearchArgs), ctypes.POINTER(MultiArgs), _vp]),
+    "mzh_probe_actions": (ctypes.c_int, [_vp, ctypes.POINTER(ProbeArgs), ctypes.POINTER(MultiArgs), _vp]),
     "mzh_search_plan_query": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int,
                                              ctypes.c_int, ctypes.POINTER(SearchPlan)]),
     "mzh_rng_predraw": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int,

@@ -15,20 +15,29 @@ fused kernel launch, every env step the integer kernel).
   permutation_play_game / permutation_run_evaluation  permutation_importance.py:27-76 / 79-91 (solve rate with one
                        disc's peg replaced by a random peg in that observation)
   get_ablated_network  permutation_importance.py:17-24 (a copy with re-initialised heads)
+  ablate_network / legality_evaluate_network  legal_illegal_preds.py:16-23 / 26-80 (the predicted reward and value
+                       of the six moves at every decision, legal minus illegal; one mzh_probe_actions launch per
+                       decision); legality_summary is its statistics, shared with selfplay.evaluate_legality
 
 They run one decision at a time, exactly as the reference does (same RNG stream, same MinMaxStats
 chain); selfplay.evaluate is the batched form (sequential=True reproduces get_results, and with
 max_plan_len plan_multiple_actions; selfplay.evaluate_perturbed batches the two perturbation scripts).
 """
 import copy
+import ctypes
 import logging
 
 import numpy as np
 import torch
 
+from . import _lib
+from . import engine as _engine
 from .checkpoint import ablate_networks  # noqa: F401  (acting_ablations.py:29-45; one implementation)
 from .hanoi_utils import hanoi_solver
+from .mcts import RecordedNetwork
+from .networks import engine_for
 from .selfplay import START_STATES
+from .staging import Packed
 from .utils import oneHot_encoding
 
 _LABELS = {0: "ES", 1: "MS", 2: "LS"}
@@ -138,6 +147,125 @@ def get_ablated_network(networks, ablate_policy=False, ablate_value=False):
     """permutation_importance.py:17-24: a deep copy of `networks` with the policy and / or value head
     re-initialised (ablate_networks on the copy: the same draws from the global torch RNG)."""
     return ablate_networks(ablate_policy, ablate_value, False, copy.deepcopy(networks))
+
+
+def ablate_network(networks, ablate_policy=False, ablate_value=False):
+    """legal_illegal_preds.py:16-23: a deep copy of `networks` with the policy and / or value head re-initialised
+    (policy first: the same draws from the global torch RNG)."""
+    net_copy = copy.deepcopy(networks)
+    if ablate_policy:
+        net_copy.policy_net.apply(net_copy.reset_param)
+    if ablate_value:
+        net_copy.value_net.apply(net_copy.reset_param)
+    return net_copy
+
+
+def legality_summary(reward, value, legal, steps):
+    """legal_illegal_preds.py:60-80 from the probes of every decision: reward / value [T][B][6] float32 (the
+    predicted reward and value of move a at decision t of episode b), legal [T][B] uint8 (bit a: move a allowed),
+    steps [B] decisions of episode b (rows t >= steps[b] are not read).  Per episode the means of its legal and
+    illegal lists in the reference's append order (decision-major, move ascending), np.mean over the float64 of
+    the float32 values as the reference's lists of Python floats give, 0.0 for an empty list; then the mean and
+    the standard error np.std(ddof=1) / sqrt(n) of the per-episode (legal - illegal) differences, 0.0 without
+    episodes.  Returns evaluate_network's dict."""
+    reward, value = np.asarray(reward, np.float32), np.asarray(value, np.float32)
+    legal, steps = np.asarray(legal, np.uint8), np.asarray(steps, np.int64).reshape(-1)
+    mean = lambda xs: np.mean(xs) if xs else 0.0
+    reward_diffs, value_diffs = [], []
+    for b in range(steps.shape[0]):
+        T = int(steps[b])
+        ok = ((legal[:T, b, None] >> np.arange(6)) & 1).astype(bool).reshape(-1)  # decision-major, move ascending
+        r = [float(x) for x in reward[:T, b].reshape(-1)]
+        v = [float(x) for x in value[:T, b].reshape(-1)]
+        pick = lambda xs, keep: [x for x, k in zip(xs, ok) if k == keep]
+        reward_diffs.append(mean(pick(r, True)) - mean(pick(r, False)))
+        value_diffs.append(mean(pick(v, True)) - mean(pick(v, False)))
+    n_r, n_v = len(reward_diffs), len(value_diffs)
+    return {
+        "reward_diff_mean": float(np.mean(reward_diffs)) if reward_diffs else 0.0,
+        "reward_diff_std": float(np.std(reward_diffs, ddof=1) / np.sqrt(n_r)) if reward_diffs else 0.0,
+        "value_diff_mean": float(np.mean(value_diffs)) if value_diffs else 0.0,
+        "value_diff_std": float(np.std(value_diffs, ddof=1) / np.sqrt(n_v)) if value_diffs else 0.0,
+    }
+
+
+class _OneRootProbe:
+    """the host side of a probe of one root on `eng`: its observation and state in, the six (reward, value) pairs
+    and the legal mask out, in pinned host memory the kernel addresses where the device can (one launch and one
+    synchronisation per decision, as the one-root search)"""
+
+    def __init__(self, eng):
+        n = eng.n_disks
+        self.eng = eng
+        self.pin = Packed.mapped([("obs", torch.float32, (1, 3 * n)), ("state", torch.uint8, (1, n))], eng.device)
+        self.pout = Packed.mapped([("reward", torch.float32, (1, 6)), ("value", torch.float32, (1, 6)),
+                                   ("legal", torch.uint8, (1,))], eng.device)
+        a = self.args = _lib.ProbeArgs()
+        a.B = a.n = 1
+        a.obs, a.state = self.pin.dptr["obs"], self.pin.dptr["state"]
+        a.reward, a.value, a.legal = (self.pout.dptr[k] for k in ("reward", "value", "legal"))
+
+    def __call__(self, obs, c_state):
+        h = self.pin.h
+        h["obs"][0] = obs  # torch.tensor(state, dtype=torch.float32), legal_illegal_preds.py:39
+        h["state"][0] = c_state
+        self.pin.to_device()
+        _lib.check(_lib.lib().mzh_probe_actions(self.eng._h, ctypes.byref(self.args), None,
+                                                _lib.stream_handle(self.eng.device)), "mzh_probe_actions")
+        self.pout.to_host()
+        o = self.pout.h
+        return o["reward"][0].copy(), o["value"][0].copy(), int(o["legal"][0])
+
+
+def _probe_decision(env, mcts, networks, state):
+    """one decision's probe after its search: (reward [6], value [6] float32, legal mask).  A RecordedNetwork
+    carries the probe in its recording (no probe launch; the mask is mzh_legal_mask's on the env's state)."""
+    if isinstance(networks, RecordedNetwork):
+        p = networks.last_probe()
+        st = torch.tensor([list(env.c_state)], dtype=torch.uint8, device=env._dev)
+        return (np.asarray(p["reward"], np.float32), np.asarray(p["value"], np.float32),
+                int(_engine.legal_mask(env.discs, st).item()))
+    eng = engine_for(networks, int(mcts.n_simulations), 1)  # the engine the search just ran on
+    probe = eng.__dict__.get("_one_probe")
+    if probe is None:
+        probe = eng._one_probe = _OneRootProbe(eng)
+    return probe(np.asarray(state).reshape(-1), env.c_state)
+
+
+@torch.no_grad()
+def legality_evaluate_network(env, mcts, networks, episodes, device, trace=None):
+    """legal_illegal_preds.py:26-80 evaluate_network, with its signature and its dict: episodes from
+    random_reset, at every decision run_mcts(temperature=0.0, deterministic=False) and then the model's predicted
+    reward and value of each of the six moves from the current state, filed under legal or illegal by
+    env._move_allowed; per episode the means' difference, over episodes its mean and standard error.  The same
+    draws from NumPy's global stream as the reference.  The reference's seven network calls per decision
+    (represent, six recurrent_inference) are one mzh_probe_actions launch of one row.  `device` is accepted as
+    the reference takes it (the probe runs on the network's engine).
+    trace: a list that receives per decision (reward [6] float32, value [6] float32, legal mask, action)."""
+    rec_r, rec_v, rec_l, steps = [], [], [], []
+    for _ in range(episodes):
+        state = env.random_reset()
+        done = False
+        ep_r, ep_v, ep_l = [], [], []
+        while not done:
+            action, _, _ = mcts.run_mcts(state, networks, temperature=0.0, deterministic=False)
+            r6, v6, mask = _probe_decision(env, mcts, networks, state)
+            ep_r.append(r6)
+            ep_v.append(v6)
+            ep_l.append(mask)
+            if trace is not None:
+                trace.append((r6, v6, mask, int(action)))
+            state, _, done, _ = env.step(action)
+        rec_r.append(ep_r)
+        rec_v.append(ep_v)
+        rec_l.append(ep_l)
+        steps.append(len(ep_l))
+    T, B = max(steps, default=0), len(steps)
+    reward, value = np.zeros((T, B, 6), np.float32), np.zeros((T, B, 6), np.float32)
+    legal = np.zeros((T, B), np.uint8)
+    for b in range(B):
+        reward[:steps[b], b], value[:steps[b], b], legal[:steps[b], b] = rec_r[b], rec_v[b], rec_l[b]
+    return legality_summary(reward, value, legal, steps)
 
 
 def _start_game(env, start_state):

@@ -657,6 +657,56 @@ extern "C" int mzh_search_multi(mzh_engine* eng, const mzh_search_args* a, const
   return e == hipSuccess ? MZH_OK : hip_fail(e, "multi search launch");
 }
 
+// The six one-step lookaheads of a batch of roots in one launch (mzh_probe_kernel; with `m` the rows of a
+// loaded network set, mzh_probe_multi_kernel).  What the arguments alone decide is refused first, so those
+// refusals need neither a device nor an engine.
+extern "C" int mzh_probe_actions(mzh_engine* eng, const mzh_probe_args* a, const mzh_multi_args* m, mzh_stream stream) {
+  if (!a) return fail(MZH_ERR_ARG, "probe_actions: args is NULL");
+  if (a->n < 1 || a->B < 1 || (!a->env_index && a->B < a->n))
+    return fail(MZH_ERR_ARG, "probe_actions: bad n=%d rows for B=%d envs", a->n, a->B);
+  if (!a->obs || !a->reward || !a->value || (a->legal && !a->state))
+    return fail(MZH_ERR_ARG, "probe_actions: required buffer is NULL (obs, reward, value; state for legal)");
+  if (a->flags & ~(MZH_FLAG_COOP_TILE16 | MZH_FLAG_COOP_TILE32))
+    return fail(MZH_ERR_ARG, "probe_actions: flags=0x%x, only MZH_FLAG_COOP_TILE16 / 32 apply", a->flags);
+  if (m) {
+    if (!m->net_index) return fail(MZH_ERR_ARG, "probe_actions: net_index is NULL");
+    if (m->n_networks < 1 || m->n_networks > MZH_MULTI_MAX_NETS)
+      return fail(MZH_ERR_ARG, "probe_actions: n_networks=%d outside [1, %d]", m->n_networks, MZH_MULTI_MAX_NETS);
+  }
+  if (!eng) return fail(MZH_ERR_ARG, "probe_actions: engine NULL");
+  if (m) {
+    if (eng->set_m == 0) return fail(MZH_ERR_STATE, "no weight set loaded (mzh_load_weight_set)");
+    if (m->n_networks > eng->set_m)
+      return fail(MZH_ERR_ARG, "probe_actions: n_networks=%d outside [1, %d], the loaded set", m->n_networks, eng->set_m);
+  } else if (!eng->loaded) {
+    return fail(MZH_ERR_STATE, "weights not loaded");
+  }
+  if (a->n > eng->max_roots) return fail(MZH_ERR_CAPACITY, "probe_actions: n=%d > max_roots=%d", a->n, eng->max_roots);
+  DeviceGuard g(eng->device);
+  if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+  MzhProbeParams p{};
+  p.B = a->B; p.n = a->n; p.in_dim = eng->in_dim; p.kin = eng->kin; p.n_disks = eng->n_disks;
+  p.env_index = a->env_index; p.obs = a->obs; p.state = a->state; p.reward = a->reward; p.value = a->value;
+  p.legal = a->legal; p.h0 = a->h0; p.pi0 = a->pi0; p.value0 = a->value0; p.h1 = a->h1; p.pi1 = a->pi1;
+  p.err_count = a->err_count;
+  const int R = pick_tile(a->n, a->flags);
+  hipError_t e;
+  if (m) {
+    MzhMultiParams mp{};
+    mp.net_index = m->net_index;
+    mp.M = m->n_networks;
+    mp.tiles = eng->mtiles;
+    mp.ntiles = eng->mntiles;
+    mp.status = m->status;
+    mp.stride = eng->set_stride;
+    mp.scal = eng->set_scal;
+    e = mzh_launch_probe(R, eng->setnet, p, &mp, (hipStream_t)stream);
+  } else {
+    e = mzh_launch_probe(R, eng->net, p, nullptr, (hipStream_t)stream);
+  }
+  return e == hipSuccess ? MZH_OK : hip_fail(e, "probe_actions launch");
+}
+
 // ---------------------------------------------------------------------------------------------
 // fused training update (mzh_train.hip)
 namespace {

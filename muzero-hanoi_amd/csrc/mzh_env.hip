@@ -244,12 +244,7 @@ __global__ void mzh_env_step_observe_kernel(mzh_observe_args p) {
 __global__ void mzh_legal_mask_kernel(int n, int B, const uint8_t* state, uint8_t* mask) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  uint8_t st[MZH_MAXN];
-  int top[3];
-  load_state(state + (size_t)b * n, n, st, top);
-  uint8_t m = 0;
-  for (int a = 0; a < 6; ++a) m |= (uint8_t)((top[kMoveFrom[a]] < top[kMoveTo[a]]) << a);
-  mask[b] = m;
+  mask[b] = mzh_legal_mask_row(state + (size_t)b * n, n);
 }
 
 __global__ void mzh_encode_obs_kernel(int n, int B, const uint8_t* state, float* obs) {

@@ -182,6 +182,30 @@ static inline int mzh_multi_max_tiles(int B, int R, int M) { return (B + R - 1) 
 hipError_t mzh_launch_search_multi(const MzhSearchPlan& pl, const MzhNet& net, const MzhSearchParams& p,
                                    const MzhMultiParams& mp, hipStream_t stream);
 
+// mzh_probe_actions (mzh_probe_kernel / mzh_probe_multi_kernel, mzh_search.hip): row j of the call is env
+// env_index[j] (or j) of a batch of B; every array but env_index (and a set's net_index) is indexed by env
+struct MzhProbeParams {
+  int B, n;         // envs of the batch, rows of the call
+  int in_dim, kin;  // observation width 3N and its zero-padded width (16 * rep0.kb)
+  int n_disks;
+  const int32_t* env_index;  // [n] nullable
+  const float* obs;          // [B][in_dim]
+  const uint8_t* state;      // [B][n_disks] nullable
+  float* reward;             // [B][6]
+  float* value;              // [B][6]
+  uint8_t* legal;            // [B] nullable
+  float* h0;                 // [B][64] nullable
+  float* pi0;                // [B][6] nullable
+  float* value0;             // [B] nullable
+  float* h1;                 // [B][6][64] nullable
+  float* pi1;                // [B][6][6] nullable
+  int32_t* err_count;        // nullable
+};
+size_t mzh_probe_smem_bytes(int R);
+// mp == nullptr: mzh_probe_kernel<R> on ceil(n / R) workgroups; else the tile table of the n rows, then
+// mzh_probe_multi_kernel<R> on mzh_multi_max_tiles(n, R, mp->M) workgroups (net: the set's network 0)
+hipError_t mzh_launch_probe(int R, const MzhNet& net, const MzhProbeParams& p, const MzhMultiParams* mp, hipStream_t stream);
+
 size_t mzh_one_smem_bytes(int S, bool latl);
 hipError_t mzh_launch_one(const MzhSearchPlan& pl, const MzhNet& net, const MzhOneNet& on, const MzhSearchParams& p,
                           hipStream_t stream);

@@ -10,6 +10,7 @@
 // holding its 6 children's N/X/R/P/W); the per-sim path, per-root min-max, root stats, UCB table and
 // the MLP activations live in LDS.  Weights stream from L2 (shared by every workgroup of an XCD).
 #include "mzh_device.h"
+#include "mzh_env_kernels.h"
 #include "mzh_internal.h"
 #include "mzh_tree.h"
 
@@ -399,6 +400,111 @@ __global__ __launch_bounds__(MZH_THREADS, 1) void mzh_recurrent_kernel(MzhNet ne
 }
 
 // ------------------------------------------------------------------------------------------
+// Action probe (mzh_probe_actions; the reference's legal_illegal_preds.py evaluate_network, lines 26-80): per
+// row represent(obs), then recurrent_inference(h, a) for a = 0..5, in one launch.  The R root latents stay in
+// LDS (x0) between the six lookaheads -- mzh_mlp_recurrent_body overwrites sm.x with the new latent -- so the
+// launch reads each observation once and never writes or re-reads a latent through HBM unless the caller asks
+// for h0 / h1.  Every dot product is the chain mzh_initial_kernel / mzh_recurrent_kernel run (the same
+// mzh_mlp_initial / mzh_mlp_recurrent on the same LDS block), so a row's outputs are bit-identical to those
+// two calls composed.  Row r of the tile is env sm.env[r] of the batch (-1: beyond the tile, or an env index
+// outside [0, B): the row runs on a zero observation and stores nothing).
+// ------------------------------------------------------------------------------------------
+template <int R>
+struct ProbeSmem : MlpSmem<R> {
+  float x0[R * MZH_LD64];  // the normalised root latents, in sm.x's layout
+  int env[R];
+};
+
+template <int R, class TILE = MzhGridTile>
+__device__ __forceinline__ void mzh_probe_body(const MzhNet& net, const MzhProbeParams& p, const TILE tile = TILE{}) {
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  ProbeSmem<R>& sm = *reinterpret_cast<ProbeSmem<R>*>(smem_raw);
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int row0 = tile.template root0<R>();
+  const int nvalid = tile.template nvalid<R>(p.n, row0);
+  if (tid < R) {
+    int e = -1;
+    if (tid < nvalid) {
+      e = p.env_index ? p.env_index[row0 + tid] : row0 + tid;
+      if ((unsigned)e >= (unsigned)p.B) {
+        if (p.err_count) atomicAdd(p.err_count, 1);
+        e = -1;
+      }
+    }
+    sm.env[tid] = e;
+  }
+  __syncthreads();
+  for (int i = tid; i < R * p.kin; i += MZH_THREADS) {
+    const int r = i / p.kin, k = i - r * p.kin;
+    const int e = sm.env[r];
+    sm.x[r * MZH_LD64 + mzh_kpos(k)] = (e >= 0 && k < p.in_dim) ? p.obs[(size_t)e * p.in_dim + k] : 0.0f;
+  }
+  __syncthreads();
+  MlpSmem<R>& ms = sm;  // the MLP block the inference kernels run on
+  mzh_mlp_initial<R>(ms, net, wave, lane);
+  // the root: position k of a row of sm.x holds unit mzh_kpos(k) (an involution)
+  for (int i = tid; i < R * MZH_H; i += MZH_THREADS) {
+    const int r = i >> 6, k = i & 63;
+    const int e = sm.env[r];
+    const float v = sm.x[r * MZH_LD64 + k];
+    sm.x0[r * MZH_LD64 + k] = v;
+    if (p.h0 && e >= 0) p.h0[(size_t)e * MZH_H + mzh_kpos(k)] = v;
+  }
+  if (tid < R * 8) {
+    const int r = tid >> 3, c = tid & 7;
+    const int e = sm.env[r];
+    if (e >= 0) {
+      if (p.pi0 && c < MZH_A) p.pi0[(size_t)e * MZH_A + c] = sm.pi[r * 8 + c];
+      if (p.value0 && c == 6) p.value0[e] = sm.value[r];
+      if (p.legal && c == 7) p.legal[e] = mzh_legal_mask_row(p.state + (size_t)e * p.n_disks, p.n_disks);
+    }
+  }
+  __syncthreads();
+#pragma unroll 1
+  for (int a = 0; a < MZH_A; ++a) {
+    for (int i = tid; i < R * MZH_H; i += MZH_THREADS) {
+      const int r = i >> 6, k = i & 63;
+      sm.x[r * MZH_LD64 + k] = sm.x0[r * MZH_LD64 + k];
+    }
+    if (tid < R) sm.act[tid] = a;
+    __syncthreads();
+    mzh_mlp_recurrent<R>(ms, net, wave, lane);
+    if (p.h1)
+      for (int i = tid; i < R * MZH_H; i += MZH_THREADS) {
+        const int r = i >> 6, k = i & 63;
+        const int e = sm.env[r];
+        if (e >= 0) p.h1[((size_t)e * MZH_A + a) * MZH_H + mzh_kpos(k)] = sm.x[r * MZH_LD64 + k];
+      }
+    if (tid < R * 8) {
+      const int r = tid >> 3, c = tid & 7;
+      const int e = sm.env[r];
+      if (e >= 0) {
+        if (p.pi1 && c < MZH_A) p.pi1[((size_t)e * MZH_A + a) * MZH_A + c] = sm.pi[r * 8 + c];
+        if (c == 6) p.reward[(size_t)e * MZH_A + a] = sm.reward[r];
+        if (c == 7) p.value[(size_t)e * MZH_A + a] = sm.value[r];
+      }
+    }
+    __syncthreads();  // the next action's copy overwrites sm.x
+  }
+}
+
+template <int R>
+__global__ __launch_bounds__(MZH_THREADS, 1) void mzh_probe_kernel(MzhNet net, MzhProbeParams p) {
+  mzh_probe_body<R>(net, p);
+}
+
+// Rows of several networks (a set, mzh_load_weight_set): workgroup t probes tile t of the table
+// mzh_multi_tiles_kernel made of this call's net_index; one at or above the tile count returns before its
+// first barrier (a refused net_index leaves the count 0: nothing is written)
+template <int R>
+__global__ __launch_bounds__(MZH_THREADS, 1) void mzh_probe_multi_kernel(MzhNet net, MzhProbeParams p, MzhMultiParams mp) {
+  if ((int)blockIdx.x >= *mp.ntiles) return;
+  const MzhTableTile t{mp.tiles[blockIdx.x]};
+  mzh_net_select(net, mp, t.t.net, net.support == 33);
+  mzh_probe_body<R>(net, p, t);
+}
+
+// ------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------
 template <int R, int DC = search_dc<R>()>
@@ -522,4 +628,31 @@ extern "C" int mzh_diag_stamps(unsigned long long* host) {
 
 hipError_t mzh_launch_infer(int R, bool recurrent, const MzhNet& net, const MzhInferParams& p, hipStream_t stream) {
   return R == 32 ? launch_infer_t<32>(recurrent, net, p, stream) : launch_infer_t<16>(recurrent, net, p, stream);
+}
+
+template <int R>
+static size_t probe_smem_bytes() { return (sizeof(ProbeSmem<R>) + 15) & ~(size_t)15; }
+size_t mzh_probe_smem_bytes(int R) { return R == 32 ? probe_smem_bytes<32>() : probe_smem_bytes<16>(); }
+
+template <int R>
+static hipError_t launch_probe_t(const MzhNet& net, const MzhProbeParams& p, const MzhMultiParams* mp, hipStream_t stream) {
+  const size_t smem = probe_smem_bytes<R>();
+  const void* fn = mp ? reinterpret_cast<const void*>(&mzh_probe_multi_kernel<R>)
+                      : reinterpret_cast<const void*>(&mzh_probe_kernel<R>);
+  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+  if (e != hipSuccess) return e;
+  if (!mp) {
+    hipLaunchKernelGGL((mzh_probe_kernel<R>), dim3((p.n + R - 1) / R), dim3(MZH_THREADS), smem, stream, net, p);
+    return hipGetLastError();
+  }
+  hipLaunchKernelGGL(mzh_multi_tiles_kernel, dim3(1), dim3(MZH_MULTI_MAX_NETS), 0, stream, *mp, p.n, R);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((mzh_probe_multi_kernel<R>), dim3(mzh_multi_max_tiles(p.n, R, mp->M)), dim3(MZH_THREADS), smem, stream,
+                     net, p, *mp);
+  return hipGetLastError();
+}
+
+hipError_t mzh_launch_probe(int R, const MzhNet& net, const MzhProbeParams& p, const MzhMultiParams* mp, hipStream_t stream) {
+  return R == 32 ? launch_probe_t<32>(net, p, mp, stream) : launch_probe_t<16>(net, p, mp, stream);
 }

@@ -123,6 +123,60 @@ class Engine:
                                                  self._stream()), "mzh_recurrent_inference")
         return out
 
+    def probe_actions(self, obs, *, env_index=None, state=None, net_index=None, out=None, full=False, tile=None,
+                      err=None):
+        """mzh_probe_actions: for every row the six one-step lookaheads recurrent_inference(represent(obs), a),
+        a = 0..5, in one launch (legal_illegal_preds.py:39-57).  obs [B, 3N] float32 is the full batch's; row j of
+        the call is env env_index[j] ([n] int32, distinct; None: every env, n = B); every output is indexed by env
+        and rows outside the call are left as they are.  state [B, N] uint8 adds legal [B] (mzh_legal_mask's
+        bits); net_index [n] int32 probes row j under network net_index[j] of the loaded weight set (non-decreasing).
+        out: a dict of output tensors to write into (reward / value [B, 6] float32, legal [B] uint8, and with
+        them any of h0 [B, 64], pi0 [B, 6], value0 [B], h1 [B, 6, 64], pi1 [B, 6, 6]); missing reward / value
+        (and legal with state) are allocated, the others only with full=True.  tile = None | 16 | 32.
+        Returns the dict; with net_index, "_status" is the device's [2] int32 verdict as in search_multi."""
+        dev = self.device
+        B = int(obs.shape[0])
+        checks = [("obs", obs, torch.float32, (B, 3 * self.n_disks))]
+        n = B
+        if env_index is not None:
+            n = int(env_index.shape[0])
+            checks.append(("env_index", env_index, torch.int32, (n,)))
+        if state is not None:
+            checks.append(("state", state, torch.uint8, (B, self.n_disks)))
+        if net_index is not None:
+            checks.append(("net_index", net_index, torch.int32, (n,)))
+        out = dict(out) if out is not None else {}
+        shapes = dict(reward=(B, ACTIONS), value=(B, ACTIONS), h0=(B, LATENT), pi0=(B, ACTIONS), value0=(B,),
+                      h1=(B, ACTIONS, LATENT), pi1=(B, ACTIONS, ACTIONS))
+        for k, shp in shapes.items():
+            if k not in out and (full or k in ("reward", "value")):
+                out[k] = torch.empty(shp, dtype=torch.float32, device=dev)
+            if k in out:
+                checks.append((k, out[k], torch.float32, shp))
+        if state is not None and "legal" not in out:
+            out["legal"] = torch.empty(B, dtype=torch.uint8, device=dev)
+        if "legal" in out:
+            checks.append(("legal", out["legal"], torch.uint8, (B,)))
+        for name, t, dt, shp in checks:
+            if t.dtype != dt or tuple(t.shape) != shp or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"probe_actions: {name} must be a contiguous {dt} {shp} tensor on {dev}")
+        a = _lib.ProbeArgs()
+        a.B, a.n, a.flags = B, n, search_flags(None, tile)
+        for k, t in (("env_index", env_index), ("obs", obs), ("state", state), ("err_count", err)):
+            setattr(a, k, ptr(t))
+        for k in ("reward", "value", "legal", "h0", "pi0", "value0", "h1", "pi1"):
+            setattr(a, k, ptr(out.get(k)))
+        m = None
+        if net_index is not None:
+            if getattr(self, "set_size", 0) < 1:
+                raise RuntimeError("probe_actions: no weight set loaded (load_weight_set)")
+            out["_status"] = torch.zeros(2, dtype=torch.int32, device=dev)
+            m = _lib.MultiArgs()
+            m.n_networks, m.net_index, m.status = self.set_size, ptr(net_index), ptr(out["_status"])
+        check(_lib.lib().mzh_probe_actions(self._h, ctypes.byref(a), None if m is None else ctypes.byref(m),
+                                           self._stream()), "mzh_probe_actions")
+        return out
+
     # ---------------------------------------------------------------- search
     def alloc_search_outputs(self, B, n_sims, lockstep=False):
         """lockstep=True adds lockstep_levels (zeroed, one entry per group of roots that advance together: at most

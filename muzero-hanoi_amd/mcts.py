@@ -70,6 +70,14 @@ class RecordedNetwork:
         self.cursor += 1
         return c
 
+    def last_probe(self):
+        """the action probe recorded with the call next_call() returned last (optional key "probe": reward [6],
+        value [6] float32 -- recurrent_inference(represent(obs), a) for a = 0..5, legal_illegal_preds.py:39-50)"""
+        call = self.calls[self.cursor - 1]
+        if "probe" not in call:
+            raise KeyError("RecordedNetwork: the recording holds no action probe for this call")
+        return call["probe"]
+
     def next_replay(self, device):
         """next_call() as Engine.search's `replay` tensors: fp32 [1, ...] on `device`"""
         call = self.next_call()

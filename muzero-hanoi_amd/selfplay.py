@@ -685,3 +685,96 @@ def evaluate_perturbed(networks, n_disks, *, conditions, starts=None, start_idx=
     rate, importance = perturbed_scores(got["solved"], len(nset), conditions)
     return dict(solve_rate=rate, importance=importance, **got, net_index=lay["net_index"],
                 cond_index=lay["cond_index"], start_idx=lay["start_idx"])
+
+
+# ------------------------------------------------------------------------------------------------
+# predicted reward / value of legal versus illegal moves (legal_illegal_preds.py)
+# ------------------------------------------------------------------------------------------------
+def evaluate_legality(networks, n_disks, *, episodes=100, n_sims=25, max_steps=200, seed=0, starts=None,
+                      start_idx=None, goal_peg=2, legacy_rng=False, record=False):
+    """legal_illegal_preds.py (main: evaluate_network for the base, the policy-ablated and the value-ablated
+    network) as one batch of len(networks) * episodes envs: network m's episodes consecutive, every network given
+    the same starts (starts = state tuples, or start_idx = state indices, or `episodes` random non-goal states of
+    `seed`).  Searches as the script runs them: 25 simulations, temperature 0.0, deterministic=False, at most 200
+    steps.  Per move: one search over the unfinished rows (mzh_search_multi; mzh_search with one network), one
+    mzh_probe_actions on the same rows into slot t of a device record (reward / value [T][B][6], legal [T][B]),
+    one env step and one host read of the done flags.  The record is read once at the end and scored by
+    acting.legality_summary, the drop-in's own statistics.
+    Every episode is its own agent with a fresh MinMaxStats (the script carries one MCTS instance through a
+    network's episodes: acting.legality_evaluate_network is that schedule).  Episode e of every network takes
+    row e of a move's synthetic draws, so a network's result does not depend on which other networks share the
+    batch; legacy_rng=True draws from NumPy's global stream instead, in env order over the unfinished rows (the
+    reference's order when the batch is one env).
+    networks: one network, a sequence of networks or a networks.NetworkSet.  Returns a list with, per network,
+    evaluate_network's dict plus steps [E]; record=True adds the network's slice of the record: reward / value
+    [T][E][6], legal [T][E], action [T][E] (-1 after the episode's end)."""
+    from .acting import legality_summary  # acting imports this module
+
+    if isinstance(networks, NetworkSet):
+        nets = list(networks.nets)
+    else:
+        nets = list(networks) if isinstance(networks, (list, tuple)) else [networks]
+    M = len(nets)
+    if M < 1:
+        raise ValueError("evaluate_legality: no networks")
+    if starts is not None:
+        start_idx = [state_index(s) for s in starts]
+    elif start_idx is None:
+        if int(episodes) < 1:
+            raise ValueError("evaluate_legality: no starts (give starts, start_idx or episodes >= 1)")
+        start_idx = _batch_starts(n_disks, int(episodes), None, None, seed, goal_peg)
+    start_idx = np.asarray(start_idx, np.int64).reshape(-1)
+    E = int(start_idx.shape[0])
+    if E < 1 or start_idx.min() < 0 or start_idx.max() >= 3 ** n_disks:
+        raise ValueError(f"evaluate_legality: starts must be state indices in [0, {3 ** n_disks}), at least one")
+    if int(max_steps) < 1:
+        raise ValueError(f"evaluate_legality: max_steps must be >= 1, got {max_steps}")
+    multi = M > 1
+    nset = (networks if isinstance(networks, NetworkSet) else NetworkSet(nets)) if multi else None
+    if (nset.in_dim if multi else nets[0].representation_net[0].in_features) != 3 * n_disks:
+        raise ValueError(f"evaluate_legality: the networks do not read {3 * n_disks} inputs (n_disks={n_disks})")
+    B, T, S = M * E, int(max_steps), int(n_sims)
+    sp = BatchedSelfPlay(nset if multi else nets[0], n_disks, T, S, goal_peg=goal_peg)
+    net_index = np.repeat(np.arange(M), E) if multi else None
+    _, eng, _, env, _, gen, mm = sp._setup(np.tile(start_idx, M), None, seed, net_index)
+    dev = eng.device
+    episode_of = torch.arange(B, device=dev) % E  # the row of a move's draws an env takes
+    rec_r = torch.zeros((T, B, 6), dtype=torch.float32, device=dev)
+    rec_v = torch.zeros((T, B, 6), dtype=torch.float32, device=dev)
+    rec_l = torch.zeros((T, B), dtype=torch.uint8, device=dev)
+    rec_a = torch.full((T, B), -1, dtype=torch.int32, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    env._tallies()  # last_obs: the starts' observations
+    n, idx, t = B, torch.arange(B, device=dev), 0
+    while n:
+        if legacy_rng:
+            draws = sp._draws(n, False, True, gen)
+        else:
+            rows = episode_of.index_select(0, idx)
+            draws = [None if x is None else torch.as_tensor(x).to(dev).index_select(0, rows)
+                     for x in sp._draws(E, False, False, gen)]
+        out = sp._search(eng, False, env.last_obs.index_select(0, idx), idx, draws, mm, 0.0, False)
+        idx32 = idx.to(torch.int32)
+        eng.probe_actions(env.last_obs, env_index=idx32, state=env.state, err=err,
+                          net_index=sp._net_index.index_select(0, idx) if multi else None,
+                          out=dict(reward=rec_r[t], value=rec_v[t], legal=rec_l[t]))
+        rec_a[t].index_copy_(0, idx, out["action"])
+        env.step_observe(out["action"], idx32)
+        # the move's one host read: how many envs are still playing, and the kernels' error counts
+        left, e1, e2 = (int(x) for x in torch.stack([env.active.sum(dtype=torch.int32), env.err[0], err[0]]).cpu())
+        if e1 or e2:
+            raise RuntimeError(f"evaluate_legality: the env step reported {e1} and the probe {e2} error(s)")
+        n, t = left, t + 1
+        idx = torch.sort(env.active, descending=True, stable=True).indices[:n]
+    steps = env.steps_total.cpu().numpy()
+    reward, value, legal, action = (x[:t].cpu().numpy() for x in (rec_r, rec_v, rec_l, rec_a))
+    res = []
+    for m in range(M):
+        sl = slice(m * E, (m + 1) * E)
+        d = legality_summary(reward[:, sl], value[:, sl], legal[:, sl], steps[sl])
+        d["steps"] = steps[sl].copy()
+        if record:
+            d.update(reward=reward[:, sl].copy(), value=value[:, sl].copy(), legal=legal[:, sl].copy(),
+                     action=action[:, sl].copy())
+        res.append(d)
+    return res
