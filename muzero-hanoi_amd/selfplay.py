@@ -3,14 +3,19 @@
 play_game          Muzero._play_game (Muzero.py:153-207) for one env through the drop-ins: the
                    reference's control flow, RNG consumption and episode bookkeeping, every search
                    and every env step on the GPU.
-BatchedSelfPlay    B envs resident on the GPU (HanoiBatch) stepping with search-chosen actions:
-                   one mzh_search launch + one mzh_env_step launch per step for all unfinished
-                   envs.  Each env is one agent with its own MCTS instance: its MinMaxStats
-                   (MCTS/mcts.py:23, never reset) is carried from decision to decision
-                   (minmax_out -> minmax_in), starting from the `minmax` handed in.
-                   play_plans is the plan-ahead form (acting_experiments/planning_multiple_actions.py):
-                   a search's latent path executed open loop by one mzh_env_run_plan launch, the next
-                   search only for the envs whose plan ran out.
+BatchedSelfPlay    B envs resident on the GPU (HanoiBatch) stepping with search-chosen actions.  Each env
+                   is one agent with its own MCTS instance: its MinMaxStats (MCTS/mcts.py:23, never
+                   reset) is carried from decision to decision (minmax_out -> minmax_in), starting from
+                   the `minmax` handed in.  Every form runs on one lockstep move loop (_Lockstep: the
+                   unfinished rows, their draws, the search with the MinMaxStats carry, the move's one
+                   host read) and differs in what it does between a search and that read:
+                   play            one mzh_search + one mzh_env_step_observe launch per move on the
+                                   full-batch env arrays through env_index; records every move.
+                   play_plans      the plan-ahead form (acting_experiments/planning_multiple_actions.py):
+                                   a search's latent path executed open loop by one mzh_env_run_plan
+                                   launch, the next search only for the envs whose plan ran out.
+                   play_perturbed  searches on noisy / disc-permuted observations of the true envs.
+                   play_probed     play plus one mzh_probe_actions launch per move (evaluate_legality).
 episode_records    the reference's per-episode bookkeeping (returns, priorities,
                    organise_transitions) of every env of a BatchedSelfPlay run.
 ingest_records     that bookkeeping, the success filter and Buffer.add for every env in one device call
@@ -35,7 +40,6 @@ import numpy as np
 import torch
 
 from . import rng as _rng
-from .engine import env_step as _env_step
 from .engine import hanoi_solver_batch
 from .env import HanoiBatch
 from .mcts import RecordedNetwork, _replay_engine
@@ -110,6 +114,119 @@ def _bookkeeping(episode_state, episode_rwd, episode_action, episode_piProb, epi
     return episode_returns, priorities, trans
 
 
+class _Lockstep:
+    """One lockstep run of a BatchedSelfPlay: B envs reset to their starts, one agent (MinMaxStats) each, and
+    the rows that are still playing.  A form of play is a loop body on it:
+
+        run = _Lockstep(sp, start_idx, ...)
+        while run.n:
+            out = run.search()      # the rows run.idx, their MinMaxStats carried in run.mm
+            ...                     # act on run.env through env_index=run.idx32
+            run.advance(kernel)     # the move's one host read; the next run.idx / run.n
+
+    eng: the engine; env: the HanoiBatch, its last_obs the starts' observations; mm [B, 2]; net_index [B] int32 on
+    the device with a NetworkSet, else None; start [B] int64 on the device; idx (int64) / idx32 / n: the
+    unfinished rows in env order and their count; draw_index [B] on the device or None (rows)."""
+
+    def __init__(self, sp, start_idx, minmax, seed, net_index, temperature, deterministic, legacy_rng=False,
+                 draw_index=None):
+        start = torch.as_tensor(np.asarray(start_idx), dtype=torch.int64).reshape(-1)
+        B = int(start.shape[0])
+        self.sp, self.temperature, self.deterministic, self.legacy_rng = sp, temperature, deterministic, legacy_rng
+        self.replay = isinstance(sp.network, RecordedNetwork)
+        if self.replay and B != 1:
+            raise ValueError("a RecordedNetwork replays one sequential stream of searches: B must be 1")
+        multi = isinstance(sp.network, NetworkSet)
+        if multi != (net_index is not None):
+            raise ValueError("net_index [B] is required with a NetworkSet and only accepted with one")
+        if multi:
+            ni = np.asarray(net_index, np.int64).reshape(-1)
+            if ni.shape[0] != B or (B and (ni.min() < 0 or ni.max() >= len(sp.network) or np.any(np.diff(ni) < 0))):
+                raise ValueError(f"net_index must be {B} non-decreasing indices into the set of {len(sp.network)}")
+            self.eng = engine_for_set(sp.network, sp.S, B)
+        else:
+            self.eng = _replay_engine(sp.N, sp.S) if self.replay else engine_for(sp.network, sp.S, B)
+        dev = self.eng.device
+        self.net_index = torch.as_tensor(ni, dtype=torch.int32).to(dev) if multi else None
+        # with the legacy stream a move's draws are those of its unfinished rows in env order, whatever draw_index
+        self.draw_index, self.n_draw = None, B
+        if draw_index is not None and not legacy_rng:
+            di = np.asarray(draw_index, np.int64).reshape(-1)
+            if di.shape[0] != B or di.min() < 0:
+                raise ValueError(f"draw_index must be {B} non-negative rows")
+            self.draw_index, self.n_draw = torch.from_numpy(di).to(dev), int(di.max()) + 1
+        self.env = HanoiBatch(sp.N, sp.max_steps, B, goal_peg=sp.goal_peg, device=dev)
+        self.start = start.to(dev)
+        self.env.reset(self.start)
+        self.env._tallies()  # the first observations (env.last_obs) and the per-env counts
+        self.mm = torch.empty((B, 2), dtype=torch.float64, device=dev)
+        if minmax is None:
+            self.mm[:, 0], self.mm[:, 1] = -float("inf"), float("inf")
+        else:
+            self.mm.copy_(torch.as_tensor(np.asarray(minmax, np.float64)).reshape(B, 2))
+        self.gen = np.random.default_rng(seed)  # of the synthetic draws' seeds
+        self._pre = None
+        self._unfinished(torch.arange(B, device=dev))
+
+    def _unfinished(self, idx):
+        self.idx, self.idx32, self.n = idx, idx.to(torch.int32), int(idx.shape[0])
+        if self.draw_index is None:
+            self.n_draw = self.n
+
+    def _draw(self):
+        """a move's draws, n_draw rows: the global NumPy stream, or synthetic ones seeded from gen"""
+        kw = dict(deterministic=self.deterministic, alpha=self.sp.alpha, eps=self.sp.eps)
+        if self.legacy_rng:
+            return _rng.predraw(self.n_draw, **kw)
+        return _rng.synthetic_draws(self.n_draw, seed=int(self.gen.integers(2**31)), **kw)
+
+    def rows(self, x):
+        """the rows of a draw x (None passes through) for the rows idx, on their device: the first n, or, with
+        draw_index, x[draw_index[idx]] of a draw of max(draw_index) + 1 rows"""
+        if x is None:
+            return None
+        x = torch.as_tensor(x).to(self.idx.device)
+        return x[:self.n] if self.draw_index is None else x.index_select(0, self.draw_index.index_select(0, self.idx))
+
+    def search(self):
+        """one search over the rows idx from env.last_obs (a RecordedNetwork: its next recorded call), their
+        MinMaxStats read from and carried into mm.  Returns the search's dict, plus obs: the rows searched."""
+        sp, idx = self.sp, self.idx
+        draws, self._pre = self._draw() if self._pre is None else self._pre, None
+        noise, tie, u = (self.rows(x) for x in draws)
+        obs = self.env.last_obs.index_select(0, idx)
+        kw = dict(tie_idx=tie, noise=noise, action_u=u, minmax_in=self.mm.index_select(0, idx),
+                  temperature=float(self.temperature), deterministic=bool(self.deterministic), discount=sp.discount,
+                  eps=sp.eps, np1_ucb=sp.np1_ucb)
+        if self.net_index is not None:  # a NetworkSet: idx is increasing, so the networks' envs stay consecutive
+            out = self.eng.search_multi(sp.S, net_index=self.net_index.index_select(0, idx), obs=obs, **kw)
+        elif self.replay:
+            out = self.eng.search(sp.S, replay=sp.network.next_replay(self.eng.device), **kw)
+        else:
+            out = self.eng.search(sp.S, obs=obs, **kw)
+        self.mm.index_copy_(0, idx, out["minmax"])
+        out["obs"] = obs
+        return out
+
+    def advance(self, kernel, **extra_err):
+        """The move's single host read: the unfinished envs left, env.err (the errors `kernel`, the move's env
+        launch, counted) and extra_err (kernel name = its [1] int32 error counter).  RuntimeError naming the
+        kernel if a counter is not zero.  Sets the next idx / n.
+        Synthetic draws: the next move's are made here, on the host while the GPU still runs this move, for this
+        move's count of rows (an upper bound); `rows` cuts them to the count left (the draws of n rows are the
+        first n rows of a larger draw, rng.synthetic_draws).  Legacy-stream draws wait for the count."""
+        if not self.legacy_rng and not self.replay:
+            self._pre = self._draw()
+        errs = {kernel: self.env.err, **extra_err}
+        left, *counts = (int(x) for x in torch.stack([self.env.active.sum(dtype=torch.int32)]
+                                                     + [e[0] for e in errs.values()]).cpu())
+        bad = [f"{k} reported {c} error(s)" for k, c in zip(errs, counts) if c]
+        if bad:
+            raise RuntimeError("; ".join(bad))
+        # the unfinished envs in env order, without another host read (their count is known)
+        self._unfinished(torch.sort(self.env.active, descending=True, stable=True).indices[:left])
+
+
 class BatchedSelfPlay:
     """B independent agents in lockstep on one GPU, one MCTS instance (MinMaxStats) each.
 
@@ -124,120 +241,39 @@ class BatchedSelfPlay:
         self.discount, self.alpha, self.eps, self.goal_peg = discount, dirichlet_alpha, root_exploration_eps, goal_peg
         self.np1_ucb = np1_ucb
 
-    def _setup(self, start_idx, minmax, seed, net_index=None):
-        """-> start [B] int64, the engine, whether it replays a RecordedNetwork, the envs reset to the starts and
-        their observations, the generator of the synthetic draws' seeds, and the agents' MinMaxStats [B, 2] (default: fresh)"""
-        start = torch.as_tensor(np.asarray(start_idx), dtype=torch.int64).reshape(-1)
-        B = int(start.shape[0])
-        replay = isinstance(self.network, RecordedNetwork)
-        if replay and B != 1:
-            raise ValueError("a RecordedNetwork replays one sequential stream of searches: B must be 1")
-        multi = isinstance(self.network, NetworkSet)
-        if multi != (net_index is not None):
-            raise ValueError("net_index [B] is required with a NetworkSet and only accepted with one")
-        if multi:
-            ni = np.asarray(net_index, np.int64).reshape(-1)
-            if ni.shape[0] != B or (B and (ni.min() < 0 or ni.max() >= len(self.network) or np.any(np.diff(ni) < 0))):
-                raise ValueError(f"net_index must be {B} non-decreasing indices into the set of {len(self.network)}")
-            eng = engine_for_set(self.network, self.S, B)
-            self._net_index = torch.as_tensor(ni, dtype=torch.int32).to(eng.device)
-        else:
-            eng = _replay_engine(self.N, self.S) if replay else engine_for(self.network, self.S, B)
-            self._net_index = None
-        dev = eng.device
-        env = HanoiBatch(self.N, self.max_steps, B, goal_peg=self.goal_peg, device=dev)
-        obs = env.reset(start.to(dev))
-        mm = torch.empty((B, 2), dtype=torch.float64, device=dev)
-        if minmax is None:
-            mm[:, 0], mm[:, 1] = -float("inf"), float("inf")
-        else:
-            mm.copy_(torch.as_tensor(np.asarray(minmax, np.float64)).reshape(B, 2))
-        return start, eng, replay, env, obs, np.random.default_rng(seed), mm
-
-    def _draws(self, n, deterministic, legacy_rng, gen):
-        """a round's draws for n envs: the global NumPy stream, or synthetic ones seeded from `gen`"""
-        if legacy_rng:
-            return _rng.predraw(n, deterministic=deterministic, alpha=self.alpha, eps=self.eps)
-        return _rng.synthetic_draws(n, deterministic=deterministic, alpha=self.alpha, eps=self.eps,
-                                    seed=int(gen.integers(2**31)))
-
-    def _search(self, eng, replay, obs, idx, draws, mm, temperature, deterministic):
-        """one search over the envs `idx` (obs: their observations; or the RecordedNetwork's next call), their
-        MinMaxStats read from and carried into mm [B, 2]"""
-        noise, tie, u = (None if x is None else torch.as_tensor(x).to(eng.device) for x in draws)
-        kw = dict(tie_idx=tie, noise=noise, action_u=u, minmax_in=mm.index_select(0, idx),
-                  temperature=float(temperature), deterministic=bool(deterministic), discount=self.discount,
-                  eps=self.eps, np1_ucb=self.np1_ucb)
-        if self._net_index is not None:  # a NetworkSet: idx is increasing, so the networks' envs stay consecutive
-            out = eng.search_multi(self.S, net_index=self._net_index.index_select(0, idx), obs=obs, **kw)
-        else:
-            out = eng.search(self.S, obs=None if replay else obs,
-                             replay=self.network.next_replay(eng.device) if replay else None, **kw)
-        mm.index_copy_(0, idx, out["minmax"])
-        return out
-
     def play(self, start_idx, temperature=1.0, deterministic=False, seed=0, legacy_rng=False, minmax=None,
              record_obs=False, net_index=None):
         """Play every env from start_idx[b] until done (goal or max_steps).
 
         minmax: [B, 2] (maximum, minimum) of each agent's MinMaxStats at the start (default: fresh,
         -inf / +inf); the final values come back as res["minmax"].  net_index: [B] with a NetworkSet (the
-        class docstring), else None.  Returns device tensors:
+        class docstring), else None.  Per move: one search over the unfinished envs, one mzh_env_step_observe
+        launch through env_index, one host read (_Lockstep.advance).  Returns device tensors:
         per step t (rows of envs that were still playing): action, reward, pi, root_q, active,
-        obs (record_obs); per env: steps, illegal (count), start_idx, minmax."""
-        start, eng, replay, env, obs, gen, mm = self._setup(start_idx, minmax, seed, net_index)
-        B, dev = int(start.shape[0]), eng.device
-        active = torch.ones(B, dtype=torch.bool, device=dev)
-        steps = torch.zeros(B, dtype=torch.int32, device=dev)
-        illegal_n = torch.zeros(B, dtype=torch.int32, device=dev)
+        obs (record_obs: the observation searched); per env: steps, illegal (count), start_idx, minmax.
+        An empty start_idx plays nothing: no launch, empty records.  RuntimeError if the env kernel counted an
+        error, which a search's own actions cannot cause."""
+        run = _Lockstep(self, start_idx, minmax, seed, net_index, temperature, deterministic, legacy_rng)
+        env, B, dev = run.env, run.env.B, run.eng.device
         rec = dict(action=[], reward=[], pi=[], root_q=[], active=[])
         if record_obs:
             rec["obs"] = []
-        # synthetic draws: a move's batch is drawn on the host while the GPU still runs the previous move, for
-        # that move's count of envs (an upper bound), and cut to the count left once it is known (the draws
-        # of n envs are the first n rows of a larger draw, rng.synthetic_draws)
-        pre = None
-        while True:
-            idx = active.nonzero().squeeze(1)
-            n = int(idx.numel())
-            if n == 0:
-                break
-            draws = self._draws(n, deterministic, legacy_rng, gen) if pre is None else pre
-            pre = None
-            sub_obs_in = obs.index_select(0, idx)
-            out = self._search(eng, replay, sub_obs_in, idx, [None if x is None else x[:n] for x in draws], mm,
-                               temperature, deterministic)
-            # step only the unfinished envs (gather -> one env kernel -> scatter)
-            sub_state = env.state.index_select(0, idx).contiguous()
-            sub_ctr = env.step_ctr.index_select(0, idx).contiguous()
-            sub_act = env.active.index_select(0, idx).contiguous()
-            sub_obs = torch.empty((n, 3 * self.N), dtype=torch.float32, device=dev)
-            code, done, ill = _env_step(self.N, self.max_steps, sub_state, out["action"], sub_ctr, sub_act,
-                                        goal_peg=self.goal_peg, obs=sub_obs, err=env.err)
-            env.state.index_copy_(0, idx, sub_state)
-            env.step_ctr.index_copy_(0, idx, sub_ctr)
-            env.active.index_copy_(0, idx, sub_act)
-            steps.index_add_(0, idx, torch.ones_like(idx, dtype=torch.int32))
-            illegal_n.index_add_(0, idx, ill.to(torch.int32))
+        while run.n:
+            idx = run.idx
+            out = run.search()
+            r = env.step_observe(out["action"], run.idx32)
             full = lambda v, fill, dt: torch.full((B,) + tuple(v.shape[1:]), fill, dtype=dt, device=dev).index_copy(
                 0, idx, v.to(dt))
             rec["action"].append(full(out["action"], -1, torch.int32))
-            rec["reward"].append(full(HanoiBatch.reward_value(code), 0.0, torch.float64))
+            rec["reward"].append(full(HanoiBatch.reward_value(r["reward"]), 0.0, torch.float64))
             rec["pi"].append(full(out["pi"], 0.0, torch.float64))
             rec["root_q"].append(full(out["root_q"], 0.0, torch.float64))
-            rec["active"].append(active.clone())
+            rec["active"].append(torch.zeros(B, dtype=torch.bool, device=dev).index_fill(0, idx, True))
             if record_obs:
-                rec["obs"].append(full(sub_obs_in, 0.0, torch.float32))
-            obs = obs.index_copy(0, idx, sub_obs)
-            active = active.index_copy(0, idx, done == 0)
-            if not legacy_rng and not replay:  # the next move's draws, overlapping this move's kernels
-                pre = self._draws(n, deterministic, False, gen)
+                rec["obs"].append(full(out["obs"], 0.0, torch.float32))
+            run.advance("mzh_env_step_observe (an action outside 0..5)")
         res = {k: torch.stack(v) if v else torch.empty(0, device=dev) for k, v in rec.items()}
-        res["steps"] = steps
-        res["illegal"] = illegal_n
-        res["start_idx"] = start.to(dev)
-        res["minmax"] = mm
-        return res
+        return dict(res, steps=env.steps_total, illegal=env.illegal_total, start_idx=run.start, minmax=run.mm)
 
     def play_plans(self, start_idx, max_plan_len, temperature=1.0, deterministic=False, seed=0, legacy_rng=False,
                    minmax=None, net_index=None):
@@ -260,19 +296,15 @@ class BatchedSelfPlay:
             raise ValueError("play_plans: a plan needs n_simulations >= 1")
         if np.asarray(start_idx).size < 1:
             raise ValueError("play_plans: no start states")
-        start, eng, replay, env, _, gen, mm = self._setup(start_idx, minmax, seed, net_index)
-        B, dev = int(start.shape[0]), eng.device
+        run = _Lockstep(self, start_idx, minmax, seed, net_index, temperature, deterministic, legacy_rng)
+        env, B, dev = run.env, run.env.B, run.eng.device
         plans = torch.zeros(B, dtype=torch.int32, device=dev)
         rec = dict(action=[], reward=[], root_q=[], search_action=[])
-        n, idx = B, torch.arange(B, device=dev)
-        while n:
-            draws = self._draws(n, deterministic, legacy_rng, gen)
-            # the observation env.step returned last (the start's before the first plan): HanoiBatch.last_obs
-            obs = env.obs() if env.last_obs is None else env.last_obs
-            out = self._search(eng, replay, obs.index_select(0, idx), idx, draws, mm, temperature, deterministic)
+        while run.n:
+            idx = run.idx
+            out = run.search()
             # a path has at most S + 1 moves (the row stride of `latent`): a longer max_plan_len cuts nothing more
-            r = env.run_plan(out["latent"], out["latent_len"], min(L, self.S + 1), env_index=idx.to(torch.int32),
-                             record=True)
+            r = env.run_plan(out["latent"], out["latent_len"], min(L, self.S + 1), env_index=run.idx32, record=True)
             plans.index_add_(0, idx, torch.ones_like(idx, dtype=torch.int32))
             full = lambda v, fill: torch.full(tuple(v.shape[:-1]) + (B,), fill, dtype=v.dtype, device=dev).index_copy(
                 v.dim() - 1, idx, v)
@@ -282,22 +314,10 @@ class BatchedSelfPlay:
             rec["reward"].append(pad(full(r["reward"], 0), 0))
             rec["root_q"].append(full(out["root_q"], 0.0))
             rec["search_action"].append(full(out["action"], -1))
-            # the round's one host read: how many envs still need a plan, and the kernel's error count
-            left, err = (int(x) for x in torch.stack([env.active.sum(dtype=torch.int32), env.err[0]]).cpu())
-            if err:
-                raise RuntimeError(f"mzh_env_run_plan reported {err} error(s): a search returned an empty path or "
-                                   "an action outside 0..5")
-            n = left
-            # the unfinished envs in env order, without another host read (their count is known)
-            idx = torch.sort(env.active, descending=True, stable=True).indices[:n]
+            run.advance("mzh_env_run_plan (a search returned an empty path or an action outside 0..5)")
         res = {k: torch.stack(v) for k, v in rec.items()}
-        res["steps"] = env.steps_total
-        res["illegal"] = env.illegal_total
-        res["plans"] = plans
-        res["start_idx"] = start.to(dev)
-        res["minmax"] = mm
-        return res
-
+        return dict(res, steps=env.steps_total, illegal=env.illegal_total, plans=plans, start_idx=run.start,
+                    minmax=run.mm)
 
     def play_perturbed(self, start_idx, *, noise_std=None, permute_disc=None, temperature=0.0, deterministic=True,
                        seed=0, minmax=None, net_index=None, draw_index=None):
@@ -324,52 +344,56 @@ class BatchedSelfPlay:
             raise ValueError("play_perturbed: a RecordedNetwork replays recorded observations; use the acting drop-ins")
         if np.asarray(start_idx).size < 1:
             raise ValueError("play_perturbed: no start states")
-        start, eng, _, env, _, gen, mm = self._setup(start_idx, minmax, seed, net_index)
-        B, dev, no = int(start.shape[0]), eng.device, 3 * self.N
-        std, disc = perturbation_arrays(B, self.N, noise_std, permute_disc)
+        run = _Lockstep(self, start_idx, minmax, seed, net_index, temperature, deterministic, draw_index=draw_index)
+        env, dev = run.env, run.eng.device
+        std, disc = perturbation_arrays(env.B, self.N, noise_std, permute_disc)
         pgen = _rng.perturbation_seeds(seed)
         std_dev = None if std is None else torch.from_numpy(std).to(dev)[:, None]
         env.set_perturbation(disc)
-        rows_of, total = None, None
-        if draw_index is not None:
-            di = np.asarray(draw_index, np.int64).reshape(-1)
-            if di.shape[0] != B or di.min() < 0:
-                raise ValueError(f"play_perturbed: draw_index must be {B} non-negative rows")
-            rows_of, total = torch.from_numpy(di).to(dev), int(di.max()) + 1
 
-        def take(x, idx, n):
-            """a draw's rows for the envs idx: the first n, or the envs' own rows of a draw of `total`"""
-            if x is None:
-                return None
-            x = torch.as_tensor(x).to(dev)
-            return x[:n] if rows_of is None else x.index_select(0, rows_of.index_select(0, idx))
-
-        def perturbation(idx, n):
+        def perturbation():
             if std is None and disc is None:
                 return None, None
-            peg, z = _rng.perturbation_draws(n if total is None else total, no, int(pgen.integers(2**31)))
-            peg = None if disc is None else take(peg, idx, n).contiguous()
-            noise = None if std is None else (std_dev.index_select(0, idx) * take(z, idx, n)).contiguous()
+            peg, z = _rng.perturbation_draws(run.n_draw, 3 * self.N, int(pgen.integers(2**31)))
+            peg = None if disc is None else run.rows(peg).contiguous()
+            noise = None if std is None else (std_dev.index_select(0, run.idx) * run.rows(z)).contiguous()
             return peg, noise
 
-        n, idx = B, torch.arange(B, device=dev)
-        peg, noise = perturbation(idx, n)
-        env.step_observe(None, perm_peg=peg, noise=noise)  # the first observations
-        while n:
-            draws = self._draws(n if total is None else total, deterministic, False, gen)
-            out = self._search(eng, False, env.last_obs.index_select(0, idx), idx, [take(x, idx, n) for x in draws], mm,
-                               temperature, deterministic)
-            peg, noise = perturbation(idx, n)
-            env.step_observe(out["action"], idx.to(torch.int32), perm_peg=peg, noise=noise)
-            # the move's one host read: how many envs are still playing, and the kernel's error count
-            left, err = (int(x) for x in torch.stack([env.active.sum(dtype=torch.int32), env.err[0]]).cpu())
-            if err:
-                raise RuntimeError(f"mzh_env_step_observe reported {err} error(s): an action outside 0..5 or a "
-                                   "perturbation outside its range")
-            n = left
-            idx = torch.sort(env.active, descending=True, stable=True).indices[:n]
-        return dict(steps=env.steps_total, illegal=env.illegal_total, solved=env.solved, start_idx=start.to(dev),
-                    minmax=mm)
+        peg, noise = perturbation()
+        env.step_observe(None, perm_peg=peg, noise=noise)  # the first observations, perturbed
+        while run.n:
+            out = run.search()
+            peg, noise = perturbation()
+            env.step_observe(out["action"], run.idx32, perm_peg=peg, noise=noise)
+            run.advance("mzh_env_step_observe (an action outside 0..5 or a perturbation outside its range)")
+        return dict(steps=env.steps_total, illegal=env.illegal_total, solved=env.solved, start_idx=run.start,
+                    minmax=run.mm)
+
+    def play_probed(self, start_idx, *, seed=0, legacy_rng=False, net_index=None, draw_index=None):
+        """evaluate_legality's episodes: `play` at temperature 0.0, deterministic=False, every agent fresh, with
+        one mzh_probe_actions launch per move on the rows that are searched, into slot t of a device record of
+        max_steps slots.  draw_index: as in play_perturbed (not used with legacy_rng, which draws for the
+        unfinished rows in env order).  Returns device tensors: reward / value [T][B][6] float32 and legal [T][B]
+        uint8 (zeros after an episode's end), action [T][B] int32 (-1 after it), T the moves played, and
+        steps [B]."""
+        run = _Lockstep(self, start_idx, None, seed, net_index, 0.0, False, legacy_rng, draw_index)
+        env, B, dev, T = run.env, run.env.B, run.eng.device, self.max_steps
+        rec_r = torch.zeros((T, B, 6), dtype=torch.float32, device=dev)
+        rec_v = torch.zeros((T, B, 6), dtype=torch.float32, device=dev)
+        rec_l = torch.zeros((T, B), dtype=torch.uint8, device=dev)
+        rec_a = torch.full((T, B), -1, dtype=torch.int32, device=dev)
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+        t = 0
+        while run.n:
+            out = run.search()
+            run.eng.probe_actions(env.last_obs, env_index=run.idx32, state=env.state, err=err,
+                                  net_index=None if run.net_index is None else run.net_index.index_select(0, run.idx),
+                                  out=dict(reward=rec_r[t], value=rec_v[t], legal=rec_l[t]))
+            rec_a[t].index_copy_(0, run.idx, out["action"])
+            env.step_observe(out["action"], run.idx32)
+            run.advance("mzh_env_step_observe", mzh_probe_actions=err)
+            t += 1
+        return dict(reward=rec_r[:t], value=rec_v[:t], legal=rec_l[:t], action=rec_a[:t], steps=env.steps_total)
 
 
 def perturbation_arrays(B, n_disks, noise_std, permute_disc):
@@ -474,11 +498,7 @@ def evaluate(network, n_disks, n_sims_range, *, episodes=1, start=None, start_id
     moves, is executed open loop and the next search runs only when it ran out; every budget must be >= 1.
     `illegal` then counts the executed illegal moves.
     dirichlet_alpha: the agents' root_dirichlet_alpha (0: no root noise, the plan-ahead script's setting)."""
-    if max_plan_len is not None:
-        if int(max_plan_len) != max_plan_len or int(max_plan_len) < 1:
-            raise ValueError(f"evaluate: max_plan_len must be an integer >= 1, got {max_plan_len}")
-        if any(int(n) < 1 for n in n_sims_range):
-            raise ValueError("evaluate: a plan needs n_simulations >= 1 in every budget")
+    _check_plan("evaluate", max_plan_len, n_sims_range)
     if not sequential and minmax is not None:
         raise ValueError("evaluate: minmax applies to the sequential schedule only (batched agents start fresh)")
     legacy_rng = sequential if legacy_rng is None else legacy_rng
@@ -511,6 +531,41 @@ def evaluate(network, n_disks, n_sims_range, *, episodes=1, start=None, start_id
             steps, ill = res["steps"].cpu().numpy(), res["illegal"].cpu().numpy()
         _score_budget(score, int(n), n_disks, goal_peg, starts, steps, ill)
     return dict(**score, minmax=mm if sequential else None)
+
+
+def _check_plan(who, max_plan_len, n_sims_range):
+    """max_plan_len: None, or an integer >= 1 with every budget >= 1 (a plan is a search's path)"""
+    if max_plan_len is None:
+        return
+    if int(max_plan_len) != max_plan_len or int(max_plan_len) < 1:
+        raise ValueError(f"{who}: max_plan_len must be an integer >= 1, got {max_plan_len}")
+    if any(int(n) < 1 for n in n_sims_range):
+        raise ValueError(f"{who}: a plan needs n_simulations >= 1 in every budget")
+
+
+def _network_set(who, networks):
+    """one network, a sequence of networks or a networks.NetworkSet -> a NetworkSet"""
+    if isinstance(networks, NetworkSet):
+        return networks
+    nets = list(networks) if isinstance(networks, (list, tuple)) else [networks]
+    if not nets:
+        raise ValueError(f"{who}: no networks")
+    return NetworkSet(nets)
+
+
+def _start_indices(who, n_disks, starts, start_idx, episodes, seed, goal_peg):
+    """starts (state tuples), else start_idx (state indices), else `episodes` random non-goal states of `seed`
+    -> int64 [E] state indices, at least one and each in [0, 3^n_disks)"""
+    if starts is not None:
+        start_idx = [state_index(s) for s in starts]
+    elif start_idx is None:
+        if episodes is None or int(episodes) < 1:
+            raise ValueError(f"{who}: no starts (give starts, start_idx or episodes >= 1)")
+        start_idx = _batch_starts(n_disks, int(episodes), None, None, seed, goal_peg)
+    start_idx = np.asarray(start_idx, np.int64).reshape(-1)
+    if start_idx.size < 1 or start_idx.min() < 0 or start_idx.max() >= 3 ** n_disks:
+        raise ValueError(f"{who}: starts must be state indices in [0, {3 ** n_disks}), at least one")
+    return start_idx
 
 
 def _new_score():
@@ -557,12 +612,8 @@ def evaluate_networks(networks, n_disks, n_sims_range, *, episodes=1, start=None
     would give network m's episode alone).
     networks: a networks.NetworkSet or a sequence of networks.  Returns a list with, per network, the dict
     evaluate returns (minmax None), scored by the same code."""
-    nset = networks if isinstance(networks, NetworkSet) else NetworkSet(networks)
-    if max_plan_len is not None:
-        if int(max_plan_len) != max_plan_len or int(max_plan_len) < 1:
-            raise ValueError(f"evaluate_networks: max_plan_len must be an integer >= 1, got {max_plan_len}")
-        if any(int(n) < 1 for n in n_sims_range):
-            raise ValueError("evaluate_networks: a plan needs n_simulations >= 1 in every budget")
+    nset = _network_set("evaluate_networks", networks)
+    _check_plan("evaluate_networks", max_plan_len, n_sims_range)
     if int(max_roots) < 1:
         raise ValueError(f"evaluate_networks: max_roots must be >= 1, got {max_roots}")
     M = len(nset)
@@ -656,20 +707,12 @@ def evaluate_perturbed(networks, n_disks, *, conditions, starts=None, start_idx=
     draw, r its row of the batch, so the slicing does not change any episode.
     Returns dict(solve_rate [M][C], importance [M][C], solved [R] uint8, steps [R] int32, illegal [R] int32 and the
     layout's net_index / cond_index / start_idx [R]) as host arrays."""
-    if isinstance(networks, NetworkSet):
-        nset = networks
-    else:
-        nset = NetworkSet(list(networks) if isinstance(networks, (list, tuple)) else [networks])
+    nset = _network_set("evaluate_perturbed", networks)
     if nset.in_dim != 3 * n_disks:
         raise ValueError(f"evaluate_perturbed: the networks read {nset.in_dim} inputs, n_disks={n_disks} gives {3 * n_disks}")
     if int(max_roots) < 1:
         raise ValueError(f"evaluate_perturbed: max_roots must be >= 1, got {max_roots}")
-    if starts is not None:
-        start_idx = [state_index(s) for s in starts]
-    elif start_idx is None:
-        if episodes is None or int(episodes) < 1:
-            raise ValueError("evaluate_perturbed: no starts (give starts, start_idx or episodes >= 1)")
-        start_idx = _batch_starts(n_disks, int(episodes), None, None, seed, goal_peg)
+    start_idx = _start_indices("evaluate_perturbed", n_disks, starts, start_idx, episodes, seed, goal_peg)
     lay = perturbed_layout(len(nset), conditions, start_idx, n_disks)
     R = int(lay["net_index"].shape[0])
     sp = BatchedSelfPlay(nset, n_disks, max_steps, int(n_sims), goal_peg=goal_peg)
@@ -710,64 +753,21 @@ def evaluate_legality(networks, n_disks, *, episodes=100, n_sims=25, max_steps=2
     [T][E][6], legal [T][E], action [T][E] (-1 after the episode's end)."""
     from .acting import legality_summary  # acting imports this module
 
-    if isinstance(networks, NetworkSet):
-        nets = list(networks.nets)
-    else:
-        nets = list(networks) if isinstance(networks, (list, tuple)) else [networks]
-    M = len(nets)
-    if M < 1:
-        raise ValueError("evaluate_legality: no networks")
-    if starts is not None:
-        start_idx = [state_index(s) for s in starts]
-    elif start_idx is None:
-        if int(episodes) < 1:
-            raise ValueError("evaluate_legality: no starts (give starts, start_idx or episodes >= 1)")
-        start_idx = _batch_starts(n_disks, int(episodes), None, None, seed, goal_peg)
-    start_idx = np.asarray(start_idx, np.int64).reshape(-1)
+    nset = _network_set("evaluate_legality", networks)
+    M = len(nset)
+    start_idx = _start_indices("evaluate_legality", n_disks, starts, start_idx, episodes, seed, goal_peg)
     E = int(start_idx.shape[0])
-    if E < 1 or start_idx.min() < 0 or start_idx.max() >= 3 ** n_disks:
-        raise ValueError(f"evaluate_legality: starts must be state indices in [0, {3 ** n_disks}), at least one")
     if int(max_steps) < 1:
         raise ValueError(f"evaluate_legality: max_steps must be >= 1, got {max_steps}")
-    multi = M > 1
-    nset = (networks if isinstance(networks, NetworkSet) else NetworkSet(nets)) if multi else None
-    if (nset.in_dim if multi else nets[0].representation_net[0].in_features) != 3 * n_disks:
+    if nset.in_dim != 3 * n_disks:
         raise ValueError(f"evaluate_legality: the networks do not read {3 * n_disks} inputs (n_disks={n_disks})")
-    B, T, S = M * E, int(max_steps), int(n_sims)
-    sp = BatchedSelfPlay(nset if multi else nets[0], n_disks, T, S, goal_peg=goal_peg)
-    net_index = np.repeat(np.arange(M), E) if multi else None
-    _, eng, _, env, _, gen, mm = sp._setup(np.tile(start_idx, M), None, seed, net_index)
-    dev = eng.device
-    episode_of = torch.arange(B, device=dev) % E  # the row of a move's draws an env takes
-    rec_r = torch.zeros((T, B, 6), dtype=torch.float32, device=dev)
-    rec_v = torch.zeros((T, B, 6), dtype=torch.float32, device=dev)
-    rec_l = torch.zeros((T, B), dtype=torch.uint8, device=dev)
-    rec_a = torch.full((T, B), -1, dtype=torch.int32, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    env._tallies()  # last_obs: the starts' observations
-    n, idx, t = B, torch.arange(B, device=dev), 0
-    while n:
-        if legacy_rng:
-            draws = sp._draws(n, False, True, gen)
-        else:
-            rows = episode_of.index_select(0, idx)
-            draws = [None if x is None else torch.as_tensor(x).to(dev).index_select(0, rows)
-                     for x in sp._draws(E, False, False, gen)]
-        out = sp._search(eng, False, env.last_obs.index_select(0, idx), idx, draws, mm, 0.0, False)
-        idx32 = idx.to(torch.int32)
-        eng.probe_actions(env.last_obs, env_index=idx32, state=env.state, err=err,
-                          net_index=sp._net_index.index_select(0, idx) if multi else None,
-                          out=dict(reward=rec_r[t], value=rec_v[t], legal=rec_l[t]))
-        rec_a[t].index_copy_(0, idx, out["action"])
-        env.step_observe(out["action"], idx32)
-        # the move's one host read: how many envs are still playing, and the kernels' error counts
-        left, e1, e2 = (int(x) for x in torch.stack([env.active.sum(dtype=torch.int32), env.err[0], err[0]]).cpu())
-        if e1 or e2:
-            raise RuntimeError(f"evaluate_legality: the env step reported {e1} and the probe {e2} error(s)")
-        n, t = left, t + 1
-        idx = torch.sort(env.active, descending=True, stable=True).indices[:n]
-    steps = env.steps_total.cpu().numpy()
-    reward, value, legal, action = (x[:t].cpu().numpy() for x in (rec_r, rec_v, rec_l, rec_a))
+    multi = M > 1  # one network: mzh_search
+    sp = BatchedSelfPlay(nset if multi else nset[0], n_disks, int(max_steps), int(n_sims), goal_peg=goal_peg)
+    # episode e of every network takes row e of a move's draws
+    got = sp.play_probed(np.tile(start_idx, M), seed=seed, legacy_rng=legacy_rng,
+                         net_index=np.repeat(np.arange(M), E) if multi else None, draw_index=np.arange(M * E) % E)
+    reward, value, legal, action, steps = (got[k].cpu().numpy()
+                                           for k in ("reward", "value", "legal", "action", "steps"))
     res = []
     for m in range(M):
         sl = slice(m * E, (m + 1) * E)

@@ -220,7 +220,7 @@ def test_perturbation_draws_prefix_property(seed):
 
 
 def test_perturbation_seeds_are_a_stream_apart_from_the_search_seeds():
-    """the search draws' seeds are default_rng(seed).integers(2**31) (BatchedSelfPlay._draws); the perturbation
+    """the search draws' seeds are default_rng(seed).integers(2**31) (selfplay._Lockstep._draw); the perturbation
     draws' come from a child of seed's sequence, and taking them does not move the search seeds"""
     for seed in (0, 5):
         search = np.random.default_rng(seed).integers(2**31, size=8)

@@ -93,7 +93,8 @@ def test_episode_replay_dropin_gpu(name):
 @pytest.mark.gpu
 def test_batched_selfplay_vs_oracle(oracle):
     """B envs in lockstep on the GPU == the same episodes simulated with the oracle (MLP mode), each
-    env one agent whose MinMaxStats is carried from decision to decision (MCTS/mcts.py:23)."""
+    env one agent whose MinMaxStats is carried from decision to decision (MCTS/mcts.py:23).  Every key of
+    play's record is compared per move and per env, the fill values in the rows of finished envs included."""
     from muzero_hanoi_amd.networks import MuZeroNet
     from muzero_hanoi_amd.selfplay import BatchedSelfPlay
 
@@ -107,10 +108,19 @@ def test_batched_selfplay_vs_oracle(oracle):
     mm0 = np.stack([np.linspace(-2.0, 0.0, B), np.linspace(0.5, 3.0, B)], 1)  # agents with history
     mm0[::3] = (-np.inf, np.inf)  # and fresh ones
     res = BatchedSelfPlay(net, n, max_steps, S).play(starts, temperature=1.0, deterministic=False, seed=seed,
-                                                     minmax=mm0)
-    act = res["action"].cpu().numpy()
-    steps = res["steps"].cpu().numpy()
+                                                     minmax=mm0, record_obs=True)
+    got = {k: v.cpu().numpy() for k, v in res.items()}
+    act = got["action"]
+    steps = got["steps"]
+    T = act.shape[0]
+    assert {k: (v.dtype, v.shape) for k, v in got.items()} == dict(
+        action=(np.int32, (T, B)), reward=(np.float64, (T, B)), pi=(np.float64, (T, B, 6)),
+        root_q=(np.float64, (T, B)), active=(np.bool_, (T, B)), obs=(np.float32, (T, B, 3 * n)),
+        steps=(np.int32, (B,)), illegal=(np.int32, (B,)), start_idx=(np.int64, (B,)), minmax=(np.float64, (B, 2)))
+    assert np.array_equal(got["start_idx"], starts)
     mm = mm0.copy()
+    illegal = np.zeros(B, int)
+    goal_end = np.zeros(B, bool)
     # oracle simulation with the same per-step draws
     gen = np.random.default_rng(seed)
     st = np.stack([(starts // 3 ** (n - 1 - d)) % 3 for d in range(n)], 1).astype(np.uint8)
@@ -124,19 +134,38 @@ def test_batched_selfplay_vs_oracle(oracle):
         noise, tie, u = mrng.synthetic_draws(len(idx), deterministic=False, alpha=0.25, seed=int(gen.integers(2**31)))
         o = oracle.search(n, S, obs[idx], flat=flat, support=33, noise=noise, tie_idx=tie, action_u=u, temperature=1.0,
                           minmax_in=mm[idx])
+        assert t < T, "the oracle's envs play longer than the GPU's"
         assert np.array_equal(o["action"], act[t, idx]), f"step {t}"
+        assert np.array_equal(o["pi"], got["pi"][t, idx]), f"step {t}"
+        assert np.array_equal(o["rootQ"], got["root_q"][t, idx]), f"step {t}"
+        assert np.array_equal(obs[idx], got["obs"][t, idx]), f"step {t}"  # the observation searched
+        assert np.array_equal(alive, got["active"][t]), f"step {t}"
         mm[idx] = np.stack([o["mm_max"], o["mm_min"]], 1)
+        rwd = np.zeros(B)
         for j, b in enumerate(idx):
             code, s2, moved, c2, a2, d, ill = oracle.env_step(st[b], int(o["action"][j]), int(ctr[b]), 1, max_steps)
             st[b], ctr[b] = s2, c2
+            rwd[b] = {0: 0.0, 1: 100.0, -1: -100 / 1000}[int(code)]
+            illegal[b] += int(ill)
+            goal_end[b] |= int(code) == 1
             obs[b] = 0
             obs[b, np.arange(n) * 3 + moved] = 1
             if d:
                 alive[b] = False
+        assert np.array_equal(rwd[idx], got["reward"][t, idx]), f"step {t}"
+        # the rows of envs that had finished before this move: action -1, zeros elsewhere
+        over = np.setdiff1d(np.arange(B), idx)
+        assert np.all(act[t, over] == -1)
+        for k in ("reward", "pi", "root_q", "obs"):
+            assert not got[k][t, over].any(), f"step {t}: {k}"
         t += 1
-    assert t == act.shape[0]
-    assert np.all(steps == (act >= 0).sum(0))
-    assert np.array_equal(res["minmax"].cpu().numpy(), mm)
+    assert t == T
+    assert np.all(steps == (act >= 0).sum(0)) and np.array_equal(steps, got["active"].sum(0))
+    assert np.array_equal(got["illegal"], illegal)
+    assert np.array_equal(got["minmax"], mm)
+    # the three ways a move can go wrong are in the run: an episode that reaches the goal, one that is cut at
+    # max_steps, and an illegal move
+    assert goal_end.any() and (~goal_end & (steps == max_steps)).any() and illegal.any()
 
 
 def _fresh_net(n, seed=0):
@@ -242,3 +271,68 @@ def test_muzero_batched_selfplay():
         assert states.shape == (steps, 9) and rwds.shape == (steps, 5) and returns.shape == (steps, 5)
         assert prio.shape == (steps,) and np.allclose(pi_probs.sum(-1), 1.0)
         assert np.all(states.sum(1) == 3)  # one-hot 3-disk observations
+
+
+def test_lockstep_rows_selects_draw_rows():
+    """_Lockstep.rows on CPU tensors: the first n rows of a draw, or with draw_index the rows
+    x[draw_index[idx]]; None passes through; draw_index = arange(B) % E is evaluate_legality's "episode e of
+    every network takes row e of a move's draws"."""
+    from types import SimpleNamespace
+
+    from muzero_hanoi_amd.selfplay import _Lockstep
+
+    B, E = 12, 4
+    idx = torch.tensor([1, 2, 5, 7, 8, 11])  # the unfinished rows, in env order
+    n = int(idx.numel())
+    x = np.arange(B * 6, dtype=np.float64).reshape(B, 6)  # a draw with rows to spare (drawn for an earlier count)
+    tie = np.arange(100, 100 + B, dtype=np.int32)
+    run = SimpleNamespace(idx=idx, n=n, draw_index=None)
+    for v in (x, tie, torch.from_numpy(x)):
+        got = _Lockstep.rows(run, v)
+        assert isinstance(got, torch.Tensor) and got.dtype == torch.as_tensor(v).dtype
+        assert np.array_equal(got.numpy(), np.asarray(v)[:n])
+    assert _Lockstep.rows(run, None) is None
+    di = torch.tensor([3, 0, 9, 9, 4, 1, 7, 2, 8, 5, 6, 10])  # any rows, repeats included
+    run = SimpleNamespace(idx=idx, n=n, draw_index=di)
+    assert np.array_equal(_Lockstep.rows(run, x).numpy(), x[di.numpy()[idx.numpy()]])
+    assert np.array_equal(_Lockstep.rows(run, tie).numpy(), tie[di.numpy()[idx.numpy()]])
+    assert _Lockstep.rows(run, None) is None
+    # evaluate_legality's selection: a draw of E rows, row (env % E) for env b
+    run = SimpleNamespace(idx=idx, n=n, draw_index=torch.arange(B) % E)
+    episode_of = torch.arange(B) % E
+    want = torch.as_tensor(x[:E]).index_select(0, episode_of.index_select(0, idx))
+    assert torch.equal(_Lockstep.rows(run, x[:E]), want)
+    assert np.array_equal(want.numpy(), x[[1, 2, 1, 3, 0, 3]])
+
+
+@pytest.mark.gpu
+def test_play_launches_and_host_reads_per_move(monkeypatch):
+    """play makes, per move, one HanoiBatch.step_observe call on the full-batch arrays, no engine.env_step
+    call (no gather / scatter of a sub-batch) and one host read (no nonzero(): the count of unfinished envs
+    and the error count come in one copy)."""
+    from muzero_hanoi_amd import engine
+    from muzero_hanoi_amd.env import HanoiBatch
+    from muzero_hanoi_amd.selfplay import BatchedSelfPlay
+
+    n, S, B, max_steps = 3, 8, 12, 10
+    reads = ("nonzero", "cpu", "item", "tolist", "numpy")  # what brings a device tensor's values to the host
+    calls = dict.fromkeys(("env_step", "step_observe") + reads, 0)
+
+    def counted(name, fn, device_only=False):
+        def f(*a, **k):
+            calls[name] += not device_only or a[0].is_cuda
+            return fn(*a, **k)
+        return f
+
+    sp = BatchedSelfPlay(_fresh_net(n), n, max_steps, S)
+    starts = np.random.RandomState(2).randint(0, 3 ** n - 1, B)
+    sp.play(starts, seed=1)  # the engine and its weights are in place before the calls are counted
+    with monkeypatch.context() as m:
+        m.setattr(engine, "env_step", counted("env_step", engine.env_step))
+        m.setattr(HanoiBatch, "step_observe", counted("step_observe", HanoiBatch.step_observe))
+        for name in reads:
+            m.setattr(torch.Tensor, name, counted(name, getattr(torch.Tensor, name), device_only=True))
+        res = sp.play(starts, seed=3, record_obs=True)
+    T = int(res["action"].shape[0])
+    assert 1 <= T <= max_steps and int(res["steps"].max()) == T
+    assert calls == dict(env_step=0, step_observe=T, nonzero=0, cpu=T, item=0, tolist=0, numpy=0)
