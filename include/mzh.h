@@ -320,6 +320,44 @@ int mzh_search_replay(mzh_engine* eng, const mzh_search_args* args, mzh_stream s
 int mzh_search_plan_query(int support, int B, int n_sims, uint32_t flags, int replay, int has_minmax_in,
                           mzh_search_plan* out);
 
+/* The expansion memo of the wave kernel.  A network output is a pure function of the
+ * weights, the root state and the action path, and an N-disc game has only 3^N states, so an engine keeps the
+ * outputs of every node up to D moves below every one-hot root state in a table: node id(path + a) =
+ * 6 id(path) + a + 1 with id(empty) = 0, row = state * K(D) + id with K(D) = 1 + 6 + ... + 6^D, state =
+ * sum_i peg(disc i) 3^i.  A row is the node's normalised latent (64 floats, as the search stores it) and a
+ * 32-byte record (6 priors, reward, value: the replay record's layout), filled level by level with the
+ * inference kernels, so every row is bit for bit what the search would compute.  The table is built by the
+ * first mzh_search after mzh_load_weights whose plan is the wave kernel (on that call's stream, which it
+ * waits for; never under replay or a weight set), dropped by mzh_load_weights and freed by mzh_destroy.  A
+ * root whose observation is not exactly one-hot per disc never uses it.  Results do not depend on the memo.
+ *   depth -1: automatic, the largest D whose table fits the byte budget (the default); 0: off; d > 0: force
+ *   D = d (MZH_ERR_CAPACITY above 2^26 rows).  A change takes effect with the next search.  The environment
+ *   variable MZH_MEMO_DEPTH gives a new engine its initial request; mzh_create refuses a value that is no
+ *   integer or that this call would refuse.
+ * A build holds, beside the table, about 1.7 times its bytes in temporaries until it returns (0.55 GiB in all
+ * at four discs and D = 5).  When a forced depth's build fails, the search fails.  When the automatic depth's
+ * build runs out of device memory, the next shallower depth is tried, down to no memo, the search runs as it
+ * would have without one, and later searches keep that depth until this call is made again. */
+int mzh_set_memo_depth(mzh_engine* eng, int depth);
+typedef struct mzh_memo_info {
+  int32_t depth;        /* D in use by the next wave search (0: no memo) */
+  int32_t built;        /* 1: the table of the loaded weights exists */
+  int64_t rows;         /* 3^N K(D) */
+  int64_t table_bytes;  /* rows * 288 */
+  double build_ms;      /* the last build on the host's clock: allocations, the fill, the wait for it, the frees */
+  /* (wave, simulation) pairs since mzh_create that ran no MLP / the packed 16-column MLP / the full MLP,
+   * counted by the wave searches that had a table (the call waits for the device) */
+  uint64_t pairs_skipped, pairs_packed, pairs_full;
+} mzh_memo_info;
+int mzh_memo_stats(mzh_engine* eng, mzh_memo_info* out);
+/* Host-only: the depth a request gives for n_disks (as mzh_set_memo_depth reads it), its rows and bytes. */
+int mzh_memo_plan(int n_disks, int depth, int32_t* depth_out, int64_t* rows, int64_t* bytes);
+/* Debug: the built table's rows and depth (0 / 0 before the build) and, where the device buffers are given, a
+ * copy of it: latent [rows][64] (position 16kb + 4g + t of a row holds unit 16kb + 4t + g, the order the wave
+ * kernel keeps latents in) and record [rows][8].  Waits for the device. */
+int mzh_memo_debug_table(mzh_engine* eng, float* latent /* nullable */, float* record /* nullable */, int64_t* rows,
+                         int32_t* depth);
+
 /* Search roots of several networks in one launch: root b is searched under network net_index[b] of the set
  * loaded by mzh_load_weight_set, with the result mzh_search gives on an engine holding that network alone
  * (bit for bit).  `args` is mzh_search's, unchanged: every input and output is indexed by root.  The roots of

@@ -57,6 +57,16 @@ class SearchArgs(ctypes.Structure):
     ]
 
 
+class MemoInfo(ctypes.Structure):
+    """mirror of struct mzh_memo_info (include/mzh.h)"""
+    _fields_ = [("depth", _i32), ("built", _i32), ("rows", ctypes.c_int64), ("table_bytes", ctypes.c_int64),
+                ("build_ms", ctypes.c_double), ("pairs_skipped", ctypes.c_uint64), ("pairs_packed", ctypes.c_uint64),
+                ("pairs_full", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 class MultiArgs(ctypes.Structure):
     """mirror of struct mzh_multi_args (include/mzh.h)"""
     _fields_ = [("n_networks", _i32), ("net_index", _vp), ("status", _vp)]
@@ -149,6 +159,11 @@ SIGNATURES = {
     "mzh_probe_actions": (ctypes.c_int, [_vp, ctypes.POINTER(ProbeArgs), ctypes.POINTER(MultiArgs), _vp]),
     "mzh_search_plan_query": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int,
                                              ctypes.c_int, ctypes.POINTER(SearchPlan)]),
+    "mzh_set_memo_depth": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "mzh_memo_stats": (ctypes.c_int, [_vp, ctypes.POINTER(MemoInfo)]),
+    "mzh_memo_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(_i32), ctypes.POINTER(ctypes.c_int64),
+                                     ctypes.POINTER(ctypes.c_int64)]),
+    "mzh_memo_debug_table": (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(_i32)]),
     "mzh_rng_predraw": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int,
                                        _vp, _vp, _vp]),
     "mzh_train_scratch_bytes": (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_size_t)]),
@@ -214,6 +229,15 @@ def search_plan(support, B, n_sims, flags=0, replay=False, minmax_in=False):
     check(lib().mzh_search_plan_query(int(support), int(B), int(n_sims), int(flags), 1 if replay else 0,
                                       1 if minmax_in else 0, ctypes.byref(out)), "mzh_search_plan_query")
     return out.as_dict()
+
+
+def memo_plan(n_disks, depth=-1):
+    """the expansion memo a depth request gives at n_disks (host-only): dict(depth, rows, bytes);
+    depth -1 = automatic (the byte budget), 0 = off, d > 0 = forced"""
+    d, rows, nbytes = _i32(), ctypes.c_int64(), ctypes.c_int64()
+    check(lib().mzh_memo_plan(int(n_disks), int(depth), ctypes.byref(d), ctypes.byref(rows), ctypes.byref(nbytes)),
+          "mzh_memo_plan")
+    return {"depth": d.value, "rows": rows.value, "bytes": nbytes.value}
 
 
 def device_count():

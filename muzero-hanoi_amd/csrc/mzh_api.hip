@@ -7,6 +7,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <chrono>
 #include <string>
 #include <vector>
 
@@ -36,6 +37,8 @@ static int hip_fail(hipError_t e, const char* what) {
     hipError_t e_ = (expr);                            \
     if (e_ != hipSuccess) return hip_fail(e_, #expr);  \
   } while (0)
+
+static int memo_depth_for(int n_disks, int want, int* D);  // the expansion memo's depth of a request (below)
 
 // RAII: run on the engine's device, restore the caller's current device afterwards
 struct DeviceGuard {
@@ -72,6 +75,14 @@ struct mzh_engine {
   const float* set_scal = nullptr;
   MzhTile* mtiles = nullptr;   // tile table workspace of mzh_search_multi, allocated with the first set
   int32_t* mntiles = nullptr;
+  // the wave kernel's expansion memo (mzh.h): built by the first wave search after a weight load
+  int memo_want = -1;          // mzh_set_memo_depth: -1 automatic, 0 off, d > 0 forced
+  int memo_auto_cap = MZH_MEMO_MAX_DEPTH;  // the automatic depth's ceiling: lowered when a build ran out of memory
+  int memo_D = 0;              // depth of the built table (0: none)
+  float* memo_h = nullptr;     // [rows][64]
+  float* memo_rec = nullptr;   // [rows][8]
+  unsigned long long* memo_cnt = nullptr;  // [3] device counters, zeroed by mzh_create
+  double memo_build_ms = 0.0;
 };
 
 extern "C" int mzh_abi_version(void) { return MZH_ABI_VERSION; }
@@ -127,12 +138,32 @@ extern "C" int mzh_create(int device, int n_disks, int max_sims, int max_roots, 
   eng->in_dim = 3 * n_disks;
   eng->kin = ((eng->in_dim + 15) / 16) * 16;
   eng->E = max_sims + 1;
+  // MZH_MEMO_DEPTH: the engine's initial memo depth request, as mzh_set_memo_depth reads it (measurements
+  // through programs that do not call it).  A value that is no integer, or one mzh_set_memo_depth would
+  // refuse, is an error: no engine is made
+  if (const char* v = getenv("MZH_MEMO_DEPTH")) {
+    char* end = nullptr;
+    const long d = strtol(v, &end, 10);
+    int D = 0;
+    if (end == v || *end != '\0' || d < -1 || d > MZH_MEMO_MAX_DEPTH) {
+      delete eng;
+      return fail(MZH_ERR_ARG, "MZH_MEMO_DEPTH='%s': expected an integer in [-1, %d]", v, MZH_MEMO_MAX_DEPTH);
+    }
+    const int st = memo_depth_for(n_disks, (int)d, &D);
+    if (st) {
+      delete eng;
+      return st;
+    }
+    eng->memo_want = (int)d;
+  }
   const size_t nblk = (size_t)max_roots * eng->E;
   // MzhBlock (mzh_tree.h) / MzwBlock (mzh_wave.hip): one 128-B cache line per expanded node
   hipError_t e = hipMalloc(&eng->tree, nblk * 128);  // one 128-B block per expanded node
   if (e == hipSuccess) e = hipMalloc(&eng->htree, nblk * MZH_LATENT * sizeof(float));
   if (e == hipSuccess) e = hipMalloc(&eng->pathx, nblk * sizeof(uint16_t));
   if (e == hipSuccess) e = hipMalloc(&eng->table, sizeof(double) * (size_t)(max_sims + 2));
+  if (e == hipSuccess) e = hipMalloc(&eng->memo_cnt, 3 * sizeof(unsigned long long));
+  if (e == hipSuccess) e = hipMemset(eng->memo_cnt, 0, 3 * sizeof(unsigned long long));
   if (e != hipSuccess) {
     mzh_destroy(eng);
     return hip_fail(e, "hipMalloc (engine workspace)");
@@ -160,8 +191,24 @@ extern "C" int mzh_destroy(mzh_engine* eng) {
   if (eng->setbuf) (void)hipFree(eng->setbuf);
   if (eng->mtiles) (void)hipFree(eng->mtiles);
   if (eng->mntiles) (void)hipFree(eng->mntiles);
+  if (eng->memo_h) (void)hipFree(eng->memo_h);
+  if (eng->memo_rec) (void)hipFree(eng->memo_rec);
+  if (eng->memo_cnt) (void)hipFree(eng->memo_cnt);
   delete eng;
   return MZH_OK;
+}
+
+// drop the expansion memo (after the device has finished with it)
+static hipError_t memo_drop(mzh_engine* eng) {
+  if (!eng->memo_h && !eng->memo_rec) return hipSuccess;
+  hipError_t e = hipDeviceSynchronize();
+  if (e != hipSuccess) return e;
+  if (eng->memo_h) (void)hipFree(eng->memo_h);
+  if (eng->memo_rec) (void)hipFree(eng->memo_rec);
+  eng->memo_h = nullptr;
+  eng->memo_rec = nullptr;
+  eng->memo_D = 0;
+  return hipSuccess;
 }
 
 // the cooperative kernels' view of a packed blob uploaded at `base` (MzhPacked's offsets as pointers)
@@ -208,6 +255,7 @@ extern "C" int mzh_load_weights(mzh_engine* eng, const float* flat, size_t n_flo
     eng->wbuf = nullptr;
     eng->loaded = false;
   }
+  HIP_OK(memo_drop(eng));  // the table is a function of the weights
   HIP_OK(hipMalloc(&eng->wbuf, pk.blob.size() * sizeof(float)));
   HIP_OK(hipMemcpy(eng->wbuf, pk.blob.data(), pk.blob.size() * sizeof(float), hipMemcpyHostToDevice));
   const float* base = static_cast<const float*>(eng->wbuf);
@@ -550,6 +598,183 @@ static MzhSearchParams search_params(const mzh_engine* eng, const mzh_search_arg
   return p;
 }
 
+// ---- the wave kernel's expansion memo (mzh.h) ----
+// the depth a request gives: -1 the budget's, 0 off, d > 0 as asked (status: a forced table too large)
+static int memo_depth_for(int n_disks, int want, int* D) {
+  if (want < -1 || want > MZH_MEMO_MAX_DEPTH)
+    return fail(MZH_ERR_ARG, "memo depth must be -1 (automatic), 0 (off) or 1..%d, got %d", MZH_MEMO_MAX_DEPTH, want);
+  if (n_disks < 1 || n_disks > 16) return fail(MZH_ERR_ARG, "n_disks must be in [1,16], got %d", n_disks);
+  *D = want < 0 ? mzh_memo_auto_depth(n_disks) : want;
+  if (mzh_memo_states(n_disks) * mzh_memo_nodes(*D) > MZH_MEMO_MAX_ROWS)
+    return fail(MZH_ERR_CAPACITY, "memo depth %d at %d discs is %lld rows, more than %lld", *D, n_disks,
+                mzh_memo_states(n_disks) * mzh_memo_nodes(*D), MZH_MEMO_MAX_ROWS);
+  return MZH_OK;
+}
+
+extern "C" int mzh_memo_plan(int n_disks, int depth, int32_t* depth_out, int64_t* rows, int64_t* bytes) {
+  int D = 0;
+  const int st = memo_depth_for(n_disks, depth, &D);
+  if (st) return st;
+  const long long r = D > 0 ? mzh_memo_states(n_disks) * mzh_memo_nodes(D) : 0;
+  if (depth_out) *depth_out = D;
+  if (rows) *rows = r;
+  if (bytes) *bytes = r * MZH_MEMO_ROW_BYTES;
+  return MZH_OK;
+}
+
+extern "C" int mzh_set_memo_depth(mzh_engine* eng, int depth) {
+  if (!eng) return fail(MZH_ERR_ARG, "engine NULL");
+  int D = 0;
+  const int st = memo_depth_for(eng->n_disks, depth, &D);
+  if (st) return st;
+  eng->memo_want = depth;
+  eng->memo_auto_cap = MZH_MEMO_MAX_DEPTH;
+  return MZH_OK;
+}
+
+// the depth the next wave search uses: the request's, the automatic one no deeper than a build's memory allowed
+static int memo_effective_depth(const mzh_engine* eng, int* D) {
+  const int st = memo_depth_for(eng->n_disks, eng->memo_want, D);
+  if (st == MZH_OK && eng->memo_want < 0 && *D > eng->memo_auto_cap) *D = eng->memo_auto_cap;
+  return st;
+}
+
+// Fill the table for the loaded weights at depth D, level by level with the inference kernels: the 3^N one-hot
+// states through initial inference, then every (node, move) of the level above through recurrent inference.
+// Within a level the rows are ordered (state, node): child row = 6 * parent row + move.  Runs on `stream` and
+// waits for it (the temporaries are freed on return).
+static int memo_build(mzh_engine* eng, int D, hipStream_t stream, bool* oom) {
+  *oom = false;
+  HIP_OK(memo_drop(eng));
+  const auto t_start = std::chrono::steady_clock::now();
+  const int N = eng->n_disks, in = eng->in_dim;
+  const long long ST = mzh_memo_states(N), K = mzh_memo_nodes(D), rows = ST * K;
+  long long top = ST;  // rows of the deepest level
+  for (int d = 0; d < D; ++d) top *= 6;
+  std::vector<float> obs((size_t)ST * in, 0.0f);
+  for (long long s = 0; s < ST; ++s) {
+    long long q = s;
+    for (int i = 0; i < N; ++i, q /= 3) obs[(size_t)s * in + 3 * i + (int)(q % 3)] = 1.0f;
+  }
+  // temporaries: two natural-order latent levels (ping-pong), the level's expanded input, moves, heads
+  float *dobs = nullptr, *hA = nullptr, *hB = nullptr, *xin = nullptr, *pi = nullptr, *rw = nullptr, *va = nullptr;
+  int32_t* act = nullptr;
+  auto release = [&]() {
+    for (void* q : {(void*)dobs, (void*)hA, (void*)hB, (void*)xin, (void*)pi, (void*)rw, (void*)va, (void*)act})
+      if (q) (void)hipFree(q);
+  };
+  auto bail = [&](hipError_t e, const char* what) {
+    release();
+    (void)memo_drop(eng);
+    return hip_fail(e, what);
+  };
+  hipError_t e = hipMalloc(&eng->memo_h, (size_t)rows * MZH_LATENT * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc(&eng->memo_rec, (size_t)rows * 8 * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc(&dobs, obs.size() * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc(&hA, (size_t)top * MZH_LATENT * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc(&hB, (size_t)(top / 6 + 1) * MZH_LATENT * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc(&xin, (size_t)top * MZH_LATENT * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc(&act, (size_t)top * sizeof(int32_t));
+  if (e == hipSuccess) e = hipMalloc(&pi, (size_t)top * MZH_A * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc(&rw, (size_t)top * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc(&va, (size_t)top * sizeof(float));
+  if (e != hipSuccess) {
+    *oom = e == hipErrorOutOfMemory;
+    if (*oom) (void)hipGetLastError();  // the runtime's sticky copy of this error
+    return bail(e, "memo build: allocation");
+  }
+  e = hipMemcpyAsync(dobs, obs.data(), obs.size() * sizeof(float), hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess) e = hipMemsetAsync(rw, 0, (size_t)ST * sizeof(float), stream);  // a root has no reward
+  if (e != hipSuccess) return bail(e, "memo build: upload");
+  // the level's outputs go to hcur; levels alternate between hA and hB so that the deepest lands in hA
+  float* hcur = (D % 2 == 0) ? hA : hB;
+  float* hprev = (D % 2 == 0) ? hB : hA;
+  long long n = ST, first = 0, per_state = 1;
+  for (int d = 0; d <= D; ++d) {
+    MzhInferParams p{};
+    p.B = (int)n; p.in_dim = in; p.kin = eng->kin; p.h = hcur; p.pi = pi; p.value = va;
+    if (d == 0) {
+      p.x = dobs;
+    } else {
+      e = mzh_launch_memo_level(hprev, xin, act, n, stream);
+      if (e != hipSuccess) return bail(e, "memo build: level input");
+      p.x = xin; p.action = act; p.reward = rw;
+    }
+    e = mzh_launch_infer(pick_rows((int)n), d > 0, eng->net, p, stream);
+    if (e == hipSuccess) e = mzh_launch_memo_scatter(hcur, pi, rw, va, n, per_state, K, first, eng->memo_h, eng->memo_rec, stream);
+    if (e != hipSuccess) return bail(e, "memo build: level");
+    first += per_state;
+    per_state *= 6;
+    n *= 6;
+    float* t = hcur; hcur = hprev; hprev = t;
+  }
+  e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) return bail(e, "memo build: run");
+  release();
+  eng->memo_D = D;
+  // what the building search call paid: allocations, the fill, the wait and the frees, on the host's clock
+  eng->memo_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+  return MZH_OK;
+}
+
+// the memo of a wave MLP search: built on first use, rebuilt when the wanted depth changed.  A forced depth
+// whose build fails is the call's error.  The automatic depth is an optimisation the caller did not ask for:
+// when its table or the build's temporaries do not fit the device's free memory, the next shallower one is
+// tried, down to no memo, and later searches keep that depth (mzh_set_memo_depth lifts the ceiling)
+static int memo_ensure(mzh_engine* eng, hipStream_t stream) {
+  for (;;) {
+    int D = 0;
+    const int st = memo_effective_depth(eng, &D);
+    if (st) return st;
+    if (D == eng->memo_D) return MZH_OK;
+    if (D == 0) {
+      HIP_OK(memo_drop(eng));
+      return MZH_OK;
+    }
+    bool oom = false;
+    const int bs = memo_build(eng, D, stream, &oom);
+    if (bs == MZH_OK || eng->memo_want >= 0 || !oom) return bs;
+    eng->memo_auto_cap = D - 1;
+  }
+}
+
+extern "C" int mzh_memo_stats(mzh_engine* eng, mzh_memo_info* out) {
+  if (!eng || !out) return fail(MZH_ERR_ARG, "memo_stats: engine or out NULL");
+  memset(out, 0, sizeof(*out));
+  int D = 0;
+  const int st = memo_effective_depth(eng, &D);
+  if (st) return st;
+  out->depth = D;
+  out->built = (D > 0 && eng->memo_D == D) ? 1 : 0;
+  out->rows = D > 0 ? mzh_memo_states(eng->n_disks) * mzh_memo_nodes(D) : 0;
+  out->table_bytes = out->rows * MZH_MEMO_ROW_BYTES;
+  out->build_ms = eng->memo_build_ms;
+  DeviceGuard g(eng->device);
+  if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+  unsigned long long c[3] = {0, 0, 0};
+  HIP_OK(hipDeviceSynchronize());
+  HIP_OK(hipMemcpy(c, eng->memo_cnt, sizeof(c), hipMemcpyDeviceToHost));
+  out->pairs_skipped = c[0];
+  out->pairs_packed = c[1];
+  out->pairs_full = c[2];
+  return MZH_OK;
+}
+
+extern "C" int mzh_memo_debug_table(mzh_engine* eng, float* latent, float* record, int64_t* rows, int32_t* depth) {
+  if (!eng || !rows || !depth) return fail(MZH_ERR_ARG, "memo_debug_table: NULL argument");
+  const long long n = eng->memo_D > 0 ? mzh_memo_states(eng->n_disks) * mzh_memo_nodes(eng->memo_D) : 0;
+  *rows = n;
+  *depth = eng->memo_D;
+  if (n == 0 || (!latent && !record)) return MZH_OK;
+  DeviceGuard g(eng->device);
+  if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+  HIP_OK(hipDeviceSynchronize());
+  if (latent) HIP_OK(hipMemcpy(latent, eng->memo_h, (size_t)n * MZH_LATENT * sizeof(float), hipMemcpyDeviceToDevice));
+  if (record) HIP_OK(hipMemcpy(record, eng->memo_rec, (size_t)n * 8 * sizeof(float), hipMemcpyDeviceToDevice));
+  HIP_OK(hipDeviceSynchronize());
+  return MZH_OK;
+}
+
 static int search_common(mzh_engine* eng, const mzh_search_args* a, mzh_stream stream, bool replay) {
   if (!eng || !a) return fail(MZH_ERR_ARG, "engine or args NULL");
   if (a->B < 0 || a->n_sims < 0) return fail(MZH_ERR_ARG, "B=%d n_sims=%d", a->B, a->n_sims);
@@ -580,7 +805,15 @@ static int search_common(mzh_engine* eng, const mzh_search_args* a, mzh_stream s
   if (a->plan_out) plan_info(pl, a->B, a->n_sims, a->plan_out);
   DeviceGuard g(eng->device);
   if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
-  const MzhSearchParams p = search_params(eng, a);
+  MzhSearchParams p = search_params(eng, a);
+  if (pl.wave && !replay) {  // the expansion memo: wave MLP searches only, built on first use
+    const int ms = memo_ensure(eng, (hipStream_t)stream);
+    if (ms) return ms;
+    if (eng->memo_D > 0) {
+      p.memo_h = eng->memo_h; p.memo_rec = eng->memo_rec; p.memo_cnt = eng->memo_cnt;
+      p.memo_D = eng->memo_D; p.memo_K = (int)mzh_memo_nodes(eng->memo_D);
+    }
+  }
   hipError_t e = pl.one ? mzh_launch_one(pl, eng->net, eng->onet, p, (hipStream_t)stream)
                  : pl.wave ? mzh_launch_wave_search(pl, eng->wnet, p, (hipStream_t)stream)
                            : mzh_launch_search(pl, eng->net, p, (hipStream_t)stream);

@@ -35,7 +35,39 @@ struct MzhSearchParams {
   int32_t* sel_steps;
   const double* pow_table;  // [S + 1] np.power(n, 1/T) for a non-integer exponent (nullable)
   int32_t* lockstep_levels;  // [groups] sum over simulations of each lockstep group's deepest selection (nullable)
+  // the expansion memo (wave kernel, MLP searches; all null / 0 without one): rows state * memo_K + node id
+  const float* memo_h;    // [rows][64] normalised latents in htree's order
+  const float* memo_rec;  // [rows][8] 6 priors, reward, value
+  unsigned long long* memo_cnt;  // [3] (wave, simulation) pairs without MLP / packed / full
+  int memo_D, memo_K;     // depth, nodes per state 1 + 6 + ... + 6^D
 };
+
+// Expansion-memo arithmetic (host): nodes per state, rows and bytes at depth D, the automatic depth
+static inline long long mzh_memo_nodes(int D) {  // K(D) = (6^(D+1) - 1) / 5
+  long long k = 0, p = 1;
+  for (int d = 0; d <= D; ++d, p *= 6) k += p;
+  return k;
+}
+static inline long long mzh_memo_states(int n_disks) {
+  long long s = 1;
+  for (int i = 0; i < n_disks; ++i) s *= 3;
+  return s;
+}
+#define MZH_MEMO_ROW_BYTES 288          // 64 fp32 latent + the 32-byte record
+#define MZH_MEMO_MAX_ROWS (1ll << 26)   // a forced depth's limit (row indices stay far inside int32)
+#define MZH_MEMO_MAX_DEPTH 12
+// the byte budget of the automatic depth (N = 4 gets D = 5, N = 7 gets D = 3)
+#define MZH_MEMO_BUDGET_BYTES (256ll << 20)
+static inline int mzh_memo_auto_depth(int n_disks) {
+  const long long st = mzh_memo_states(n_disks);
+  int D = 0;
+  while (D < MZH_MEMO_MAX_DEPTH && st * mzh_memo_nodes(D + 1) * MZH_MEMO_ROW_BYTES <= MZH_MEMO_BUDGET_BYTES) ++D;
+  return D;
+}
+hipError_t mzh_launch_memo_level(const float* hprev, float* xin, int32_t* act, long long n, hipStream_t stream);
+hipError_t mzh_launch_memo_scatter(const float* h, const float* pi, const float* reward, const float* value, long long n,
+                                   long long per_state, long long K, long long first_id, float* memo_h, float* memo_rec,
+                                   hipStream_t stream);
 
 // visits ** e as generate_play_policy computes it (np.power(int64 visits, e), mcts.py:168-174), for
 // x = n visits and e = max(1, min(5, 1/T)): an integer exponent is an exact product (n^5 < 2^53);

@@ -416,6 +416,18 @@ __device__ __forceinline__ int mzw_pick_pair(const float (&u)[3], int half, int 
   return mzh_tie_pick(r[0] | r[1], tie, firstTie, extra);
 }
 
+// The column tiles of one M phase: NC = NT for the wave's own roots (column c of tile n is root 16n + c), or one
+// tile of the roots that missed the expansion memo, packed (column c is the c-th missing root)
+template <int NC>
+struct MzwCols {
+  int root[NC];    // the column's root (a valid address even where !valid)
+  bool valid[NC];  // the column's stores count
+  int en[NC], an[NC];  // the leaf's parent (expanded index) and move
+  int prow[NC];    // the parent's memo row, or -1: its latent is in htree
+  float val[NC], rew[NC];
+  floatx4 cpi[NC];
+};
+
 // The two waves a SIMD holds drift apart.  Phase-locking them (8-wave workgroups, one barrier per
 // simulation before the MLP) was measured 5-10% slower (profiles/r04_experiments.json): each
 // simulation then waits for the deepest of 256 roots.
@@ -466,6 +478,26 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
   int lsum = 0;  // p.lockstep_levels: the wave's deepest selection below the root, summed over simulations
   double rootW = 0.0;
   const int tie = (rvalid && p.tie_idx) ? p.tie_idx[rroot] : 0;
+  // the expansion memo (mzh.h): a root lane's state index when its observation row is exactly one-hot per disc
+  // (one 1.0f, two +0.0f, by bit pattern), else -1: that root never touches the table.  pid: the id of the
+  // leaf's parent node, carried through selection (meaningful while the parent's depth is <= memo_D)
+  const bool memo = !REPLAY && p.memo_h != nullptr;  // wave-uniform
+  int sigma = -1;
+  unsigned pid = 0;
+  unsigned cnt = 0;  // simulations without an M phase (low 16 bits; S <= 32000) | with the packed one (high 16)
+  if (memo && rvalid) {
+    const unsigned* orow = reinterpret_cast<const unsigned*>(p.obs) + (size_t)rroot * p.in_dim;
+    int sg = 0, w3 = 1;
+    bool ok = true;
+    for (int i = 0; 3 * i + 2 < p.in_dim; ++i, w3 *= 3) {
+      const unsigned a0 = orow[3 * i], a1 = orow[3 * i + 1], a2 = orow[3 * i + 2];
+      const unsigned one = 0x3F800000u;
+      const int n1 = (a0 == one) + (a1 == one) + (a2 == one), n0 = (a0 == 0u) + (a1 == 0u) + (a2 == 0u);
+      ok = ok && n1 == 1 && n0 == 2;
+      sg += w3 * (a1 == one ? 1 : a2 == one ? 2 : 0);
+    }
+    sigma = ok ? sg : -1;
+  }
 
   // column lanes: lane (g, col) works on root wr0 + 16n + col of column tile n (MLP phases)
   int croot[NT];
@@ -542,10 +574,14 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
   }
   mzw_wave_sync();
 
-  int en[NT], an[NT];  // the leaf's parent (expanded index) and move, per column tile
-  floatx4 rl[NOV][NT], pl[1][NT], vl[NOV][NT];  // reward / policy / value logits
-  float val[NT], rew[NT];
-  floatx4 cpi[NT];
+  MzwCols<NT> cf;  // the wave's own column tiles
+#pragma unroll
+  for (int n = 0; n < NT; ++n) {
+    cf.root[n] = cvalid[n] ? croot[n] : 0;
+    cf.valid[n] = cvalid[n];
+    cf.prow[n] = -1;
+  }
+  MzwCols<1> cp;  // the packed tile of the roots that missed the memo (32-root waves)
 
   // the four recurrent chains' rolling weight buffer, handed from chain to chain (mzw_chain WS)
   floatx4 wst[8];
@@ -579,6 +615,7 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
       ws.pcR[0][rho] = ws.rR[pick][rho];
       ws.pcN[0][rho] = Np;
       int e = 0, d = 1;
+      pid = 0;
       // 16-root waves (NT = 1) prefetch the children's blocks one level ahead (16,384 roots: 2.66 ->
       // 2.57 ms); at 32 roots per wave the partner wave's MFMA stream already covers the latency
       // (65,536 roots: neutral), so NT = 2 leaves the load queue to the block loads
@@ -588,6 +625,7 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
       // measured slower: 65,536 roots +0.6%, 16,384 roots x 200 simulations +3.7%)
       while (X >= 0 && d <= S) {  // depth <= s + 1 always; the bound only guards against a corrupt tree
         e = X;
+        pid = 6u * pid + (unsigned)pick + 1u;  // the node stepped into (wraps far below memo_D: unused there)
         int nx;
         double Wp;
         float Rp;
@@ -669,107 +707,114 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
       for (int off = 32; off > 0; off >>= 1) m = max(m, __shfl_xor(m, off));
       lsum += m;
     }
-    if (!REPLAY) {
-#pragma unroll
-      for (int n = 0; n < NT; ++n) {
-        en[n] = __shfl(leafE, 16 * n + col);
-        an[n] = __shfl(leafA, 16 * n + col);
-      }
-    }
   };
 
   // M phase: recurrent_inference's four MLPs (networks.py:96-150) as MFMA chains, each head
   // evaluated right after its chain (only scalars stay live)
-  auto phase_mlp = [&](int s) {
+  auto phase_mlp = [&](int s, auto& C) {
     if (REPLAY) return;
-    // the leaf's parent latent (mcts.py:89-92), stored by an earlier M phase (or the root inference)
-    floatx4 x[NT][4];
+    constexpr int NC = sizeof(C.root) / sizeof(int);
+    const float* const nohc[NC] = {};
+    floatx4 rl[NOV][NC], pl[1][NC], vl[NOV][NC];  // reward / policy / value logits
+    // the leaf's parent latent (mcts.py:89-92), stored by an earlier M phase (or the root inference), or the
+    // memo's row where the parent is a memo node (those are never copied into htree)
+    floatx4 x[NC][4];
 #pragma unroll
-    for (int n = 0; n < NT; ++n) {
-      const floatx4* src = reinterpret_cast<const floatx4*>(p.htree + ((size_t)(cvalid[n] ? croot[n] : 0) * E + en[n]) * MZH_H) + g;
+    for (int n = 0; n < NC; ++n) {
+      const float* row = C.prow[n] >= 0 ? p.memo_h + (size_t)C.prow[n] * MZH_H
+                                        : p.htree + ((size_t)C.root[n] * E + C.en[n]) * MZH_H;
+      const floatx4* src = reinterpret_cast<const floatx4*>(row) + g;
 #pragma unroll
       for (int kb = 0; kb < 4; ++kb) x[n][kb] = src[4 * kb];
     }
-    floatx4 hreg[NT][4];  // the new node's normalised latent
-    floatx4 hp[4][NT];
-    const float* ohp[NT];
+    floatx4 hreg[NC][4];  // the new node's normalised latent
+    floatx4 hp[4][NC];
+    const float* ohp[NC];
 #pragma unroll
-    for (int n = 0; n < NT; ++n) ohp[n] = ohl + an[n] * MZH_F + 4 * g;
+    for (int n = 0; n < NC; ++n) ohp[n] = ohl + C.an[n] * MZH_F + 4 * g;
     MZH_STAMP(10);  // latent gather
     floatx4 b2[4];  // a chain's layer-2 bias fragments, loaded by the chain (mzw_chain b2)
-    mzw_chain<NT, 4, 4, true, false, 8>(net.dyn, rw, x, ohp, hp, b2, lane, nullptr, wst, net.rwd.soff);
-    mzw_bias2<NT, 4>(hp, b2);  // h' (un-normalised, networks.py:129-138)
+    mzw_chain<NC, 4, 4, true, false, 8>(net.dyn, rw, x, ohp, hp, b2, lane, nullptr, wst, net.rwd.soff);
+    mzw_bias2<NC, 4>(hp, b2);  // h' (un-normalised, networks.py:129-138)
     MZH_STAMP(5);
-    floatx4 hx[NT][4];
+    floatx4 hx[NC][4];
 #pragma unroll
-    for (int n = 0; n < NT; ++n)
+    for (int n = 0; n < NC; ++n)
 #pragma unroll
       for (int kb = 0; kb < 4; ++kb) hx[n][kb] = hp[kb][n];
-    float r32[NT], v32[NT];
-    mzw_chain<NT, 4, NOV, false, SUP33, 8>(net.rwd, rw, hx, noh, rl, b2, lane, r32, wst, net.pol.soff);  // reward from h' (networks.py:132-135)
-    mzw_bias2<NT, NOV>(rl, b2);
+    float r32[NC], v32[NC];
+    mzw_chain<NC, 4, NOV, false, SUP33, 8>(net.rwd, rw, hx, nohc, rl, b2, lane, r32, wst, net.pol.soff);  // reward from h' (networks.py:132-135)
+    mzw_bias2<NC, NOV>(rl, b2);
     MZH_STAMP(6);
 #pragma unroll
-    for (int n = 0; n < NT; ++n) rew[n] = mzw_head<NT, NOV>(rl, n, lane, SUP33 ? r32[n] : 0.0f, net.rwd.b32);
+    for (int n = 0; n < NC; ++n) C.rew[n] = mzw_head<NC, NOV>(rl, n, lane, SUP33 ? r32[n] : 0.0f, net.rwd.b32);
     MZH_STAMP(11);
 #pragma unroll
-    for (int n = 0; n < NT; ++n) {
-      mzw_normalize<NT>(hp, n, hreg);
-      if (cvalid[n]) {
-        floatx4* dst = reinterpret_cast<floatx4*>(p.htree + ((size_t)croot[n] * E + s + 1) * MZH_H) + g;
+    for (int n = 0; n < NC; ++n) {
+      mzw_normalize<NC>(hp, n, hreg);
+      if (C.valid[n]) {
+        floatx4* dst = reinterpret_cast<floatx4*>(p.htree + ((size_t)C.root[n] * E + s + 1) * MZH_H) + g;
 #pragma unroll
         for (int kb = 0; kb < 4; ++kb) dst[4 * kb] = hreg[n][kb];
       }
     }
     MZH_STAMP(7);
-    mzw_chain<NT, 4, 1, false, false, 8>(net.pol, rw, hreg, noh, pl, b2, lane, nullptr, wst, net.val.soff);
-    mzw_bias2<NT, 1>(pl, b2);
+    mzw_chain<NC, 4, 1, false, false, 8>(net.pol, rw, hreg, nohc, pl, b2, lane, nullptr, wst, net.val.soff);
+    mzw_bias2<NC, 1>(pl, b2);
 #pragma unroll
-    for (int n = 0; n < NT; ++n) cpi[n] = mzw_policy(pl[0][n], lane);
+    for (int n = 0; n < NC; ++n) C.cpi[n] = mzw_policy(pl[0][n], lane);
     MZH_STAMP(8);
-    mzw_chain<NT, 4, NOV, false, SUP33, 8>(net.val, rw, hreg, noh, vl, b2, lane, v32, wst, net.dyn.soff);  // + next dyn block 0
-    mzw_bias2<NT, NOV>(vl, b2);
+    mzw_chain<NC, 4, NOV, false, SUP33, 8>(net.val, rw, hreg, nohc, vl, b2, lane, v32, wst, net.dyn.soff);  // + next dyn block 0
+    mzw_bias2<NC, NOV>(vl, b2);
     MZH_STAMP(9);
 #pragma unroll
-    for (int n = 0; n < NT; ++n) val[n] = mzw_head<NT, NOV>(vl, n, lane, SUP33 ? v32[n] : 0.0f, net.val.b32);
+    for (int n = 0; n < NC; ++n) C.val[n] = mzw_head<NC, NOV>(vl, n, lane, SUP33 ? v32[n] : 0.0f, net.val.b32);
+  };
+
+  // the new nodes' blocks of the columns an M phase evaluated
+  auto phase_blocks = [&](int s, auto& C) {
+    constexpr int NC = sizeof(C.root) / sizeof(int);
+    // the new node's 6 children (node.py:44-49): N = 0, X = -1, R = 0, P, W = 0.  The whole 128-B
+    // line as eight 16-B stores, two per lane group (lane groups 0/1 hold pi[0..3] / pi[4..5]):
+    // a line written whole is valid in L2 without a fill from HBM.  Chunk k = bytes 16k..16k+15:
+    // 0 nx0-3 | 1 nx4,5 R0,1 | 2 R2-5 | 3 P0-3 | 4 P4,5 W0 | 5 W1,2 | 6 W3,4 | 7 W5 pad
+#pragma unroll
+    for (int n = 0; n < NC; ++n) {
+      if (!C.valid[n]) continue;
+      uint4* nb = reinterpret_cast<uint4*>(reinterpret_cast<MzwBlock*>(p.tree) + (size_t)C.root[n] * E + s + 1);
+      const uint32_t nx = 0xFFFF0000u;  // N = 0, X = -1
+      uint4 c0, c1;
+      if (g == 0) {
+        c0 = make_uint4(nx, nx, nx, nx);
+        c1 = make_uint4(__float_as_uint(C.cpi[n][0]), __float_as_uint(C.cpi[n][1]), __float_as_uint(C.cpi[n][2]),
+                        __float_as_uint(C.cpi[n][3]));
+      } else if (g == 1) {
+        c0 = make_uint4(nx, nx, 0u, 0u);
+        c1 = make_uint4(__float_as_uint(C.cpi[n][0]), __float_as_uint(C.cpi[n][1]), 0u, 0u);
+      } else {
+        c0 = make_uint4(0u, 0u, 0u, 0u);
+        c1 = c0;
+      }
+      // g0: chunks 0, 3; g1: chunks 1, 4; g2: chunks 2, 5; g3: chunks 6, 7
+      const int k0 = g < 3 ? g : 6, k1 = g < 3 ? g + 3 : 7;
+      nb[k0] = c0;
+      nb[k1] = c1;
+    }
   };
 
   // the new node's block, then backup (node.py:30-70)
-  auto phase_head = [&](int s) {
-    if (!REPLAY) {
-      // the new node's 6 children (node.py:44-49): N = 0, X = -1, R = 0, P, W = 0.  The whole 128-B
-      // line as eight 16-B stores, two per lane group (lane groups 0/1 hold pi[0..3] / pi[4..5]):
-      // a line written whole is valid in L2 without a fill from HBM.  Chunk k = bytes 16k..16k+15:
-      // 0 nx0-3 | 1 nx4,5 R0,1 | 2 R2-5 | 3 P0-3 | 4 P4,5 W0 | 5 W1,2 | 6 W3,4 | 7 W5 pad
-#pragma unroll
-      for (int n = 0; n < NT; ++n) {
-        if (!cvalid[n]) continue;
-        uint4* nb = reinterpret_cast<uint4*>(reinterpret_cast<MzwBlock*>(p.tree) + (size_t)croot[n] * E + s + 1);
-        const uint32_t nx = 0xFFFF0000u;  // N = 0, X = -1
-        uint4 c0, c1;
-        if (g == 0) {
-          c0 = make_uint4(nx, nx, nx, nx);
-          c1 = make_uint4(__float_as_uint(cpi[n][0]), __float_as_uint(cpi[n][1]), __float_as_uint(cpi[n][2]),
-                          __float_as_uint(cpi[n][3]));
-        } else if (g == 1) {
-          c0 = make_uint4(nx, nx, 0u, 0u);
-          c1 = make_uint4(__float_as_uint(cpi[n][0]), __float_as_uint(cpi[n][1]), 0u, 0u);
-        } else {
-          c0 = make_uint4(0u, 0u, 0u, 0u);
-          c1 = c0;
-        }
-        // g0: chunks 0, 3; g1: chunks 1, 4; g2: chunks 2, 5; g3: chunks 6, 7
-        const int k0 = g < 3 ? g : 6, k1 = g < 3 ? g + 3 : 7;
-        nb[k0] = c0;
-        nb[k1] = c1;
-      }
-    }
+  // fromrec (root lanes): the new node's outputs come from a 32-byte record -- the replay records, or the
+  // memo's row of a root that hit it in a simulation that ran no MLP for it; else vcol / rcol: the value and
+  // reward its column evaluated
+  auto phase_head = [&](int s, bool fromrec, float vcol, float rcol) {
     // ---------------- expand bookkeeping + backup (node.py:30-70): one lane per root ----------------
     if (rvalid) {
       const int enew = s + 1;
       float vv, rr;
-      if (REPLAY) {
-        const uint4* rec = reinterpret_cast<const uint4*>(p.rp_sim + ((size_t)s * p.B + rroot) * 8);
+      if (REPLAY || fromrec) {
+        const uint4* rec = reinterpret_cast<const uint4*>(
+            REPLAY ? p.rp_sim + ((size_t)s * p.B + rroot) * 8
+                   : p.memo_rec + ((size_t)sigma * p.memo_K + (6u * pid + (unsigned)leafA + 1u)) * 8);
         const uint4 r0 = rec[0], r1 = rec[1];  // priors 0-3 | priors 4, 5, reward, value
         rr = __uint_as_float(r1.z);
         vv = __uint_as_float(r1.w);
@@ -786,15 +831,8 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
         nb[6] = z;
         nb[7] = z;
       } else {
-        // root lane rho is column rho & 15 of tile rho >> 4 (every row of a column holds its scalars)
-        vv = val[0];
-        rr = rew[0];
-#pragma unroll
-        for (int n = 1; n < NT; ++n)
-          if ((rho >> 4) == n) {
-            vv = val[n];
-            rr = rew[n];
-          }
+        vv = vcol;
+        rr = rcol;
       }
       if (leafE == 0) {
         ws.rX[leafA][rho] = enew;
@@ -886,10 +924,72 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
     // a wave in its matrix phase wins VALU issue arbitration over the co-resident wave's tree work
     // (measured against the tree phases first and against no priorities: profiles/r04_experiments.json)
     __builtin_amdgcn_s_setprio(1);
-    phase_mlp(s);
+    // Which M phase the simulation needs (wave-uniform).  A root misses the memo when its observation is not a
+    // state's (sigma < 0) or its new node lies deeper than the table.  mode 0: no root misses, no chain runs;
+    // mode 1 (32-root waves): at most 16 miss and are packed into one column tile -- half the MFMAs, in-chain
+    // epilogues and heads; mode 2: the wave's own tiles, as without a memo (the hits are evaluated too)
+    int mode = 2, nm = 0;
+    unsigned mask = 0;
+    bool hit = false;
+    if (memo) {
+      hit = rvalid && sigma >= 0 && depth <= p.memo_D;
+      // bit rho: lanes 0-31 (lanes 32-63 mirror them)
+      mask = __builtin_amdgcn_readfirstlane((unsigned)__ballot(rvalid && !hit));
+      nm = __popc(mask);
+      mode = nm == 0 ? 0 : (NT == 2 && nm <= 16) ? 1 : 2;
+      cnt = __builtin_amdgcn_readfirstlane(cnt + (mode == 0 ? 1u : mode == 1 ? 0x10000u : 0u));
+    }
+    // the parent's memo row (root lanes): a memo node's latent is read from the table, never from htree
+    const int prow_r = (memo && sigma >= 0 && depth - 1 <= p.memo_D) ? sigma * p.memo_K + (int)pid : -1;
+    float vcol = 0.0f, rcol = 0.0f;
+    if (mode == 2) {
+      if (!REPLAY) {
+#pragma unroll
+        for (int n = 0; n < NT; ++n) {
+          cf.en[n] = __shfl(leafE, 16 * n + col);
+          cf.an[n] = __shfl(leafA, 16 * n + col);
+          if (memo) cf.prow[n] = __shfl(prow_r, 16 * n + col);
+        }
+        phase_mlp(s, cf);
+        // root lane rho is column rho & 15 of tile rho >> 4 (every row of a column holds its scalars)
+        vcol = cf.val[0];
+        rcol = cf.rew[0];
+#pragma unroll
+        for (int n = 1; n < NT; ++n)
+          if ((rho >> 4) == n) {
+            vcol = cf.val[n];
+            rcol = cf.rew[n];
+          }
+      }
+    } else if constexpr (NT == 2) {
+     if (mode == 1) {
+      // pack: the c-th missing root (ascending rho) becomes column c.  A lane permutation sends each missing
+      // root lane's rho to lane rank = missing roots below it; the other lanes of rows 0-31 fill nm..31 and
+      // lanes 32-63 stay, so every lane is written exactly once
+      const int rank = __popc(mask & ((1u << rho) - 1u));
+      const bool missl = (mask >> rho) & 1u;
+      const int dest = half ? lane : (missl ? rank : nm + rho - rank);
+      const int rsel = __builtin_amdgcn_ds_permute(dest << 2, rho);
+      const bool pv = col < nm;
+      const int rs = __shfl(rsel, col);
+      const int r = pv ? rs : (int)__builtin_ctz(mask);  // spare columns repeat the first missing root
+      cp.root[0] = wr0 + r;
+      cp.valid[0] = pv;
+      cp.en[0] = __shfl(leafE, r);
+      cp.an[0] = __shfl(leafA, r);
+      cp.prow[0] = __shfl(prow_r, r);
+      phase_mlp(s, cp);
+      vcol = __shfl(cp.val[0], rank);  // a missing root's column is its rank (every row holds the scalars)
+      rcol = __shfl(cp.rew[0], rank);
+     }
+    }
     __builtin_amdgcn_s_setprio(0);
     MZH_STAMP(1);
-    phase_head(s);
+    if (!REPLAY) {
+      if (mode == 2) phase_blocks(s, cf);
+      else if (NT == 2 && mode == 1) phase_blocks(s, cp);  // (cp is never valid in a 16-root wave)
+    }
+    phase_head(s, mode != 2 && hit, vcol, rcol);
     MZH_STAMP(2);
     // this simulation's tree stores (other lanes' new-block writes) before the next selection
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
@@ -898,6 +998,12 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
 
   // ---------------- results (mcts.py:111-126, 154-176) ----------------
   if (p.lockstep_levels && lane == 0) p.lockstep_levels[blockIdx.x * MZW_WAVES + wave] = lsum;
+  if (memo && lane == 0) {  // one vector atomic per counter and wave
+    const unsigned nskip = cnt & 0xFFFFu, npack = cnt >> 16;
+    atomicAdd(p.memo_cnt + 0, (unsigned long long)nskip);
+    atomicAdd(p.memo_cnt + 1, (unsigned long long)npack);
+    atomicAdd(p.memo_cnt + 2, (unsigned long long)((unsigned)S - nskip - npack));
+  }
   if (!rvalid || half) return;
   int vis[MZH_A];
   for (int a = 0; a < MZH_A; ++a) vis[a] = ws.rN[a][rho];
@@ -930,6 +1036,48 @@ static hipError_t launch_wave_nt(const MzhSearchPlan& pl, const MzhWNet& net, co
 
 hipError_t mzh_launch_wave_search(const MzhSearchPlan& pl, const MzhWNet& net, const MzhSearchParams& p, hipStream_t stream) {
   return pl.nt == 1 ? launch_wave_nt<1>(pl, net, p, stream) : launch_wave_nt<2>(pl, net, p, stream);
+}
+
+// ------------------------------------------------------------------------------------------
+// Expansion-memo fill (mzh_api.hip memo_build).  Level rows are ordered (state, node): row r of a level is
+// move r % 6 from row r / 6 of the level above.
+// ------------------------------------------------------------------------------------------
+// the level's recurrent-inference input: parent latents (natural unit order) repeated per move, and the moves
+__global__ __launch_bounds__(256) void mzh_memo_level_kernel(const float4* hprev, float4* xin, int32_t* act, long long n) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;  // one float4 of one row
+  if (i >= n * 16) return;
+  const long long r = i >> 4;
+  xin[i] = hprev[(r / 6) * 16 + (i & 15)];
+  if ((i & 15) == 0) act[r] = (int32_t)(r % 6);
+}
+// a level's outputs into the table: row = state * K + first_id + node, the latent in htree's order (position
+// 16kb + 4g + t holds unit 16kb + 4t + g, what the wave kernel's B operand gathers), the record as replay's
+__global__ __launch_bounds__(256) void mzh_memo_scatter_kernel(const float* h, const float* pi, const float* reward,
+                                                               const float* value, long long n, long long per_state,
+                                                               long long K, long long first_id, float* memo_h,
+                                                               float* memo_rec) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;  // one latent position of one row
+  if (i >= n * 64) return;
+  const long long r = i >> 6;
+  const int pos = (int)(i & 63);
+  const long long row = (r / per_state) * K + first_id + (r % per_state);
+  const int kb = pos >> 4, gg = (pos >> 2) & 3, t = pos & 3;
+  memo_h[row * 64 + pos] = h[r * 64 + 16 * kb + 4 * t + gg];
+  if (pos < 8) memo_rec[row * 8 + pos] = pos < 6 ? pi[r * 6 + pos] : pos == 6 ? reward[r] : value[r];
+}
+hipError_t mzh_launch_memo_level(const float* hprev, float* xin, int32_t* act, long long n, hipStream_t stream) {
+  const long long blocks = (n * 16 + 255) / 256;
+  hipLaunchKernelGGL(mzh_memo_level_kernel, dim3((unsigned)blocks), dim3(256), 0, stream,
+                     reinterpret_cast<const float4*>(hprev), reinterpret_cast<float4*>(xin), act, n);
+  return hipGetLastError();
+}
+hipError_t mzh_launch_memo_scatter(const float* h, const float* pi, const float* reward, const float* value, long long n,
+                                   long long per_state, long long K, long long first_id, float* memo_h, float* memo_rec,
+                                   hipStream_t stream) {
+  const long long blocks = (n * 64 + 255) / 256;
+  hipLaunchKernelGGL(mzh_memo_scatter_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, h, pi, reward, value, n,
+                     per_state, K, first_id, memo_h, memo_rec);
+  return hipGetLastError();
 }
 
 #ifdef MZH_STAMPS

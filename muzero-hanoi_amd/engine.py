@@ -177,6 +177,33 @@ class Engine:
                                            self._stream()), "mzh_probe_actions")
         return out
 
+    # ---------------------------------------------------------------- expansion memo (wave kernel)
+    def set_memo_depth(self, depth):
+        """mzh_set_memo_depth: -1 automatic (default), 0 off, d > 0 forced; takes effect with the next search"""
+        check(_lib.lib().mzh_set_memo_depth(self._h, int(depth)), "mzh_set_memo_depth")
+
+    def memo_stats(self):
+        """mzh_memo_stats as a dict: depth, built, rows, table_bytes, build_ms and the cumulative
+        pairs_skipped / pairs_packed / pairs_full of the wave searches (waits for the device)"""
+        info = _lib.MemoInfo()
+        check(_lib.lib().mzh_memo_stats(self._h, ctypes.byref(info)), "mzh_memo_stats")
+        return info.as_dict()
+
+    def memo_table(self):
+        """debug: copies of the built table as (latent [rows, 64] in natural unit order, record [rows, 8], depth);
+        None before the first wave search built it.  Row = state * K(depth) + memo_node_id(path)."""
+        rows, depth = ctypes.c_int64(), ctypes.c_int32()
+        fn = _lib.lib().mzh_memo_debug_table
+        check(fn(self._h, None, None, ctypes.byref(rows), ctypes.byref(depth)), "mzh_memo_debug_table")
+        n = rows.value
+        if n == 0:
+            return None
+        h, rec = self._f32(n, LATENT), self._f32(n, 8)
+        check(fn(self._h, ptr(h), ptr(rec), ctypes.byref(rows), ctypes.byref(depth)), "mzh_memo_debug_table")
+        # the wave kernel's order: position 16kb + 4g + t holds unit 16kb + 4t + g
+        h = h.view(n, 4, 4, 4).transpose(2, 3).reshape(n, LATENT).contiguous()
+        return h, rec, depth.value
+
     # ---------------------------------------------------------------- search
     def alloc_search_outputs(self, B, n_sims, lockstep=False):
         """lockstep=True adds lockstep_levels (zeroed, one entry per group of roots that advance together: at most
@@ -298,6 +325,26 @@ class Engine:
         out["_keep"] = keep
         out["_plan_struct"] = plan
         return a, out
+
+
+def memo_node_id(path):
+    """the expansion memo's node id of an action path: id(()) = 0, id(path + (a,)) = 6 id(path) + a + 1"""
+    i = 0
+    for a in path:
+        if not 0 <= int(a) < ACTIONS:
+            raise ValueError(f"action {a} outside [0, {ACTIONS})")
+        i = 6 * i + int(a) + 1
+    return i
+
+
+def memo_nodes(depth):
+    """nodes per state of a depth-D memo: K(D) = 1 + 6 + ... + 6^D"""
+    return (6 ** (depth + 1) - 1) // 5
+
+
+def memo_state_index(pegs):
+    """a state's index in the memo: sum of peg(disc i) 3^i"""
+    return sum(int(p) * 3 ** i for i, p in enumerate(pegs))
 
 
 def search_flags(kernel=None, tile=None, np1_ucb=False):

@@ -9,6 +9,12 @@ the medians, and whether B's median is below A's by more than `--bar` times A's 
 
 --dump-dir: the first run of each leg also writes its outputs (bench.py --dump-outputs) to DIR/a, DIR/b;
 the record then says whether every array is byte-identical, and the dumps are removed.
+--a-root DIR: leg A runs DIR/bench.py on DIR's own package and built library (a checkout of the parent commit),
+for a parent whose library this tree's binding no longer loads (new entry points); --a is then only named.
+--env-b K=V: an environment variable of leg B's children alone (repeatable).
+--memo: after the legs, one search of the config's roots in this process on this tree's library and the record of
+its expansion memo beside leg B (tools/memo_depth_ab.py stats: automatic depth, table bytes, the build's time on
+the host's clock, the share of each M-phase form).
 """
 import argparse
 import filecmp
@@ -21,12 +27,18 @@ import sys
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 
 
-def bench(lib, args, limit, dump=None):
+def bench(lib, args, limit, dump=None, root=None, extra_env=()):
     env = dict(os.environ, MZH_LIB=os.path.abspath(lib))
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), *args] + (["--dump-outputs", dump] if dump else [])
-    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=limit)
+    if root is not None:  # that tree's bench.py, package and library
+        root = os.path.abspath(root)
+        env.pop("MZH_LIB")
+        env["PYTHONPATH"] = root
+    env.update(kv.split("=", 1) for kv in extra_env)
+    cmd = [sys.executable, os.path.join(root or ROOT, "bench.py"), *args] + (["--dump-outputs", dump] if dump else [])
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=limit, cwd=root or ROOT)
     if r.returncode != 0:
         raise SystemExit(f"bench.py failed ({r.returncode}) with {lib}:\n{r.stderr[-2000:]}")
     return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -41,6 +53,9 @@ def main():
     ap.add_argument("--limit", type=float, default=300.0, help="seconds per bench.py child")
     ap.add_argument("--out", default=None)
     ap.add_argument("--dump-dir", default=None)
+    ap.add_argument("--a-root", default=None, help="a checkout whose own bench.py, package and library are leg A")
+    ap.add_argument("--memo", action="store_true", help="record this tree's expansion memo beside leg B")
+    ap.add_argument("--env-b", action="append", default=[], metavar="K=V", help="environment of leg B only")
     ap.add_argument("bench_args", nargs="*")
     a = ap.parse_args()
     libs = (a.a, a.b)
@@ -49,8 +64,8 @@ def main():
         for leg in (0, 1, 1, 0):
             dump = None
             if a.dump_dir and lines[leg] is None:
-                dump = os.path.join(a.dump_dir, "ab"[leg])
-            d = bench(libs[leg], a.bench_args, a.limit, dump)
+                dump = os.path.abspath(os.path.join(a.dump_dir, "ab"[leg]))
+            d = bench(libs[leg], a.bench_args, a.limit, dump, a.a_root if leg == 0 else None, a.env_b if leg == 1 else ())
             lines[leg] = lines[leg] or d
             ms[leg].append(d["roofline"]["kernel_ms"])
             print(f"round {rnd} {'AB'[leg]} {ms[leg][-1]:.4f} ms", file=sys.stderr, flush=True)
@@ -68,6 +83,17 @@ def main():
            "ratio_median": sb["median"] / sa["median"], "gain_ms": sa["median"] - sb["median"],
            "bar_ms": a.bar * sa["spread"], "b_faster_beyond_bar": sa["median"] - sb["median"] > a.bar * sa["spread"],
            "b_slower_beyond_a_spread": sb["median"] - sa["median"] > sa["spread"]}
+    if a.env_b:
+        rec["b"]["env"] = a.env_b
+    if a.memo:
+        sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+        import memo_depth_ab
+        from muzero_hanoi_amd import _lib
+
+        cfg = lines[1]["config"]
+        d = _lib.memo_plan(cfg["n_disks"], -1)["depth"]
+        rec["b"]["memo"] = dict(memo_depth_ab.stats([d], cfg["n_disks"], cfg["roots_per_gpu"], cfg["sims_per_move"], 0)
+                                .get(str(d), {}), depth=d)
     if a.dump_dir:
         da, db = os.path.join(a.dump_dir, "a"), os.path.join(a.dump_dir, "b")
         names = sorted(os.listdir(da))
