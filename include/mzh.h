@@ -421,6 +421,45 @@ typedef struct mzh_probe_args {
 int mzh_probe_actions(mzh_engine* eng, const mzh_probe_args* args, const mzh_multi_args* multi /* nullable */,
                       mzh_stream stream);
 
+/* Input saliency (monosemanticity_analysis/gradient_analysis.py compute_saliency, lines 354-391): per row
+ * d(policy logit k)/d(obs) and d(value)/d(obs) through represent + prediction (networks.py:71-94), in one
+ * launch (mzh_saliency_kernel; with `multi` mzh_saliency_multi_kernel).  k is logit_index[env] where that is
+ * given and >= 0, else the lowest index of the row's largest fp32 policy logit.  The forward is
+ * mzh_initial_inference's (h0 / pi0 / value0 are bit-identical to it); the backward runs the six layers
+ * transposed as fp32 MFMA products, the ReLU masks of the forward's hidden tiles, normalize_h_state's backward
+ * with its min and max differentiable (lowest index on a tie) and, for a 33-bin value head, the softmax
+ * expectation and the signed parabolic transform as autograd differentiates them.  A row's outputs depend on
+ * that row and its network alone: the same bits in any position, at either tile size, with or without
+ * env_index, single network or set.  Rows, env_index, `multi`, the tile table and the grid are
+ * mzh_probe_actions'; every array but env_index (and multi's net_index) is indexed by env, rows outside the
+ * call are left untouched.
+ * MZH_ERR_ARG, before any launch and before a device or an engine is needed: a NULL required pointer (args,
+ * obs, sal_policy, sal_value), n < 1, B < 1 (B < n without env_index), a flag other than
+ * MZH_FLAG_COOP_TILE16 / 32 (default tile: 16 rows while n <= 4096, else 32); with multi a NULL net_index or
+ * n_networks outside [1, 256]; then a NULL engine, and n_networks above the loaded set's M.
+ * MZH_ERR_STATE: weights not loaded (without multi), no set loaded (with multi).  MZH_ERR_CAPACITY: n > max_roots.
+ * On the device: a row whose env index is outside [0, B), or whose logit_index entry is outside [-1, 6), is
+ * skipped and adds 1 to *err_count; a refused net_index writes nothing and sets multi->status[0] = 1. */
+typedef struct mzh_saliency_args {
+  int32_t B;                  /* envs of the full batch */
+  int32_t n;                  /* rows of this call */
+  uint32_t flags;             /* MZH_FLAG_COOP_TILE16 / 32 only */
+  const int32_t* env_index;   /* [n] or NULL: row j is env env_index[j] (distinct), else env j */
+  const float* obs;           /* [B][3 n_disks], indexed by env */
+  const int32_t* logit_index; /* [B] nullable: the policy logit differentiated, -1 = the row's argmax */
+  float* sal_policy;          /* [B][3 n_disks] d(policy logit k)/d(obs) */
+  float* sal_value;           /* [B][3 n_disks] d(value)/d(obs) */
+  int32_t* picked;            /* [B] nullable: k */
+  float* disc_policy;         /* [B][n_disks] nullable: (|s0| + |s1|) + |s2| of each disc's three elements */
+  float* disc_value;          /* [B][n_disks] nullable */
+  float* h0;                  /* [B][64] nullable: root latent */
+  float* pi0;                 /* [B][6]  nullable: root policy */
+  float* value0;              /* [B]     nullable: root value  */
+  int32_t* err_count;         /* nullable: += 1 per skipped row */
+} mzh_saliency_args;
+int mzh_saliency(mzh_engine* eng, const mzh_saliency_args* args, const mzh_multi_args* multi /* nullable */,
+                 mzh_stream stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Reference-order host pre-draw (HOST pointers only; no device, no engine).  Replaces the NumPy
  * calls B sequential run_mcts calls make on the global legacy stream, in their order per call:

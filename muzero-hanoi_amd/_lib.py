@@ -131,6 +131,14 @@ class ProbeArgs(ctypes.Structure):
                 ("h0", _vp), ("pi0", _vp), ("value0", _vp), ("h1", _vp), ("pi1", _vp), ("err_count", _vp)]
 
 
+class SaliencyArgs(ctypes.Structure):
+    """mirror of struct mzh_saliency_args (include/mzh.h)"""
+    _fields_ = [("B", _i32), ("n", _i32), ("flags", ctypes.c_uint32),
+                ("env_index", _vp), ("obs", _vp), ("logit_index", _vp), ("sal_policy", _vp), ("sal_value", _vp),
+                ("picked", _vp), ("disc_policy", _vp), ("disc_value", _vp),
+                ("h0", _vp), ("pi0", _vp), ("value0", _vp), ("err_count", _vp)]
+
+
 # name -> (restype, argtypes); every symbol include/mzh.h declares
 SIGNATURES = {
     "mzh_abi_version": (ctypes.c_int, []),
@@ -157,6 +165,7 @@ SIGNATURES = {
     "mzh_search_replay": (ctypes.c_int, [_vp, ctypes.POINTER(SearchArgs), _vp]),
     "mzh_search_multi": (ctypes.c_int, [_vp, ctypes.POINTER(SearchArgs), ctypes.POINTER(MultiArgs), _vp]),
     "mzh_probe_actions": (ctypes.c_int, [_vp, ctypes.POINTER(ProbeArgs), ctypes.POINTER(MultiArgs), _vp]),
+    "mzh_saliency": (ctypes.c_int, [_vp, ctypes.POINTER(SaliencyArgs), ctypes.POINTER(MultiArgs), _vp]),
     "mzh_search_plan_query": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int,
                                              ctypes.c_int, ctypes.POINTER(SearchPlan)]),
     "mzh_set_memo_depth": (ctypes.c_int, [_vp, ctypes.c_int]),

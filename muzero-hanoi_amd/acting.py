@@ -19,6 +19,10 @@ fused kernel launch, every env step the integer kernel).
                        of the six moves at every decision, legal minus illegal; one mzh_probe_actions launch per
                        decision); legality_summary is its statistics, shared with selfplay.evaluate_legality
 
+  compute_saliency / aggregate_saliency_per_disk  monosemanticity_analysis/gradient_analysis.py:354-391 / 569-592
+                       (d(policy logit at its argmax)/d(obs) and d(value)/d(obs) of one state: one mzh_saliency
+                       launch; selfplay.evaluate_saliency is the batched form over states and networks)
+
 They run one decision at a time, exactly as the reference does (same RNG stream, same MinMaxStats
 chain); selfplay.evaluate is the batched form (sequential=True reproduces get_results, and with
 max_plan_len plan_multiple_actions; selfplay.evaluate_perturbed batches the two perturbation scripts).
@@ -331,3 +335,25 @@ def permutation_run_evaluation(networks, env, test_states, max_game_steps, mcts,
         if permutation_play_game(networks, env, start_state, max_game_steps, mcts, permute_feature):
             solved_count += 1
     return solved_count / len(test_states)
+
+
+# ---------------------------------------------------------------------- gradient_analysis.py
+def compute_saliency(state, N, networks, action):
+    """gradient_analysis.py:354-391: {"policy": d(policy logit at its argmax)/d(obs), "value": d(value)/d(obs)},
+    float32 [3N] each, through represent + prediction -- forward and backward one mzh_saliency launch.  `action`
+    is accepted and unused, as in the reference (its dummy action only feeds the commented-out heads)."""
+    eng = engine_for(networks, 0, 1)
+    obs = torch.as_tensor(oneHot_encoding(state, n_integers=3), dtype=torch.float32)[None].to(eng.device)
+    if obs.shape[1] != 3 * N or eng.n_disks != N:
+        raise ValueError(f"compute_saliency: a state of {len(state)} discs on a {eng.n_disks}-disc network, N={N}")
+    out = eng.saliency(obs)
+    return {"policy": out["policy"][0].cpu().numpy(), "value": out["value"][0].cpu().numpy()}
+
+
+def aggregate_saliency_per_disk(saliency_vector, num_disks=3, num_rods=3):
+    """gradient_analysis.py:569-592: sum of |.| over each disc's `num_rods` elements, a list ordered small to
+    large (the kernel's disc_policy / disc_value outputs are this sum in fp32, (|s0| + |s1|) + |s2|)."""
+    if len(saliency_vector) != num_disks * num_rods:
+        raise ValueError("Saliency vector length does not match num_disks * num_rods.")
+    v = np.asarray(saliency_vector)
+    return [np.sum(np.abs(v[i * num_rods:(i + 1) * num_rods])) for i in range(num_disks)]

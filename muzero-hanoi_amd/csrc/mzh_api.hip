@@ -83,6 +83,12 @@ struct mzh_engine {
   float* memo_rec = nullptr;   // [rows][8]
   unsigned long long* memo_cnt = nullptr;  // [3] device counters, zeroed by mzh_create
   double memo_build_ms = 0.0;
+  // the transposed blobs of mzh_saliency (MzhPackedT; allocations of their own, uploaded with the weights they
+  // are a function of and dropped with them)
+  void* tbuf = nullptr;
+  MzhSalNetT tnet{};
+  void* settbuf = nullptr;
+  MzhSalNetT settnet{};
 };
 
 extern "C" int mzh_abi_version(void) { return MZH_ABI_VERSION; }
@@ -194,6 +200,8 @@ extern "C" int mzh_destroy(mzh_engine* eng) {
   if (eng->memo_h) (void)hipFree(eng->memo_h);
   if (eng->memo_rec) (void)hipFree(eng->memo_rec);
   if (eng->memo_cnt) (void)hipFree(eng->memo_cnt);
+  if (eng->tbuf) (void)hipFree(eng->tbuf);
+  if (eng->settbuf) (void)hipFree(eng->settbuf);
   delete eng;
   return MZH_OK;
 }
@@ -240,12 +248,24 @@ static int make_net(const MzhPacked& pk, const float* base, int sup, int in, Mzh
   return MZH_OK;
 }
 
+// the saliency kernel's view of a transposed blob uploaded at `base` (`stride` bytes between a set's members)
+static MzhSalNetT make_tnet(const MzhPackedT& t, const void* base, size_t stride) {
+  MzhSalNetT n{};
+  n.base = static_cast<const float4*>(base);
+  for (int i = 0; i < MZH_T_LAYERS; ++i) n.off[i] = (int)(t.off[i] / 4);
+  n.kb_val2 = t.kb[MZH_T_VAL2];
+  n.nt_rep0 = t.nt[MZH_T_REP0];
+  n.stride = stride;
+  return n;
+}
+
 extern "C" int mzh_load_weights(mzh_engine* eng, const float* flat, size_t n_floats) {
   if (!eng || !flat) return fail(MZH_ERR_ARG, "engine or weights NULL");
   const int in = eng->in_dim, sup = eng->support;
   const size_t want = mzh_canon_view(nullptr, in, sup).total;
   if (n_floats != want) return fail(MZH_ERR_ARG, "weights: expected %zu floats, got %zu", want, n_floats);
   const MzhPacked pk = mzh_pack_network(mzh_canon_view(flat, in, sup));
+  const MzhPackedT pt = mzh_pack_transposed(mzh_canon_view(flat, in, sup));
 
   DeviceGuard g(eng->device);
   if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
@@ -254,10 +274,15 @@ extern "C" int mzh_load_weights(mzh_engine* eng, const float* flat, size_t n_flo
     HIP_OK(hipFree(eng->wbuf));
     eng->wbuf = nullptr;
     eng->loaded = false;
+    if (eng->tbuf) HIP_OK(hipFree(eng->tbuf));
+    eng->tbuf = nullptr;
   }
   HIP_OK(memo_drop(eng));  // the table is a function of the weights
   HIP_OK(hipMalloc(&eng->wbuf, pk.blob.size() * sizeof(float)));
   HIP_OK(hipMemcpy(eng->wbuf, pk.blob.data(), pk.blob.size() * sizeof(float), hipMemcpyHostToDevice));
+  HIP_OK(hipMalloc(&eng->tbuf, pt.blob.size() * sizeof(float)));
+  HIP_OK(hipMemcpy(eng->tbuf, pt.blob.data(), pt.blob.size() * sizeof(float), hipMemcpyHostToDevice));
+  eng->tnet = make_tnet(pt, eng->tbuf, 0);
   const float* base = static_cast<const float*>(eng->wbuf);
   const int nst = make_net(pk, base, sup, in, &eng->net);
   if (nst) return nst;
@@ -302,6 +327,7 @@ extern "C" int mzh_load_weight_set(mzh_engine* eng, const float* flat, size_t n_
   const size_t want = mzh_canon_view(nullptr, in, sup).total;
   if (n_floats != want) return fail(MZH_ERR_ARG, "weight set: expected %zu floats per network, got %zu", want, n_floats);
   const MzhPackedSet ps = mzh_pack_network_set(flat, M, in, sup);
+  const MzhPackedTSet pts = mzh_pack_transposed_set(flat, M, in, sup);
 
   DeviceGuard g(eng->device);
   if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
@@ -310,12 +336,17 @@ extern "C" int mzh_load_weight_set(mzh_engine* eng, const float* flat, size_t n_
     HIP_OK(hipFree(eng->setbuf));
     eng->setbuf = nullptr;
     eng->set_m = 0;
+    if (eng->settbuf) HIP_OK(hipFree(eng->settbuf));
+    eng->settbuf = nullptr;
   }
   if (!eng->mtiles)
     HIP_OK(hipMalloc(&eng->mtiles, sizeof(MzhTile) * (size_t)mzh_multi_max_tiles(eng->max_roots, 16, MZH_MULTI_MAX_NETS)));
   if (!eng->mntiles) HIP_OK(hipMalloc(&eng->mntiles, sizeof(int32_t)));
   HIP_OK(hipMalloc(&eng->setbuf, ps.blob.size() * sizeof(float)));
   HIP_OK(hipMemcpy(eng->setbuf, ps.blob.data(), ps.blob.size() * sizeof(float), hipMemcpyHostToDevice));
+  HIP_OK(hipMalloc(&eng->settbuf, pts.blob.size() * sizeof(float)));
+  HIP_OK(hipMemcpy(eng->settbuf, pts.blob.data(), pts.blob.size() * sizeof(float), hipMemcpyHostToDevice));
+  eng->settnet = make_tnet(pts.layout, eng->settbuf, pts.stride * sizeof(float));
   const float* base = static_cast<const float*>(eng->setbuf);
   const int nst = make_net(ps.layout, base, sup, in, &eng->setnet);
   if (nst) return nst;
@@ -938,6 +969,57 @@ extern "C" int mzh_probe_actions(mzh_engine* eng, const mzh_probe_args* a, const
     e = mzh_launch_probe(R, eng->net, p, nullptr, (hipStream_t)stream);
   }
   return e == hipSuccess ? MZH_OK : hip_fail(e, "probe_actions launch");
+}
+
+// Input saliency of the policy and value heads of a batch of rows in one launch (mzh_saliency_kernel; with `m`
+// the rows of a loaded network set, mzh_saliency_multi_kernel).  Refusals in mzh_probe_actions' order: what the
+// arguments alone decide first, so those need neither a device nor an engine.
+extern "C" int mzh_saliency(mzh_engine* eng, const mzh_saliency_args* a, const mzh_multi_args* m, mzh_stream stream) {
+  if (!a) return fail(MZH_ERR_ARG, "saliency: args is NULL");
+  if (a->n < 1 || a->B < 1 || (!a->env_index && a->B < a->n))
+    return fail(MZH_ERR_ARG, "saliency: bad n=%d rows for B=%d envs", a->n, a->B);
+  if (!a->obs || !a->sal_policy || !a->sal_value)
+    return fail(MZH_ERR_ARG, "saliency: required buffer is NULL (obs, sal_policy, sal_value)");
+  if (a->flags & ~(MZH_FLAG_COOP_TILE16 | MZH_FLAG_COOP_TILE32))
+    return fail(MZH_ERR_ARG, "saliency: flags=0x%x, only MZH_FLAG_COOP_TILE16 / 32 apply", a->flags);
+  if (m) {
+    if (!m->net_index) return fail(MZH_ERR_ARG, "saliency: net_index is NULL");
+    if (m->n_networks < 1 || m->n_networks > MZH_MULTI_MAX_NETS)
+      return fail(MZH_ERR_ARG, "saliency: n_networks=%d outside [1, %d]", m->n_networks, MZH_MULTI_MAX_NETS);
+  }
+  if (!eng) return fail(MZH_ERR_ARG, "saliency: engine NULL");
+  if (m) {
+    if (eng->set_m == 0) return fail(MZH_ERR_STATE, "no weight set loaded (mzh_load_weight_set)");
+    if (m->n_networks > eng->set_m)
+      return fail(MZH_ERR_ARG, "saliency: n_networks=%d outside [1, %d], the loaded set", m->n_networks, eng->set_m);
+  } else if (!eng->loaded) {
+    return fail(MZH_ERR_STATE, "weights not loaded");
+  }
+  if (a->n > eng->max_roots) return fail(MZH_ERR_CAPACITY, "saliency: n=%d > max_roots=%d", a->n, eng->max_roots);
+  DeviceGuard g(eng->device);
+  if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+  MzhSalParams p{};
+  p.B = a->B; p.n = a->n; p.in_dim = eng->in_dim; p.kin = eng->kin; p.n_disks = eng->n_disks;
+  p.env_index = a->env_index; p.obs = a->obs; p.logit_index = a->logit_index;
+  p.sal_policy = a->sal_policy; p.sal_value = a->sal_value; p.picked = a->picked;
+  p.disc_policy = a->disc_policy; p.disc_value = a->disc_value;
+  p.h0 = a->h0; p.pi0 = a->pi0; p.value0 = a->value0; p.err_count = a->err_count;
+  const int R = pick_tile(a->n, a->flags);
+  hipError_t e;
+  if (m) {
+    MzhMultiParams mp{};
+    mp.net_index = m->net_index;
+    mp.M = m->n_networks;
+    mp.tiles = eng->mtiles;
+    mp.ntiles = eng->mntiles;
+    mp.status = m->status;
+    mp.stride = eng->set_stride;
+    mp.scal = eng->set_scal;
+    e = mzh_launch_saliency(R, eng->setnet, eng->settnet, p, &mp, (hipStream_t)stream);
+  } else {
+    e = mzh_launch_saliency(R, eng->net, eng->tnet, p, nullptr, (hipStream_t)stream);
+  }
+  return e == hipSuccess ? MZH_OK : hip_fail(e, "saliency launch");
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "mzh_device.h"
 #include "mzh_pack.h"
 
@@ -213,6 +215,75 @@ struct MzhMultiParams {
 static inline int mzh_multi_max_tiles(int B, int R, int M) { return (B + R - 1) / R + (M < B ? M : B) - 1; }
 hipError_t mzh_launch_search_multi(const MzhSearchPlan& pl, const MzhNet& net, const MzhSearchParams& p,
                                    const MzhMultiParams& mp, hipStream_t stream);
+// mzh_multi_tiles_kernel (mzh_search.hip) on mp.net_index [n]: the prologue of every multi-network launch
+hipError_t mzh_launch_multi_tiles(const MzhMultiParams& mp, int n, int R, hipStream_t stream);
+
+// Where a cooperative workgroup's rows [root0, root0 + nvalid), nvalid <= R, come from: MzhGridTile (workgroup
+// b owns the R rows from b * R: the single-network kernels) or a tile table entry (the multi-network kernels)
+struct MzhGridTile {
+  template <int R>
+  __device__ __forceinline__ int root0() const { return blockIdx.x * R; }
+  template <int R>
+  __device__ __forceinline__ int nvalid(int B, int root0) const { return min(R, B - root0); }
+};
+struct MzhTableTile {
+  MzhTile t;
+  template <int R>
+  __device__ __forceinline__ int root0() const { return t.root0; }
+  template <int R>
+  __device__ __forceinline__ int nvalid(int, int) const { return t.n; }
+};
+
+// the set's network `net` from the template MzhNet of network 0: every blob of a set has the same layout, at
+// a constant byte stride, so each pointer moves by net * stride (the layers' woff / boff are relative to wbase
+// and stay); the two bin-32 biases MzhNet carries by value come from the set's [M][2] array
+__device__ __forceinline__ void mzh_net_select(MzhNet& n, const MzhMultiParams& mp, int net, bool sup33) {
+  const size_t off = (size_t)net * mp.stride;
+  auto mv = [off](auto*& q) { q = reinterpret_cast<std::remove_reference_t<decltype(q)>>(reinterpret_cast<const char*>(q) + off); };
+  auto layer = [&](MzhLayer& l) {
+    mv(l.w);
+    mv(l.b);
+  };
+  layer(n.rep0); layer(n.rep2); layer(n.dyn0); layer(n.dyn2); layer(n.rwd0); layer(n.rwd2);
+  layer(n.pol0); layer(n.pol2); layer(n.val0); layer(n.val2);
+  mv(n.wbase);
+  mv(n.dyn0_onehot);
+  if (sup33) {  // null without a 33-bin head
+    mv(n.rwd32);
+    mv(n.val32);
+    n.rwd32b = mp.scal[2 * net];
+    n.val32b = mp.scal[2 * net + 1];
+  }
+}
+
+// mzh_saliency (mzh_saliency_kernel / mzh_saliency_multi_kernel, mzh_saliency.hip): rows as in MzhProbeParams
+struct MzhSalNetT {  // the transposed blob (MzhPackedT) of one network; a set's at `stride` bytes
+  const float4* base;
+  int off[MZH_T_LAYERS];  // float4 offsets of the layers' fragments
+  int kb_val2;            // k-blocks of the value head's outputs: 3 (33 bins) or 1
+  int nt_rep0;            // 16-column tiles of the observation
+  size_t stride;
+};
+struct MzhSalParams {
+  int B, n;
+  int in_dim, kin;
+  int n_disks;
+  const int32_t* env_index;    // [n] nullable
+  const float* obs;            // [B][in_dim]
+  const int32_t* logit_index;  // [B] nullable
+  float* sal_policy;           // [B][in_dim]
+  float* sal_value;            // [B][in_dim]
+  int32_t* picked;             // [B] nullable
+  float* disc_policy;          // [B][n_disks] nullable
+  float* disc_value;           // [B][n_disks] nullable
+  float* h0;                   // [B][64] nullable
+  float* pi0;                  // [B][6] nullable
+  float* value0;               // [B] nullable
+  int32_t* err_count;          // nullable
+};
+size_t mzh_saliency_smem_bytes(int R);
+hipError_t mzh_launch_saliency(int R, const MzhNet& net, const MzhSalNetT& nt, const MzhSalParams& p,
+                               const MzhMultiParams* mp, hipStream_t stream);
 
 // mzh_probe_actions (mzh_probe_kernel / mzh_probe_multi_kernel, mzh_search.hip): row j of the call is env
 // env_index[j] (or j) of a batch of B; every array but env_index (and a set's net_index) is indexed by env

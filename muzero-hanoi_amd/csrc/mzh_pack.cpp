@@ -226,6 +226,48 @@ MzhPacked mzh_pack_network(const MzhCanon& c) {
   return P;
 }
 
+// ---- transposed layout (MzhPackedT, mzh_pack.h): the saliency backward's B operands ----
+MzhPackedT mzh_pack_transposed(const MzhCanon& c) {
+  static constexpr int kLayers[MZH_T_LAYERS] = {MZH_REP0, MZH_REP2, MZH_POL0, MZH_POL2, MZH_VAL0, MZH_VAL2};
+  MzhPackedT T;
+  for (int t = 0; t < MZH_T_LAYERS; ++t) {
+    const int l = kLayers[t], O = c.out[l], I = c.in[l];
+    const float* W = c.w[l];
+    T.layer[t] = l;
+    T.nt[t] = (I + 15) / 16;
+    T.kb[t] = (O + 15) / 16;
+    T.off[t] = append_zeros(T.blob, (size_t)T.nt[t] * T.kb[t] * 64 * 4);
+    float* dst = T.blob.data() + T.off[t];
+    for (int nt = 0; nt < T.nt[t]; ++nt)
+      for (int kb = 0; kb < T.kb[t]; ++kb)
+        for (int lane = 0; lane < 64; ++lane)
+          for (int j = 0; j < 4; ++j) {
+            const int i = 16 * nt + (lane & 15);
+            const int o = 16 * kb + 4 * j + (lane >> 4);
+            dst[(((size_t)nt * T.kb[t] + kb) * 64 + lane) * 4 + j] = (o < O && i < I) ? W[(size_t)o * I + i] : 0.0f;
+          }
+  }
+  return T;
+}
+
+MzhPackedTSet mzh_pack_transposed_set(const float* flat, int M, int in_dim, int support) {
+  MzhPackedTSet S;
+  const size_t n = mzh_canon_view(nullptr, in_dim, support).total;
+  for (int m = 0; m < M; ++m) {
+    MzhPackedT T = mzh_pack_transposed(mzh_canon_view(flat + (size_t)m * n, in_dim, support));
+    if (m == 0) {
+      S.stride = (T.blob.size() + 63) & ~(size_t)63;
+      S.blob.assign((size_t)M * S.stride, 0.0f);
+    }
+    for (size_t i = 0; i < T.blob.size(); ++i) S.blob[(size_t)m * S.stride + i] = T.blob[i];
+    if (m == 0) {
+      T.blob.clear();
+      S.layout = T;
+    }
+  }
+  return S;
+}
+
 MzhPackedSet mzh_pack_network_set(const float* flat, int M, int in_dim, int support) {
   MzhPackedSet S;
   S.M = M;

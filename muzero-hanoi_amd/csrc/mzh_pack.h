@@ -62,6 +62,29 @@ struct MzhPackedSet {
 // flat: [M][n] canonical vectors, n = mzh_canon_view(nullptr, in_dim, support).total
 MzhPackedSet mzh_pack_network_set(const float* flat, int M, int in_dim, int support);
 
+// The transposed layout of the saliency kernel's backward (mzh_saliency.hip): dX = dY . W takes W with
+// k = out as the MFMA B operand, so layer [O][I] is stored as the cooperative layout of its transpose --
+// tile nt (16 input columns) x k-block kb (16 outputs) x lane -> one float4:
+//     T4[(nt*KB + kb)*64 + lane][j] = W[16kb + 4j + (lane>>4)][16nt + (lane&15)]
+// with NT = ceil(I / 16), KB = ceil(O / 16), zero beyond O and I.  Only the six layers between the
+// observation and the two heads, all 33 bins of a 33-bin value head as tiles (KB = 3).  A blob of its own:
+// mzh_pack_network's bytes and offsets are not touched.
+enum { MZH_T_REP0, MZH_T_REP2, MZH_T_POL0, MZH_T_POL2, MZH_T_VAL0, MZH_T_VAL2, MZH_T_LAYERS };
+struct MzhPackedT {
+  std::vector<float> blob;
+  size_t off[MZH_T_LAYERS];  // float offsets, each a multiple of 4
+  int nt[MZH_T_LAYERS], kb[MZH_T_LAYERS];
+  int layer[MZH_T_LAYERS];   // MzhLayerId of each entry
+};
+MzhPackedT mzh_pack_transposed(const MzhCanon& c);
+// M such blobs at `stride` floats (one blob rounded up to 256 bytes); layout.blob is empty
+struct MzhPackedTSet {
+  std::vector<float> blob;
+  size_t stride = 0;
+  MzhPackedT layout;
+};
+MzhPackedTSet mzh_pack_transposed_set(const float* flat, int M, int in_dim, int support);
+
 // the latency layout's LDS image `l2`: offsets in float4 units
 #define MZH_ONE_D2 0                        // dynamic_net.2 [64 k4][64 lanes]
 #define MZH_ONE_A2 (64 * 64)                // rwd_net.2 bins 0-31 (lanes 0-31) | value_net.2 bins 0-31 (lanes 32-63)

@@ -1,0 +1,358 @@
+// mzh_saliency.hip -- input saliency of the policy and value heads in one fused launch (gfx950).
+//
+// mzh_saliency (the reference's monosemanticity_analysis/gradient_analysis.py compute_saliency): per row
+// d(policy logit k)/d(obs) and d(value)/d(obs) through represent + prediction.  One 256-thread workgroup owns
+// R rows, like mzh_probe_kernel: row r of the tile is env sm.env[r] of the batch (-1: beyond the tile, or a
+// skipped row -- it runs on a zero observation and stores nothing).
+//
+// Forward: mzh_mlp_initial, unchanged, so h0 / pi0 / value0 and the logits the backward starts from are
+// bit-identical to mzh_initial_inference on the row.  It leaves in LDS: the policy / value hidden tiles
+// (hidP / hidV, after ReLU), the raw latent (hraw), the normalised latent (x) and the logits (lpol / lval);
+// the representation's hidden tile is gone (pol0 overwrote it) and is recomputed by the same chain.
+//
+// Backward: every product is dX = dY . W on v_mfma_f32_16x16x4_f32 with the transposed blob's fragments
+// (MzhPackedT, mzh_pack.h) as the B operand and dY, in k-block order in LDS, as the A operand.  The two
+// heads go through the trunk as 2R rows of one GEMM (policy rows [0, R), value rows [R, 2R)).
+//   seeds   lrwd  <- one-hot(k)                      seedV <- dv/dlogits (33 bins) or 1
+//   head 2  hidP  <- (lrwd . pol2) * [hidP > 0]      hidV  <- (seedV . val2) * [hidV > 0]     (in place)
+//   head 0  G     <- hidP . pol0 | hidV . val0       (G = hidR as [2R][68]: d/d normalised latent)
+//   norm    G     <- normalize_h_state's backward, min and max differentiable
+//   rep0    hidP  <- relu(obs . rep0^T + b)          (the forward's chain again: the same bits, the same mask)
+//   rep 2   hidV | hidP <- (G . rep2) * [hidP > 0]   (policy rows to hidV, value rows in place)
+//   rep 0   DX    <- hidV . rep0 | hidP . rep0       (DX = hidR as [2R][68], natural column order)
+// There is no bit contract on the backward's summation order; a row's outputs depend on that row and its
+// network alone (rows never mix in an MFMA), so they are the same bits in any position and at either R.
+#include "mzh_device.h"
+#include "mzh_internal.h"
+
+#define MZH_LDSEED 52  // value-head seed row: 48 columns (33 bins zero-padded to three k-blocks) + 4
+
+template <int R>
+struct SalSmem : MlpSmem<R> {
+  float seedV[R * MZH_LDSEED];
+  int env[R];
+  int pick[R];
+};
+
+// acc[m] += A[row tile m][0 : 16 KB] . W (one 16-column tile: KB k-blocks of 64 float4); A in k-block order
+template <int MT>
+__device__ __forceinline__ void sal_mma(floatx4* acc, const float* A, int lda, const float4* W, int KB, int lane) {
+  const int r = lane & 15, g = lane >> 4;
+  float4 t = W[lane];
+  for (int kb = 0; kb < KB; ++kb) {
+    const floatx4 b{t.x, t.y, t.z, t.w};
+    if (kb + 1 < KB) t = W[(kb + 1) * 64 + lane];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+      const floatx4 a = *reinterpret_cast<const floatx4*>(A + (m * 16 + r) * lda + kb * 16 + g * 4);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], b[j], acc[m], 0, 0, 0);
+    }
+  }
+}
+
+template <int N>
+__device__ __forceinline__ void sal_zero(floatx4* acc) {
+#pragma unroll
+  for (int m = 0; m < N; ++m) acc[m] = floatx4{0.f, 0.f, 0.f, 0.f};
+}
+
+// d(value)/d(value logits) of a 33-bin head (networks.py:152-189 as autograd differentiates it) into the row's
+// seed, k-block order: p = softmax(l), E = sum p_i s_i (s = -16..16), v = sign(E) (z^2 - 1) with
+// z = (sqrt(1 + 4 eps (eps + 1 + |E|)) - 1) / (2 eps) = 2 (eps + 1 + |E|) / (sqrt(..) + 1) (no cancellation),
+// dv/dE = 2 z / sqrt(..) (0 at E = 0, as torch's sign and abs give), dv/dl_i = dv/dE p_i (s_i - E)
+__device__ __forceinline__ void sal_value_seed33(const float* l, float* seed) {
+  float m = l[0];
+  for (int i = 1; i < 33; ++i) m = l[i] > m ? l[i] : m;
+  float s = 0.0f, se = 0.0f;
+  for (int i = 0; i < 33; ++i) {
+    const float e = mzh_expf(l[i] - m);
+    s = s + e;
+    se = se + e * (float)(i - 16);
+  }
+  const float E = se / s;
+  const float eps = 0.001f;
+  const float a = __builtin_fabsf(E);
+  const float u = eps + 1.0f + a;
+  const float sq = __builtin_sqrtf(1.0f + 4.0f * eps * u);
+  const float z = 2.0f * u / (sq + 1.0f);
+  const float dv = E != 0.0f ? 2.0f * z / sq : 0.0f;
+  for (int i = 0; i < 48; ++i) {
+    float v = 0.0f;
+    if (i < 33) v = dv * (mzh_expf(l[i] - m) / s) * ((float)(i - 16) - E);
+    seed[mzh_kpos(i)] = v;
+  }
+}
+
+template <int R, class TILE = MzhGridTile>
+__device__ __forceinline__ void mzh_saliency_body(const MzhNet& net, const MzhSalNetT& nt, const float4* T,
+                                                  const MzhSalParams& p, const TILE tile = TILE{}) {
+  constexpr int MT = R / 16;
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  SalSmem<R>& sm = *reinterpret_cast<SalSmem<R>*>(smem_raw);
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r16 = lane & 15, g = lane >> 4;
+  const int row0 = tile.template root0<R>();
+  const int nvalid = tile.template nvalid<R>(p.n, row0);
+  if (tid < R) {
+    int e = -1, li = -1;
+    if (tid < nvalid) {
+      e = p.env_index ? p.env_index[row0 + tid] : row0 + tid;
+      if ((unsigned)e >= (unsigned)p.B) {
+        if (p.err_count) atomicAdd(p.err_count, 1);
+        e = -1;
+      } else if (p.logit_index) {
+        li = p.logit_index[e];
+        if (li < -1 || li >= MZH_A) {
+          if (p.err_count) atomicAdd(p.err_count, 1);
+          e = -1;
+          li = -1;
+        }
+      }
+    }
+    sm.env[tid] = e;
+    sm.pick[tid] = li;
+  }
+  __syncthreads();
+  auto load_obs = [&]() {
+    for (int i = tid; i < R * p.kin; i += MZH_THREADS) {
+      const int r = i / p.kin, k = i - r * p.kin;
+      const int e = sm.env[r];
+      sm.x[r * MZH_LD64 + mzh_kpos(k)] = (e >= 0 && k < p.in_dim) ? p.obs[(size_t)e * p.in_dim + k] : 0.0f;
+    }
+  };
+  load_obs();
+  __syncthreads();
+  MlpSmem<R>& ms = sm;  // the MLP block the inference kernels run on
+  mzh_mlp_initial<R>(ms, net, wave, lane);
+
+  // ---- the forward's outputs, and the heads' seeds (lrwd is unused by the initial MLP) ----
+  if (p.h0)
+    for (int i = tid; i < R * MZH_H; i += MZH_THREADS) {
+      const int r = i >> 6, k = i & 63;
+      const int e = sm.env[r];
+      if (e >= 0) p.h0[(size_t)e * MZH_H + mzh_kpos(k)] = sm.x[r * MZH_LD64 + k];
+    }
+  if (tid < R * 8) {
+    const int r = tid >> 3, c = tid & 7;
+    const int e = sm.env[r];
+    if (e >= 0) {
+      if (p.pi0 && c < MZH_A) p.pi0[(size_t)e * MZH_A + c] = sm.pi[r * 8 + c];
+      if (p.value0 && c == 6) p.value0[e] = sm.value[r];
+    }
+  }
+  float* seedP = sm.lrwd;  // [R][MZH_LDSUP]: 16 columns used
+  if (tid < R) {
+    const int row = tid;
+    int k = sm.pick[row];
+    if (k < 0) {  // the lowest index of the largest logit
+      const float* l = sm.lpol + row * MZH_LDPOL;
+      k = 0;
+      float best = l[0];
+      for (int i = 1; i < MZH_A; ++i)
+        if (l[i] > best) {
+          best = l[i];
+          k = i;
+        }
+      sm.pick[row] = k;
+    }
+    for (int i = 0; i < 16; ++i) seedP[row * MZH_LDSUP + mzh_kpos(i)] = i == k ? 1.0f : 0.0f;
+  } else if (tid >= 64 && tid < 64 + R) {  // another wave: the value seeds
+    const int row = tid - 64;
+    float* seed = sm.seedV + row * MZH_LDSEED;
+    if (net.support == 33) {
+      sal_value_seed33(sm.lval + row * MZH_LDSUP, seed);
+    } else {
+      for (int i = 0; i < 16; ++i) seed[i] = i == 0 ? 1.0f : 0.0f;
+    }
+  }
+  __syncthreads();
+
+  // ---- head layer 2 transposed, the ReLU masks of hidP / hidV (in place: a lane reads the element it writes) ----
+  for (int q = 0; q < 4; ++q) {
+    const int t = wave * 4 + q;
+    const int pos = t * 16 + 4 * (r16 & 3) + (r16 >> 2);
+    floatx4 acc[MT];
+    sal_zero<MT>(acc);
+    sal_mma<MT>(acc, seedP, MZH_LDSUP, T + nt.off[MZH_T_POL2] + t * 64, 1, lane);
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        float* h = sm.hidP + (m * 16 + g * 4 + i) * MZH_LD256 + pos;
+        *h = *h > 0.0f ? acc[m][i] : 0.0f;
+      }
+    sal_zero<MT>(acc);
+    sal_mma<MT>(acc, sm.seedV, MZH_LDSEED, T + nt.off[MZH_T_VAL2] + t * nt.kb_val2 * 64, nt.kb_val2, lane);
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        float* h = sm.hidV + (m * 16 + g * 4 + i) * MZH_LD256 + pos;
+        *h = *h > 0.0f ? acc[m][i] : 0.0f;
+      }
+  }
+  __syncthreads();
+
+  // ---- head layer 0 transposed: wave w makes latent tile w of both heads ----
+  float* G = sm.hidR;  // [2R][MZH_LD64]
+  {
+    const int pos = wave * 16 + 4 * (r16 & 3) + (r16 >> 2);
+#pragma unroll
+    for (int hd = 0; hd < 2; ++hd) {
+      floatx4 acc[MT];
+      sal_zero<MT>(acc);
+      sal_mma<MT>(acc, hd ? sm.hidV : sm.hidP, MZH_LD256, T + nt.off[hd ? MZH_T_VAL0 : MZH_T_POL0] + wave * 16 * 64, 16, lane);
+#pragma unroll
+      for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) G[(hd * R + m * 16 + g * 4 + i) * MZH_LD64 + pos] = acc[m][i];
+    }
+  }
+  __syncthreads();
+
+  // ---- normalize_h_state's backward (networks.py:191-196; D = max - min + 1e-8), one thread per gradient row:
+  // every element g_i / D, the arg-max element - sum g_i (h_i - min) / D^2, the arg-min element
+  // - sum g_i / D + sum g_i (h_i - min) / D^2; arg-min / arg-max: the lowest unit index holding the forward's
+  // min / max.  The observations come back into sm.x beside it (nothing reads the normalised latent any more).
+  load_obs();
+  if (tid < 2 * R) {
+    float* gr = G + tid * MZH_LD64;
+    const float* h = sm.hraw + (tid < R ? tid : tid - R) * MZH_LD64;
+    float mn = h[0], mx = h[0];
+    for (int i = 1; i < MZH_H; ++i) {
+      mn = h[i] < mn ? h[i] : mn;
+      mx = h[i] > mx ? h[i] : mx;
+    }
+    int amin = -1, amax = -1;
+    float s1 = 0.0f, s2 = 0.0f;
+    for (int k = 0; k < MZH_H; ++k) {  // unit k at position mzh_kpos(k)
+      const int pk = mzh_kpos(k);
+      if (amin < 0 && h[pk] == mn) amin = pk;
+      if (amax < 0 && h[pk] == mx) amax = pk;
+      s1 = s1 + gr[pk];
+      s2 = s2 + gr[pk] * (h[pk] - mn);
+    }
+    if (amin < 0) amin = 0;  // a NaN latent: no element compares equal
+    if (amax < 0) amax = 0;
+    const float D = (mx - mn) + 9.999999939225290290778502821922302246094e-09f;
+    for (int i = 0; i < MZH_H; ++i) gr[i] = gr[i] / D;
+    const float c2 = s2 / (D * D);
+    gr[amax] = gr[amax] - c2;
+    gr[amin] = gr[amin] + (c2 - s1 / D);
+  }
+  __syncthreads();
+
+  // ---- rep0's hidden tile again (the forward's jobs: the same chain, the same bits) ----
+  {
+    MzhJob jobs[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) jobs[q] = mzh_job(sm.x, MZH_LD64, net.rep0, wave * 4 + q, sm.hidP, MZH_LD256, 1);
+    mzh_run_jobs<MT, 4>(jobs, net.rep0.kb, nullptr, nullptr, lane);
+  }
+  __syncthreads();
+
+  // ---- rep2 transposed on the 2R rows, rep0's ReLU mask: policy rows -> hidV, value rows -> hidP in place ----
+  for (int q = 0; q < 4; ++q) {
+    const int t = wave * 4 + q;
+    const int pos = t * 16 + 4 * (r16 & 3) + (r16 >> 2);
+    floatx4 acc[2 * MT];
+    sal_zero<2 * MT>(acc);
+    sal_mma<2 * MT>(acc, G, MZH_LD64, T + nt.off[MZH_T_REP2] + t * 4 * 64, 4, lane);
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int idx = (m * 16 + g * 4 + i) * MZH_LD256 + pos;
+        const bool on = sm.hidP[idx] > 0.0f;
+        sm.hidV[idx] = on ? acc[m][i] : 0.0f;
+        sm.hidP[idx] = on ? acc[MT + m][i] : 0.0f;
+      }
+  }
+  __syncthreads();
+
+  // ---- rep0 transposed: (observation tile, head) jobs over the waves; DX in natural column order ----
+  float* DX = sm.hidR;  // [2R][MZH_LD64]; G is dead
+  for (int j = wave; j < 2 * nt.nt_rep0; j += MZH_WAVES) {
+    const int hd = j & 1, t = j >> 1;
+    floatx4 acc[MT];
+    sal_zero<MT>(acc);
+    sal_mma<MT>(acc, hd ? sm.hidP : sm.hidV, MZH_LD256, T + nt.off[MZH_T_REP0] + t * 16 * 64, 16, lane);
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) DX[(hd * R + m * 16 + g * 4 + i) * MZH_LD64 + t * 16 + r16] = acc[m][i];
+  }
+  __syncthreads();
+
+  // ---- outputs ----
+  for (int i = tid; i < R * p.in_dim; i += MZH_THREADS) {
+    const int r = i / p.in_dim, k = i - r * p.in_dim;
+    const int e = sm.env[r];
+    if (e >= 0) {
+      p.sal_policy[(size_t)e * p.in_dim + k] = DX[r * MZH_LD64 + k];
+      p.sal_value[(size_t)e * p.in_dim + k] = DX[(R + r) * MZH_LD64 + k];
+    }
+  }
+  if (p.disc_policy || p.disc_value)
+    for (int i = tid; i < R * p.n_disks; i += MZH_THREADS) {
+      const int r = i / p.n_disks, d = i - r * p.n_disks;
+      const int e = sm.env[r];
+      if (e >= 0) {
+        const float* sp = DX + r * MZH_LD64 + 3 * d;
+        const float* sv = DX + (R + r) * MZH_LD64 + 3 * d;
+        if (p.disc_policy)
+          p.disc_policy[(size_t)e * p.n_disks + d] = (__builtin_fabsf(sp[0]) + __builtin_fabsf(sp[1])) + __builtin_fabsf(sp[2]);
+        if (p.disc_value)
+          p.disc_value[(size_t)e * p.n_disks + d] = (__builtin_fabsf(sv[0]) + __builtin_fabsf(sv[1])) + __builtin_fabsf(sv[2]);
+      }
+    }
+  if (p.picked && tid < R && sm.env[tid] >= 0) p.picked[sm.env[tid]] = sm.pick[tid];
+}
+
+template <int R>
+__global__ __launch_bounds__(MZH_THREADS, 1) void mzh_saliency_kernel(MzhNet net, MzhSalNetT nt, MzhSalParams p) {
+  mzh_saliency_body<R>(net, nt, nt.base, p);
+}
+
+// Rows of several networks (a set, mzh_load_weight_set): workgroup t takes tile t of the table
+// mzh_multi_tiles_kernel made of this call's net_index; one at or above the tile count returns before its
+// first barrier (a refused net_index leaves the count 0: nothing is written)
+template <int R>
+__global__ __launch_bounds__(MZH_THREADS, 1) void mzh_saliency_multi_kernel(MzhNet net, MzhSalNetT nt, MzhSalParams p,
+                                                                            MzhMultiParams mp) {
+  if ((int)blockIdx.x >= *mp.ntiles) return;
+  const MzhTableTile t{mp.tiles[blockIdx.x]};
+  mzh_net_select(net, mp, t.t.net, net.support == 33);
+  const float4* T = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(nt.base) + (size_t)t.t.net * nt.stride);
+  mzh_saliency_body<R>(net, nt, T, p, t);
+}
+
+template <int R>
+static size_t saliency_smem_bytes() { return (sizeof(SalSmem<R>) + 15) & ~(size_t)15; }
+size_t mzh_saliency_smem_bytes(int R) { return R == 32 ? saliency_smem_bytes<32>() : saliency_smem_bytes<16>(); }
+
+template <int R>
+static hipError_t launch_saliency_t(const MzhNet& net, const MzhSalNetT& nt, const MzhSalParams& p, const MzhMultiParams* mp,
+                                    hipStream_t stream) {
+  const size_t smem = saliency_smem_bytes<R>();
+  const void* fn = mp ? reinterpret_cast<const void*>(&mzh_saliency_multi_kernel<R>)
+                      : reinterpret_cast<const void*>(&mzh_saliency_kernel<R>);
+  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+  if (e != hipSuccess) return e;
+  if (!mp) {
+    hipLaunchKernelGGL((mzh_saliency_kernel<R>), dim3((p.n + R - 1) / R), dim3(MZH_THREADS), smem, stream, net, nt, p);
+    return hipGetLastError();
+  }
+  e = mzh_launch_multi_tiles(*mp, p.n, R, stream);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((mzh_saliency_multi_kernel<R>), dim3(mzh_multi_max_tiles(p.n, R, mp->M)), dim3(MZH_THREADS), smem,
+                     stream, net, nt, p, *mp);
+  return hipGetLastError();
+}
+
+hipError_t mzh_launch_saliency(int R, const MzhNet& net, const MzhSalNetT& nt, const MzhSalParams& p,
+                               const MzhMultiParams* mp, hipStream_t stream) {
+  return R == 32 ? launch_saliency_t<32>(net, nt, p, mp, stream) : launch_saliency_t<16>(net, nt, p, mp, stream);
+}

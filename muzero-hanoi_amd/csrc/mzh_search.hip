@@ -37,12 +37,6 @@ constexpr int search_dc() { return R == 32 ? 16 : 32; }  // LDS-cached path dept
 // on 8-fragment weight chunks (mzh_mlp_recurrent_c8), DC = 16 cached path depths, no one-hot in LDS
 // TILE: where the workgroup's roots [root0, root0 + nvalid), nvalid <= R, come from -- MzhGridTile (workgroup b
 // owns the R roots from b * R: the single-network kernels) or a tile table entry (mzh_search_multi_kernel)
-struct MzhGridTile {
-  template <int R>
-  __device__ __forceinline__ int root0() const { return blockIdx.x * R; }
-  template <int R>
-  __device__ __forceinline__ int nvalid(int B, int root0) const { return min(R, B - root0); }
-};
 
 template <int R, int DC, bool C8, bool REPLAY, bool OHL, bool SUP33, bool MMIN, class TILE = MzhGridTile>
 __device__ __forceinline__ void mzh_search_body(const MzhNet& net, const MzhSearchParams& p, const TILE tile = TILE{}) {
@@ -321,36 +315,6 @@ __global__ __launch_bounds__(MZH_MULTI_MAX_NETS) void mzh_multi_tiles_kernel(Mzh
     }
   }
 }
-
-// the set's network `net` from the template MzhNet of network 0: every blob of a set has the same layout, at
-// a constant byte stride, so each pointer moves by net * stride (the layers' woff / boff are relative to wbase
-// and stay); the two bin-32 biases MzhNet carries by value come from the set's [M][2] array
-__device__ __forceinline__ void mzh_net_select(MzhNet& n, const MzhMultiParams& mp, int net, bool sup33) {
-  const size_t off = (size_t)net * mp.stride;
-  auto mv = [off](auto*& q) { q = reinterpret_cast<std::remove_reference_t<decltype(q)>>(reinterpret_cast<const char*>(q) + off); };
-  auto layer = [&](MzhLayer& l) {
-    mv(l.w);
-    mv(l.b);
-  };
-  layer(n.rep0); layer(n.rep2); layer(n.dyn0); layer(n.dyn2); layer(n.rwd0); layer(n.rwd2);
-  layer(n.pol0); layer(n.pol2); layer(n.val0); layer(n.val2);
-  mv(n.wbase);
-  mv(n.dyn0_onehot);
-  if (sup33) {  // null without a 33-bin head
-    mv(n.rwd32);
-    mv(n.val32);
-    n.rwd32b = mp.scal[2 * net];
-    n.val32b = mp.scal[2 * net + 1];
-  }
-}
-
-struct MzhTableTile {
-  MzhTile t;
-  template <int R>
-  __device__ __forceinline__ int root0() const { return t.root0; }
-  template <int R>
-  __device__ __forceinline__ int nvalid(int, int) const { return t.n; }
-};
 
 // MMIN = true always: it only adds the subnormal max - min check, and is bit-identical with fresh bounds.
 // A workgroup at or above the tile count (the grid is the upper bound ceil(B / R) + min(M, B) - 1) returns
@@ -650,6 +614,12 @@ static hipError_t launch_probe_t(const MzhNet& net, const MzhProbeParams& p, con
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL((mzh_probe_multi_kernel<R>), dim3(mzh_multi_max_tiles(p.n, R, mp->M)), dim3(MZH_THREADS), smem, stream,
                      net, p, *mp);
+  return hipGetLastError();
+}
+
+// the tile table of n rows at R rows per tile (the prologue of every multi-network launch)
+hipError_t mzh_launch_multi_tiles(const MzhMultiParams& mp, int n, int R, hipStream_t stream) {
+  hipLaunchKernelGGL(mzh_multi_tiles_kernel, dim3(1), dim3(MZH_MULTI_MAX_NETS), 0, stream, mp, n, R);
   return hipGetLastError();
 }
 

@@ -177,6 +177,63 @@ class Engine:
                                            self._stream()), "mzh_probe_actions")
         return out
 
+    def saliency(self, obs, *, env_index=None, net_index=None, logit_index=None, out=None, full=False, tile=None,
+                 err=None):
+        """mzh_saliency: for every row d(policy logit k)/d(obs) and d(value)/d(obs) through represent + prediction
+        in one launch (gradient_analysis.py:354-391).  obs [B, 3N] float32 is the full batch's; row j of the call is
+        env env_index[j] ([n] int32, distinct; None: every env, n = B); every output is indexed by env and rows
+        outside the call are left as they are.  logit_index [B] int32 names the logit differentiated (-1, or no
+        logit_index: the row's largest); net_index [n] int32 runs row j under network net_index[j] of the loaded
+        weight set (non-decreasing).  out: a dict of output tensors to write into (policy / value [B, 3N] float32,
+        and with them any of picked [B] int32, disc_policy / disc_value [B, N], h0 [B, 64], pi0 [B, 6],
+        value0 [B]); missing policy / value are allocated, the others only with full=True.  tile = None | 16 | 32.
+        err: [1] int32, += 1 per skipped row.  Returns the dict; with net_index, "_status" is the device's [2]
+        int32 verdict as in search_multi."""
+        dev = self.device
+        B = int(obs.shape[0])
+        N = self.n_disks
+        checks = [("obs", obs, torch.float32, (B, 3 * N))]
+        n = B
+        if env_index is not None:
+            n = int(env_index.shape[0])
+            checks.append(("env_index", env_index, torch.int32, (n,)))
+        if logit_index is not None:
+            checks.append(("logit_index", logit_index, torch.int32, (B,)))
+        if net_index is not None:
+            checks.append(("net_index", net_index, torch.int32, (n,)))
+        out = dict(out) if out is not None else {}
+        shapes = dict(policy=(B, 3 * N), value=(B, 3 * N), disc_policy=(B, N), disc_value=(B, N), h0=(B, LATENT),
+                      pi0=(B, ACTIONS), value0=(B,))
+        for k, shp in shapes.items():
+            if k not in out and (full or k in ("policy", "value")):
+                out[k] = torch.empty(shp, dtype=torch.float32, device=dev)
+            if k in out:
+                checks.append((k, out[k], torch.float32, shp))
+        if full and "picked" not in out:
+            out["picked"] = torch.empty(B, dtype=torch.int32, device=dev)
+        if "picked" in out:
+            checks.append(("picked", out["picked"], torch.int32, (B,)))
+        for name, t, dt, shp in checks:
+            if t.dtype != dt or tuple(t.shape) != shp or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"saliency: {name} must be a contiguous {dt} {shp} tensor on {dev}")
+        a = _lib.SaliencyArgs()
+        a.B, a.n, a.flags = B, n, search_flags(None, tile)
+        for k, t in (("env_index", env_index), ("obs", obs), ("logit_index", logit_index), ("err_count", err)):
+            setattr(a, k, ptr(t))
+        a.sal_policy, a.sal_value = ptr(out["policy"]), ptr(out["value"])
+        for k in ("picked", "disc_policy", "disc_value", "h0", "pi0", "value0"):
+            setattr(a, k, ptr(out.get(k)))
+        m = None
+        if net_index is not None:
+            if getattr(self, "set_size", 0) < 1:
+                raise RuntimeError("saliency: no weight set loaded (load_weight_set)")
+            out["_status"] = torch.zeros(2, dtype=torch.int32, device=dev)
+            m = _lib.MultiArgs()
+            m.n_networks, m.net_index, m.status = self.set_size, ptr(net_index), ptr(out["_status"])
+        check(_lib.lib().mzh_saliency(self._h, ctypes.byref(a), None if m is None else ctypes.byref(m),
+                                      self._stream()), "mzh_saliency")
+        return out
+
     # ---------------------------------------------------------------- expansion memo (wave kernel)
     def set_memo_depth(self, depth):
         """mzh_set_memo_depth: -1 automatic (default), 0 off, d > 0 forced; takes effect with the next search"""

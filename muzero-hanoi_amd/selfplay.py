@@ -778,3 +778,34 @@ def evaluate_legality(networks, n_disks, *, episodes=100, n_sims=25, max_steps=2
                      action=action[:, sl].copy())
         res.append(d)
     return res
+
+
+def evaluate_saliency(networks, n_disks, *, states=None, start_idx=None):
+    """gradient_analysis.py's atlas (compute_saliency for one state and one network per process) as one
+    mzh_saliency call on a network set: every given state (states = state tuples, or start_idx = state indices;
+    default all 3^n_disks states in state_index order) under every network of the list, network m's S rows
+    consecutive.  networks: one network, a sequence of networks or a networks.NetworkSet.
+    Returns numpy arrays: policy / value [M][S][3N] float32 (d(policy logit at its argmax)/d(obs), d(value)/d(obs)),
+    picked [M][S] int32 (that argmax), disc_policy / disc_value [M][S][N] (aggregate_saliency_per_disk in fp32)
+    and states [S] int64."""
+    nset = _network_set("evaluate_saliency", networks)
+    M = len(nset)
+    if nset.in_dim != 3 * n_disks:
+        raise ValueError(f"evaluate_saliency: the networks do not read {3 * n_disks} inputs (n_disks={n_disks})")
+    if states is None and start_idx is None:
+        start_idx = np.arange(3 ** n_disks)
+    idx = _start_indices("evaluate_saliency", n_disks, states, start_idx, None, 0, 2)
+    S = int(idx.shape[0])
+    eng = engine_for_set(nset, 0, M * S)
+    st = np.array([index_state(int(i), n_disks) for i in idx], np.int64)  # [S][N]
+    obs1 = np.zeros((S, n_disks, 3), np.float32)
+    obs1[np.arange(S)[:, None], np.arange(n_disks)[None, :], st] = 1.0
+    obs = torch.from_numpy(np.tile(obs1.reshape(S, 3 * n_disks), (M, 1))).to(eng.device)
+    net_index = torch.from_numpy(np.repeat(np.arange(M, dtype=np.int32), S)).to(eng.device)
+    out = eng.saliency(obs, net_index=net_index, full=True)
+    if int(out["_status"][0].item()) != 0:
+        raise RuntimeError("evaluate_saliency: the device refused net_index")
+    res = {k: out[k].cpu().numpy().reshape((M, S) + tuple(out[k].shape[1:]))
+           for k in ("policy", "value", "picked", "disc_policy", "disc_value")}
+    res["states"] = idx
+    return res
