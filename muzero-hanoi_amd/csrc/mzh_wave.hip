@@ -17,7 +17,10 @@
 // the two waves per SIMD, software-pipelined MLP chains, LDS parking of the tree statistics,
 // laundered weight pointers, cached child values in the tree block, a register reciprocal, a touch of the leaf's parent latent
 // at the end of a root's walk.  The
-// child-block prefetch in selection is shipped for 16-root waves only (neutral at 32 roots per wave).
+// child-block prefetch in selection is shipped for 16-root waves only (neutral at 32 roots per wave before the
+// expansion memo, +1.7% / +4.1% with it).  With the memo: layer 1 of block i + 1 beside
+// layer 2 of block i in the one-tile chains (+0.6% / +3.5%: a dependent 16x16x4 chain already issues every 33
+// ticks), a hit's record loaded ahead of the packed form's chains (+0.4%), or only its line touched (neutral).
 //
 // Reference: MCTS/mcts.py:34-126 (run_mcts), MCTS/node.py:30-136 (expand/backup/best_child),
 // MCTS/utils_mcts.py:1-16 (MinMaxStats), networks.py:71-196 (initial/recurrent inference).
@@ -510,7 +513,27 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
 
   // ---------------- root: initial_inference (mcts.py:49-50) + root.expand (mcts.py:57-69) ----------------
   floatx4 rpi[NT];
-  if (!REPLAY) {
+  // A wave whose every valid root is a state's observation takes the root priors from the table's depth-0 records
+  // and runs no root chain (at launch every wave is in its root chains at once, so they are MFMA-bound with no tree
+  // phase beside them).  Such a root's depth-1 expansions gather the root latent from the table as well (prow_r
+  // below: depth - 1 = 0 <= memo_D), so nothing reads its htree slot 0, which is left unwritten.
+  const bool rtab = memo && __ballot(rvalid && sigma < 0) == 0;  // wave-uniform
+  if (!REPLAY && rtab) {
+#pragma unroll
+    for (int n = 0; n < NT; ++n) {
+      const int sg = __shfl(sigma, 16 * n + col);
+      rpi[n] = floatx4{0.f, 0.f, 0.f, 0.f};
+      if (cvalid[n] && g < 2) {  // lane group 0: priors 0-3, group 1: priors 4, 5 (mzw_policy's registers)
+        const float* rec = p.memo_rec + (size_t)sg * p.memo_K * 8 + 4 * g;
+        if (g == 0) {
+          rpi[n] = *reinterpret_cast<const floatx4*>(rec);
+        } else {
+          rpi[n][0] = rec[0];
+          rpi[n][1] = rec[1];
+        }
+      }
+    }
+  } else if (!REPLAY) {
     floatx4 hreg[NT][4];  // the root's normalised latent (B-operand order)
     floatx4 x[NT][4];
 #pragma unroll
@@ -618,7 +641,8 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
       pid = 0;
       // 16-root waves (NT = 1) prefetch the children's blocks one level ahead (16,384 roots: 2.66 ->
       // 2.57 ms); at 32 roots per wave the partner wave's MFMA stream already covers the latency
-      // (65,536 roots: neutral), so NT = 2 leaves the load queue to the block loads
+      // (65,536 roots: neutral; measured again with the expansion memo's shorter M phase: 65,536 roots +1.7%,
+      // 262,144 seven-disc roots +4.1%), so NT = 2 leaves the load queue to the block loads
       constexpr bool kPF = NT == 1;
       int pf0 = 0, pf1 = 0, pf2 = 0;
       // (a root lane touching its leaf's parent latent when its walk ends, ahead of the M phase's gather,
