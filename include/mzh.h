@@ -106,6 +106,48 @@ int mzh_load_weights(mzh_engine* eng, const float* flat_host, size_t n_floats);
  * one.  Synchronous.  MZH_ERR_ARG: M outside [1, 256], n_floats != mzh_weights_size, a NULL pointer. */
 int mzh_load_weight_set(mzh_engine* eng, const float* flat_host, size_t n_floats, int M);
 
+/* The same loads from the LIVE parameter tensors on the device, without a host round trip: the packers only
+ * copy, so a blob is a fixed permutation of the canonical weights with zero fill (mzh_pack_map), and one
+ * gather kernel (mzh_repack_kernel) writes the blobs from the 20 tensors where an optimiser step left them.
+ *   param : HOST array of 20 DEVICE pointers (mzh_load_weight_set_device: [M][20]), contiguous fp32 tensors in
+ *           torch layout, in state_dict order -- the order of mzh_weights_size and of mzh_train_args.param.
+ * After the call the engine is in the state mzh_load_weights / mzh_load_weight_set leaves it in for the same
+ * values: the same blob bytes, and every later call gives bit-identical results.  Either kind of load may follow
+ * the other.
+ * Stream-ordered: the gather reads the parameters as they are when `stream` reaches it, and calls that use the
+ * weights must be ordered after it (the same stream, or an event).  The engine's buffers are allocated by the
+ * first load of either kind and kept (a set's are reallocated only when M changes); the map is uploaded once
+ * per engine; the table of parameter pointers is uploaded when the pointers differ from the previous call's.
+ * Otherwise the call makes no allocation, frees nothing and does not wait for the device, with two exceptions:
+ *   - single network with a 33-bin head: the search kernels take bias bin 32 of the reward and the value head
+ *     by value, so the call reads those two floats back (one 8-byte copy) and waits for `stream`.  Support 1
+ *     and sets (whose scalars stay in device memory) do not wait;
+ *   - mzh_load_weights_device drops an existing expansion memo exactly as mzh_load_weights does, which waits
+ *     for the device.
+ * MZH_ERR_ARG, before any device work: a NULL engine, param or entry; M outside [1, 256]. */
+int mzh_load_weights_device(mzh_engine* eng, const float* const* param, mzh_stream stream);
+int mzh_load_weight_set_device(mzh_engine* eng, const float* const* param, int M, mzh_stream stream);
+
+/* The packers as index maps (host-only: no device, no engine).  which = 0 the main blob (the three kernel
+ * layouts), 1 the transposed blob of mzh_saliency.  map[j] is the canonical index (the order of
+ * mzh_weights_size) whose value blob float j holds, or -1 where the blob holds +0.0f; map may be NULL (sizes
+ * only).  *n_floats: the blob's floats.  scalar_src (nullable) [2]: the canonical indices of rwd_net.2.bias[32]
+ * and value_net.2.bias[32], the two values the kernels take by value, or -1 at support 1.
+ * MZH_ERR_ARG: n_disks / support that mzh_weights_size refuses, which outside {0, 1}. */
+int mzh_pack_map(int n_disks, int support, int which, int32_t* map /* nullable */, size_t* n_floats /* nullable */,
+                 int64_t* scalar_src /* nullable */);
+
+/* Debug, like mzh_memo_debug_table: a copy of a weight buffer as the kernels read it.  which = 0 / 1 the
+ * engine's network (main / transposed blob), 2 / 3 the loaded set (2: the whole allocation, the M blobs at
+ * their stride and the [M][2] scalar tail).  dst: device buffer of *n_floats floats, or NULL (size only).
+ * Waits for the device.  MZH_ERR_ARG: NULL engine or n_floats, which outside [0, 3]; MZH_ERR_STATE: nothing of
+ * that kind is loaded. */
+int mzh_weights_debug_blob(mzh_engine* eng, int which, float* dst /* nullable */, size_t* n_floats);
+/* Debug: counters[3] = weight buffer allocations, weight buffer frees and device-wide waits
+ * (hipDeviceSynchronize) made by this engine's weight loads and memo drops since mzh_create: a refresh that
+ * reuses the buffers moves none of them. */
+int mzh_weights_debug_counters(mzh_engine* eng, uint64_t* counters);
+
 /* ---------------------------------------------------------------------------------------------
  * Environment: TowersOfHanoi (env/hanoi.py), batched over B independent envs.
  * state[B][n] uint8 peg of disc d (disc 0 = smallest), the reference's tuple c_state layout.

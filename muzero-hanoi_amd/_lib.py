@@ -153,6 +153,12 @@ SIGNATURES = {
     "mzh_weights_size": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
     "mzh_load_weights": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t]),
     "mzh_load_weight_set": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_int]),
+    "mzh_load_weights_device": (ctypes.c_int, [_vp, _vp, _vp]),
+    "mzh_load_weight_set_device": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp]),
+    "mzh_pack_map": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.POINTER(ctypes.c_size_t),
+                                    ctypes.POINTER(ctypes.c_int64)]),
+    "mzh_weights_debug_blob": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.POINTER(ctypes.c_size_t)]),
+    "mzh_weights_debug_counters": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64)]),
     "mzh_env_step": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [_vp] * 10 + [_vp]),
     "mzh_env_run_plan": (ctypes.c_int, [ctypes.POINTER(PlanArgs), _vp]),
     "mzh_env_step_observe": (ctypes.c_int, [ctypes.POINTER(ObserveArgs), _vp]),

@@ -89,6 +89,22 @@ struct mzh_engine {
   MzhSalNetT tnet{};
   void* settbuf = nullptr;
   MzhSalNetT settnet{};
+  // floats of wbuf / tbuf / setbuf (tail included) / settbuf (mzh_weights_debug_blob)
+  size_t wn = 0, tn = 0, setn = 0, settn = 0;
+  // the device repack (mzh_load_weights_device / mzh_load_weight_set_device): made by the first such call, kept
+  MzhPackMaps* maps = nullptr;     // host: layouts and scalar sources of this engine's shape
+  int32_t* rmap = nullptr;         // device: encoded main map [rstride], then the transposed one [rtstride]
+  size_t rstride = 0, rtstride = 0;  // a blob rounded up to 256 bytes (the set strides), floats; -1 beyond the blob
+  int32_t rscal[2] = {-1, -1};     // encoded sources of the two by-value scalars
+  const float** ptab = nullptr;    // device [20]: the single network's parameter pointers
+  std::vector<const float*> ptab_host;      // what ptab holds (uploaded again only when it differs)
+  const float** set_ptab = nullptr;  // device [set_ptab_m][20]
+  int set_ptab_m = 0;
+  std::vector<const float*> set_ptab_host;
+  float* scal2 = nullptr;          // device [2]: the single network's by-value scalars as the gather wrote them
+  float* scal2_host = nullptr;     // pinned [2]: their read-back
+  // weight buffer allocations, frees and device-wide waits of every load call (mzh_weights_debug_counters)
+  uint64_t n_alloc = 0, n_free = 0, n_wait = 0;
 };
 
 extern "C" int mzh_abi_version(void) { return MZH_ABI_VERSION; }
@@ -202,6 +218,12 @@ extern "C" int mzh_destroy(mzh_engine* eng) {
   if (eng->memo_cnt) (void)hipFree(eng->memo_cnt);
   if (eng->tbuf) (void)hipFree(eng->tbuf);
   if (eng->settbuf) (void)hipFree(eng->settbuf);
+  if (eng->rmap) (void)hipFree(eng->rmap);
+  if (eng->ptab) (void)hipFree(eng->ptab);
+  if (eng->set_ptab) (void)hipFree(eng->set_ptab);
+  if (eng->scal2) (void)hipFree(eng->scal2);
+  if (eng->scal2_host) (void)hipHostFree(eng->scal2_host);
+  delete eng->maps;
   delete eng;
   return MZH_OK;
 }
@@ -209,6 +231,7 @@ extern "C" int mzh_destroy(mzh_engine* eng) {
 // drop the expansion memo (after the device has finished with it)
 static hipError_t memo_drop(mzh_engine* eng) {
   if (!eng->memo_h && !eng->memo_rec) return hipSuccess;
+  ++eng->n_wait;
   hipError_t e = hipDeviceSynchronize();
   if (e != hipSuccess) return e;
   if (eng->memo_h) (void)hipFree(eng->memo_h);
@@ -259,29 +282,10 @@ static MzhSalNetT make_tnet(const MzhPackedT& t, const void* base, size_t stride
   return n;
 }
 
-extern "C" int mzh_load_weights(mzh_engine* eng, const float* flat, size_t n_floats) {
-  if (!eng || !flat) return fail(MZH_ERR_ARG, "engine or weights NULL");
+// the three kernels' views (MzhNet, MzhWNet, MzhOneNet) and the saliency view of the single network whose
+// blobs lie in wbuf / tbuf with the offsets of pk / pt
+static int bind_single(mzh_engine* eng, const MzhPacked& pk, const MzhPackedT& pt) {
   const int in = eng->in_dim, sup = eng->support;
-  const size_t want = mzh_canon_view(nullptr, in, sup).total;
-  if (n_floats != want) return fail(MZH_ERR_ARG, "weights: expected %zu floats, got %zu", want, n_floats);
-  const MzhPacked pk = mzh_pack_network(mzh_canon_view(flat, in, sup));
-  const MzhPackedT pt = mzh_pack_transposed(mzh_canon_view(flat, in, sup));
-
-  DeviceGuard g(eng->device);
-  if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
-  if (eng->wbuf) {
-    HIP_OK(hipDeviceSynchronize());
-    HIP_OK(hipFree(eng->wbuf));
-    eng->wbuf = nullptr;
-    eng->loaded = false;
-    if (eng->tbuf) HIP_OK(hipFree(eng->tbuf));
-    eng->tbuf = nullptr;
-  }
-  HIP_OK(memo_drop(eng));  // the table is a function of the weights
-  HIP_OK(hipMalloc(&eng->wbuf, pk.blob.size() * sizeof(float)));
-  HIP_OK(hipMemcpy(eng->wbuf, pk.blob.data(), pk.blob.size() * sizeof(float), hipMemcpyHostToDevice));
-  HIP_OK(hipMalloc(&eng->tbuf, pt.blob.size() * sizeof(float)));
-  HIP_OK(hipMemcpy(eng->tbuf, pt.blob.data(), pt.blob.size() * sizeof(float), hipMemcpyHostToDevice));
   eng->tnet = make_tnet(pt, eng->tbuf, 0);
   const float* base = static_cast<const float*>(eng->wbuf);
   const int nst = make_net(pk, base, sup, in, &eng->net);
@@ -319,6 +323,81 @@ extern "C" int mzh_load_weights(mzh_engine* eng, const float* flat, size_t n_flo
   return MZH_OK;
 }
 
+extern "C" int mzh_load_weights(mzh_engine* eng, const float* flat, size_t n_floats) {
+  if (!eng || !flat) return fail(MZH_ERR_ARG, "engine or weights NULL");
+  const int in = eng->in_dim, sup = eng->support;
+  const size_t want = mzh_canon_view(nullptr, in, sup).total;
+  if (n_floats != want) return fail(MZH_ERR_ARG, "weights: expected %zu floats, got %zu", want, n_floats);
+  const MzhPacked pk = mzh_pack_network(mzh_canon_view(flat, in, sup));
+  const MzhPackedT pt = mzh_pack_transposed(mzh_canon_view(flat, in, sup));
+
+  DeviceGuard g(eng->device);
+  if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+  if (eng->wbuf) {
+    ++eng->n_wait;
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipFree(eng->wbuf));
+    ++eng->n_free;
+    eng->wbuf = nullptr;
+    eng->loaded = false;
+    if (eng->tbuf) {
+      HIP_OK(hipFree(eng->tbuf));
+      ++eng->n_free;
+    }
+    eng->tbuf = nullptr;
+  }
+  HIP_OK(memo_drop(eng));  // the table is a function of the weights
+  HIP_OK(hipMalloc(&eng->wbuf, pk.blob.size() * sizeof(float)));
+  HIP_OK(hipMemcpy(eng->wbuf, pk.blob.data(), pk.blob.size() * sizeof(float), hipMemcpyHostToDevice));
+  HIP_OK(hipMalloc(&eng->tbuf, pt.blob.size() * sizeof(float)));
+  HIP_OK(hipMemcpy(eng->tbuf, pt.blob.data(), pt.blob.size() * sizeof(float), hipMemcpyHostToDevice));
+  eng->n_alloc += 2;
+  eng->wn = pk.blob.size();
+  eng->tn = pt.blob.size();
+  return bind_single(eng, pk, pt);
+}
+
+// the views of the loaded set (network 0's MzhNet as the template the multi kernels offset, the saliency view)
+static int bind_set(mzh_engine* eng, const MzhPacked& layout, const MzhPackedT& tlayout, size_t stride, size_t tstride,
+                    int M) {
+  eng->settnet = make_tnet(tlayout, eng->settbuf, tstride * sizeof(float));
+  const float* base = static_cast<const float*>(eng->setbuf);
+  const int nst = make_net(layout, base, eng->support, eng->in_dim, &eng->setnet);
+  if (nst) return nst;
+  eng->set_stride = stride * sizeof(float);
+  eng->set_scal = base + (size_t)M * stride;
+  eng->set_m = M;
+  return MZH_OK;
+}
+
+// free the loaded set's buffers once the device has finished with them
+static hipError_t set_release(mzh_engine* eng) {
+  if (!eng->setbuf) return hipSuccess;
+  ++eng->n_wait;
+  hipError_t e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipFree(eng->setbuf);
+  if (e != hipSuccess) return e;
+  ++eng->n_free;
+  eng->setbuf = nullptr;
+  eng->set_m = 0;
+  if (eng->settbuf) {
+    e = hipFree(eng->settbuf);
+    if (e != hipSuccess) return e;
+    ++eng->n_free;
+  }
+  eng->settbuf = nullptr;
+  return hipSuccess;
+}
+
+// the tile table workspace of the multi-network kernels, allocated with the first set
+static hipError_t set_workspace(mzh_engine* eng) {
+  hipError_t e = hipSuccess;
+  if (!eng->mtiles)
+    e = hipMalloc(&eng->mtiles, sizeof(MzhTile) * (size_t)mzh_multi_max_tiles(eng->max_roots, 16, MZH_MULTI_MAX_NETS));
+  if (e == hipSuccess && !eng->mntiles) e = hipMalloc(&eng->mntiles, sizeof(int32_t));
+  return e;
+}
+
 extern "C" int mzh_load_weight_set(mzh_engine* eng, const float* flat, size_t n_floats, int M) {
   if (!eng || !flat) return fail(MZH_ERR_ARG, "engine or weights NULL");
   if (M < 1 || M > MZH_MULTI_MAX_NETS)
@@ -331,28 +410,214 @@ extern "C" int mzh_load_weight_set(mzh_engine* eng, const float* flat, size_t n_
 
   DeviceGuard g(eng->device);
   if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
-  if (eng->setbuf) {
-    HIP_OK(hipDeviceSynchronize());
-    HIP_OK(hipFree(eng->setbuf));
-    eng->setbuf = nullptr;
-    eng->set_m = 0;
-    if (eng->settbuf) HIP_OK(hipFree(eng->settbuf));
-    eng->settbuf = nullptr;
-  }
-  if (!eng->mtiles)
-    HIP_OK(hipMalloc(&eng->mtiles, sizeof(MzhTile) * (size_t)mzh_multi_max_tiles(eng->max_roots, 16, MZH_MULTI_MAX_NETS)));
-  if (!eng->mntiles) HIP_OK(hipMalloc(&eng->mntiles, sizeof(int32_t)));
+  HIP_OK(set_release(eng));
+  HIP_OK(set_workspace(eng));
   HIP_OK(hipMalloc(&eng->setbuf, ps.blob.size() * sizeof(float)));
   HIP_OK(hipMemcpy(eng->setbuf, ps.blob.data(), ps.blob.size() * sizeof(float), hipMemcpyHostToDevice));
   HIP_OK(hipMalloc(&eng->settbuf, pts.blob.size() * sizeof(float)));
   HIP_OK(hipMemcpy(eng->settbuf, pts.blob.data(), pts.blob.size() * sizeof(float), hipMemcpyHostToDevice));
-  eng->settnet = make_tnet(pts.layout, eng->settbuf, pts.stride * sizeof(float));
-  const float* base = static_cast<const float*>(eng->setbuf);
-  const int nst = make_net(ps.layout, base, sup, in, &eng->setnet);
-  if (nst) return nst;
-  eng->set_stride = ps.stride * sizeof(float);
-  eng->set_scal = base + ps.scal;
-  eng->set_m = M;
+  eng->n_alloc += 2;
+  eng->setn = ps.blob.size();
+  eng->settn = pts.blob.size();
+  return bind_set(eng, ps.layout, pts.layout, ps.stride, pts.stride, M);
+}
+
+// ---- device repack: the same blobs gathered on the device from the live parameter tensors ----
+// the pack maps of the engine's shape, on the host and (encoded, padded with -1 to the set strides) on the
+// device, and the small buffers of the single-network call: made once per engine
+static int repack_ensure(mzh_engine* eng) {
+  if (eng->rmap) return MZH_OK;
+  const int in = eng->in_dim, sup = eng->support;
+  if (!eng->maps) {
+    MzhPackMaps* m = new MzhPackMaps();
+    if (!mzh_pack_maps(in, sup, m)) {
+      delete m;
+      return fail(MZH_ERR_ARG, "pack maps: the shape has 2^24 or more weights");
+    }
+    eng->maps = m;
+  }
+  const MzhPackMaps& mp = *eng->maps;
+  if (mp.main.size() % 4 || mp.trans.size() % 4)
+    return fail(MZH_ERR_STATE, "device repack: a blob of %zu / %zu floats is no whole number of float4", mp.main.size(),
+                mp.trans.size());
+  const MzhCanon sizes = mzh_canon_view(nullptr, in, sup);
+  const size_t rs = (mp.main.size() + 63) & ~(size_t)63, rts = (mp.trans.size() + 63) & ~(size_t)63;
+  std::vector<int32_t> enc(rs + rts, -1);
+  for (size_t j = 0; j < mp.main.size(); ++j) enc[j] = mzh_pack_map_encode(sizes, mp.main[j]);
+  for (size_t j = 0; j < mp.trans.size(); ++j) enc[rs + j] = mzh_pack_map_encode(sizes, mp.trans[j]);
+  // every entry names an element inside its tensor: the kernel's reads stay in bounds
+  for (size_t j = 0; j < enc.size(); ++j) {
+    if (enc[j] < 0) continue;
+    const int t = enc[j] >> 24, l = t >> 1;
+    const size_t numel = (t & 1) ? (size_t)sizes.out[l] : (size_t)sizes.out[l] * sizes.in[l];
+    if (t >= 20 || (size_t)(enc[j] & 0xffffff) >= numel) return fail(MZH_ERR_STATE, "device repack: map entry %zu out of range", j);
+  }
+  for (int i = 0; i < 2; ++i) eng->rscal[i] = mzh_pack_map_encode(sizes, mp.scalar_src[i]);
+  if (!eng->ptab) HIP_OK(hipMalloc(&eng->ptab, 20 * sizeof(float*)));
+  if (!eng->scal2) HIP_OK(hipMalloc(&eng->scal2, 2 * sizeof(float)));
+  if (!eng->scal2_host) HIP_OK(hipHostMalloc(&eng->scal2_host, 2 * sizeof(float)));
+  int32_t* d = nullptr;
+  HIP_OK(hipMalloc(&d, enc.size() * sizeof(int32_t)));
+  hipError_t e = hipMemcpy(d, enc.data(), enc.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(d);
+    return hip_fail(e, "hipMemcpy (pack maps)");
+  }
+  eng->rmap = d;
+  eng->rstride = rs;
+  eng->rtstride = rts;
+  return MZH_OK;
+}
+
+// the device's pointer table follows the caller's: uploaded when it differs from what the table holds (the
+// first call, or parameters that moved); the host copy is consumed before hipMemcpyAsync returns (pageable)
+static int ptab_sync(const float* const* param, size_t n, const float** dev, std::vector<const float*>* host,
+                     hipStream_t stream) {
+  if (host->size() == n && memcmp(host->data(), param, n * sizeof(float*)) == 0) return MZH_OK;
+  host->clear();  // unknown contents until the copy is issued
+  HIP_OK(hipMemcpyAsync(dev, param, n * sizeof(float*), hipMemcpyHostToDevice, stream));
+  host->assign(param, param + n);
+  return MZH_OK;
+}
+
+static MzhRepackParams repack_params(const mzh_engine* eng, bool set) {
+  MzhRepackParams p{};
+  p.map_m = reinterpret_cast<const int4*>(eng->rmap);
+  p.map_t = reinterpret_cast<const int4*>(eng->rmap + eng->rstride);
+  // a set member is written up to its stride (zeros between the blobs), the single network up to its blob's end
+  p.n4m = (int)((set ? eng->rstride : eng->maps->main.size()) / 4);
+  p.n4t = (int)((set ? eng->rtstride : eng->maps->trans.size()) / 4);
+  p.stride_m = eng->rstride;
+  p.stride_t = eng->rtstride;
+  p.scal_src[0] = eng->rscal[0];
+  p.scal_src[1] = eng->rscal[1];
+  return p;
+}
+
+extern "C" int mzh_load_weights_device(mzh_engine* eng, const float* const* param, mzh_stream stream) {
+  if (!eng || !param) return fail(MZH_ERR_ARG, "load_weights_device: engine or param NULL");
+  for (int i = 0; i < 20; ++i)
+    if (!param[i]) return fail(MZH_ERR_ARG, "load_weights_device: param[%d] is NULL", i);
+  DeviceGuard g(eng->device);
+  if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+  const int st = repack_ensure(eng);
+  if (st) return st;
+  const MzhPackMaps& mp = *eng->maps;
+  if (!eng->wbuf) {
+    HIP_OK(hipMalloc(&eng->wbuf, mp.main.size() * sizeof(float)));
+    ++eng->n_alloc;
+    eng->wn = mp.main.size();
+  }
+  if (!eng->tbuf) {
+    HIP_OK(hipMalloc(&eng->tbuf, mp.trans.size() * sizeof(float)));
+    ++eng->n_alloc;
+    eng->tn = mp.trans.size();
+  }
+  HIP_OK(memo_drop(eng));  // the table is a function of the weights
+  const hipStream_t s = (hipStream_t)stream;
+  const int ps = ptab_sync(param, 20, eng->ptab, &eng->ptab_host, s);
+  if (ps) return ps;
+  MzhRepackParams p = repack_params(eng, false);
+  p.ptab = eng->ptab;
+  p.dst_m = static_cast<float*>(eng->wbuf);
+  p.dst_t = static_cast<float*>(eng->tbuf);
+  p.scal = eng->scal2;
+  hipError_t e = mzh_launch_repack(p, 1, s);
+  if (e != hipSuccess) return hip_fail(e, "repack launch");
+  MzhPacked pk = mp.layout;
+  if (eng->support == 33) {  // the kernels take bin 32's two biases by value: one 8-byte copy, one wait
+    HIP_OK(hipMemcpyAsync(eng->scal2_host, eng->scal2, 2 * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    pk.W[2].b32 = eng->scal2_host[0];
+    pk.W[4].b32 = eng->scal2_host[1];
+  }
+  return bind_single(eng, pk, mp.tlayout);
+}
+
+extern "C" int mzh_load_weight_set_device(mzh_engine* eng, const float* const* param, int M, mzh_stream stream) {
+  if (!eng || !param) return fail(MZH_ERR_ARG, "load_weight_set_device: engine or param NULL");
+  if (M < 1 || M > MZH_MULTI_MAX_NETS)
+    return fail(MZH_ERR_ARG, "weight set: M must be in [1,%d], got %d", MZH_MULTI_MAX_NETS, M);
+  for (int i = 0; i < 20 * M; ++i)
+    if (!param[i]) return fail(MZH_ERR_ARG, "load_weight_set_device: param[%d][%d] is NULL", i / 20, i % 20);
+  DeviceGuard g(eng->device);
+  if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+  const int st = repack_ensure(eng);
+  if (st) return st;
+  const MzhPackMaps& mp = *eng->maps;
+  const size_t setn = (size_t)M * eng->rstride + 2 * (size_t)M, settn = (size_t)M * eng->rtstride;
+  if (eng->setbuf && eng->set_m != M) HIP_OK(set_release(eng));
+  HIP_OK(set_workspace(eng));
+  if (!eng->setbuf) {
+    HIP_OK(hipMalloc(&eng->setbuf, setn * sizeof(float)));
+    ++eng->n_alloc;
+    eng->setn = setn;
+  }
+  if (!eng->settbuf) {
+    HIP_OK(hipMalloc(&eng->settbuf, settn * sizeof(float)));
+    ++eng->n_alloc;
+    eng->settn = settn;
+  }
+  if (eng->set_ptab_m != M) {
+    if (eng->set_ptab) HIP_OK(hipFree(eng->set_ptab));
+    eng->set_ptab = nullptr;
+    eng->set_ptab_m = 0;
+    eng->set_ptab_host.clear();
+    HIP_OK(hipMalloc(&eng->set_ptab, (size_t)M * 20 * sizeof(float*)));
+    eng->set_ptab_m = M;
+  }
+  const hipStream_t s = (hipStream_t)stream;
+  const int ps = ptab_sync(param, (size_t)M * 20, eng->set_ptab, &eng->set_ptab_host, s);
+  if (ps) return ps;
+  MzhRepackParams p = repack_params(eng, true);
+  p.ptab = eng->set_ptab;
+  p.dst_m = static_cast<float*>(eng->setbuf);
+  p.dst_t = static_cast<float*>(eng->settbuf);
+  p.scal = p.dst_m + (size_t)M * eng->rstride;  // MzhPackedSet::scal
+  hipError_t e = mzh_launch_repack(p, M, s);
+  if (e != hipSuccess) return hip_fail(e, "repack launch");
+  return bind_set(eng, mp.layout, mp.tlayout, eng->rstride, eng->rtstride, M);
+}
+
+extern "C" int mzh_pack_map(int n_disks, int support, int which, int32_t* map, size_t* n_floats, int64_t* scalar_src) {
+  size_t total = 0;
+  const int st = mzh_weights_size(n_disks, support, &total);
+  if (st) return st;
+  if (which < 0 || which > 1) return fail(MZH_ERR_ARG, "pack_map: which must be 0 (main) or 1 (transposed), got %d", which);
+  MzhPackMaps mp;
+  if (!mzh_pack_maps(3 * n_disks, support, &mp)) return fail(MZH_ERR_ARG, "pack_map: the shape has 2^24 or more weights");
+  const std::vector<int32_t>& m = which ? mp.trans : mp.main;
+  if (n_floats) *n_floats = m.size();
+  if (map) memcpy(map, m.data(), m.size() * sizeof(int32_t));
+  if (scalar_src) {
+    scalar_src[0] = mp.scalar_src[0];
+    scalar_src[1] = mp.scalar_src[1];
+  }
+  return MZH_OK;
+}
+
+extern "C" int mzh_weights_debug_blob(mzh_engine* eng, int which, float* dst, size_t* n_floats) {
+  if (!eng || !n_floats) return fail(MZH_ERR_ARG, "weights_debug_blob: NULL argument");
+  if (which < 0 || which > 3) return fail(MZH_ERR_ARG, "weights_debug_blob: which must be in [0,3], got %d", which);
+  if (which < 2 ? !eng->loaded : eng->set_m == 0)
+    return fail(MZH_ERR_STATE, which < 2 ? "weights not loaded" : "no weight set loaded");
+  const void* src[4] = {eng->wbuf, eng->tbuf, eng->setbuf, eng->settbuf};
+  const size_t n[4] = {eng->wn, eng->tn, eng->setn, eng->settn};
+  *n_floats = n[which];
+  if (!dst) return MZH_OK;
+  DeviceGuard g(eng->device);
+  if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+  HIP_OK(hipDeviceSynchronize());
+  HIP_OK(hipMemcpy(dst, src[which], n[which] * sizeof(float), hipMemcpyDeviceToDevice));
+  HIP_OK(hipDeviceSynchronize());
+  return MZH_OK;
+}
+
+extern "C" int mzh_weights_debug_counters(mzh_engine* eng, uint64_t* counters) {
+  if (!eng || !counters) return fail(MZH_ERR_ARG, "weights_debug_counters: NULL argument");
+  counters[0] = eng->n_alloc;
+  counters[1] = eng->n_free;
+  counters[2] = eng->n_wait;
   return MZH_OK;
 }
 

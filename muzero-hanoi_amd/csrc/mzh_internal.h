@@ -71,6 +71,22 @@ hipError_t mzh_launch_memo_scatter(const float* h, const float* pi, const float*
                                    long long per_state, long long K, long long first_id, float* memo_h, float* memo_rec,
                                    hipStream_t stream);
 
+// The device repack (mzh_repack.hip): gather the main and the transposed blob of M networks from their
+// parameter tensors through the pack maps (MzhPackMaps, mzh_pack.h)
+#define MZH_REPACK_THREADS 256
+struct MzhRepackParams {
+  const int4* map_m;         // [n4m] encoded map of the main blob (mzh_pack_map_encode), -1 padded to a float4
+  const int4* map_t;         // [n4t] the transposed blob's
+  int n4m, n4t;              // float4s written per network
+  const float* const* ptab;  // device [M][20] parameter tensors in state_dict order
+  float* dst_m;              // network m's main blob at dst_m + m * stride_m (floats, multiples of 4)
+  float* dst_t;
+  size_t stride_m, stride_t;
+  float* scal;               // [M][2] {rwd_net.2.bias[32], value_net.2.bias[32]}, 0 without a 33-bin head
+  int32_t scal_src[2];       // their encoded sources (-1: none)
+};
+hipError_t mzh_launch_repack(const MzhRepackParams& p, int M, hipStream_t stream);
+
 // visits ** e as generate_play_policy computes it (np.power(int64 visits, e), mcts.py:168-174), for
 // x = n visits and e = max(1, min(5, 1/T)): an integer exponent is an exact product (n^5 < 2^53);
 // a non-integer one is taken from pow_table[n], the caller's np.power(arange(S + 1), e) (NumPy's

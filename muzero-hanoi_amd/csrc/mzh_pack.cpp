@@ -289,3 +289,42 @@ MzhPackedSet mzh_pack_network_set(const float* flat, int M, int in_dim, int supp
   }
   return S;
 }
+
+// ---- the packers as index maps (MzhPackMaps, mzh_pack.h) ----
+// blob float of the pack of i -> (float)(i + 1): i + 1 where it holds element i, +0.0f where it is padding
+static int32_t map_entry(float v) { return (int32_t)v - 1; }
+
+bool mzh_pack_maps(int in_dim, int support, MzhPackMaps* out) {
+  const size_t n = mzh_canon_view(nullptr, in_dim, support).total;
+  if (n >= ((size_t)1 << 24)) return false;
+  std::vector<float> id(n);
+  for (size_t i = 0; i < n; ++i) id[i] = (float)(i + 1);
+  const MzhCanon c = mzh_canon_view(id.data(), in_dim, support);
+  MzhPacked P = mzh_pack_network(c);
+  MzhPackedT T = mzh_pack_transposed(c);
+  out->main.resize(P.blob.size());
+  for (size_t j = 0; j < P.blob.size(); ++j) out->main[j] = map_entry(P.blob[j]);
+  out->trans.resize(T.blob.size());
+  for (size_t j = 0; j < T.blob.size(); ++j) out->trans[j] = map_entry(T.blob[j]);
+  out->scalar_src[0] = map_entry(P.W[2].b32);
+  out->scalar_src[1] = map_entry(P.W[4].b32);
+  for (int i = 0; i < 5; ++i) P.W[i].b32 = 0.0f;  // an index, not a weight: the caller fills the value in
+  P.blob.clear();
+  T.blob.clear();
+  out->layout = P;
+  out->tlayout = T;
+  return true;
+}
+
+int32_t mzh_pack_map_encode(const MzhCanon& sizes, int64_t canon_index) {
+  if (canon_index < 0) return -1;
+  size_t first = 0;
+  for (int l = 0; l < 10; ++l) {
+    const size_t nw = (size_t)sizes.out[l] * sizes.in[l], nb = (size_t)sizes.out[l];
+    if ((size_t)canon_index < first + nw) return (int32_t)((2 * l) << 24 | (int32_t)(canon_index - first));
+    first += nw;
+    if ((size_t)canon_index < first + nb) return (int32_t)((2 * l + 1) << 24 | (int32_t)(canon_index - first));
+    first += nb;
+  }
+  return -1;
+}

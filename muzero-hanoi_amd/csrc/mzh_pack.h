@@ -85,6 +85,23 @@ struct MzhPackedTSet {
 };
 MzhPackedTSet mzh_pack_transposed_set(const float* flat, int M, int in_dim, int support);
 
+// The packers as a permutation with zero fill (they only copy): entry j of a map is the canonical index
+// (mzh_canon_view order) whose value blob float j holds, or -1 where the blob holds +0.0f.  Derived by running
+// mzh_pack_network / mzh_pack_transposed on the vector i -> (float)(i + 1), so the layouts keep their one
+// definition above.  The device repack (mzh_repack.hip) gathers through these maps from the live parameters.
+struct MzhPackMaps {
+  std::vector<int32_t> main, trans;  // one entry per blob float of MzhPacked / MzhPackedT
+  MzhPacked layout;                  // the offsets make_net needs; blob empty, W[i].b32 zero
+  MzhPackedT tlayout;                // the offsets make_tnet needs; blob empty
+  int64_t scalar_src[2];             // canonical index of W[2].b32 / W[4].b32 (bias bin 32 of the reward / value
+                                     // head, taken by value by the kernels), -1 without a 33-bin head
+};
+// false (nothing written) for a shape with 2^24 or more weights: i + 1 would no longer be exact in a float
+bool mzh_pack_maps(int in_dim, int support, MzhPackMaps* out);
+// a map entry as the device reads it: (tensor << 24) | offset inside that tensor, tensor = 2 * layer (weight) or
+// 2 * layer + 1 (bias) in state_dict order; -1 stays -1.  The largest tensor has 256 * 96 < 2^24 elements
+int32_t mzh_pack_map_encode(const MzhCanon& sizes, int64_t canon_index);
+
 // the latency layout's LDS image `l2`: offsets in float4 units
 #define MZH_ONE_D2 0                        // dynamic_net.2 [64 k4][64 lanes]
 #define MZH_ONE_A2 (64 * 64)                // rwd_net.2 bins 0-31 (lanes 0-31) | value_net.2 bins 0-31 (lanes 32-63)

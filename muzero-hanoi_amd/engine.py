@@ -20,6 +20,7 @@ WEIGHT_KEYS = [
 
 ACTIONS = 6
 LATENT = 64
+HIDDEN = 256
 
 
 def flat_weights(state_dict):
@@ -31,6 +32,16 @@ def flat_weights(state_dict):
             v = v.detach().to("cpu", torch.float32).numpy()
         parts.append(np.asarray(v, np.float32).reshape(-1))
     return np.ascontiguousarray(np.concatenate(parts))
+
+
+def weight_shapes(n_disks, support):
+    """the shapes of the 20 tensors of WEIGHT_KEYS for a Hanoi MuZeroNet of n_disks discs and a `support`-bin
+    reward / value head (networks.py:39-67; the layer table of csrc/mzh_pack.cpp)"""
+    mlps = ((3 * n_disks, LATENT), (LATENT + ACTIONS, LATENT), (LATENT, support), (LATENT, ACTIONS), (LATENT, support))
+    shapes = []
+    for i, o in mlps:
+        shapes += [(HIDDEN, i), (HIDDEN,), (o, HIDDEN), (o,)]
+    return shapes
 
 
 def require_device():
@@ -95,6 +106,74 @@ class Engine:
         check(_lib.lib().mzh_load_weight_set(self._h, flat.ctypes.data_as(ctypes.c_void_p), n.value, len(flats)),
               "mzh_load_weight_set")
         self.set_size = len(flats)
+
+    def _param_pointers(self, params, what):
+        """the 20 device pointers of one network's parameters for the device repack, validated: `params` is a
+        mapping with the state_dict keys or a sequence in state_dict order (WEIGHT_KEYS).  ValueError on
+        anything the gather could not read as it stands; nothing has been launched then."""
+        if hasattr(params, "keys"):
+            missing = [k for k in WEIGHT_KEYS if k not in params]
+            if missing:
+                raise ValueError(f"{what}: parameters {missing} are missing")
+            params = [params[k] for k in WEIGHT_KEYS]
+        params = list(params)
+        if len(params) != len(WEIGHT_KEYS):
+            raise ValueError(f"{what}: expected {len(WEIGHT_KEYS)} tensors in state_dict order, got {len(params)}")
+        shapes = weight_shapes(self.n_disks, self.support)
+        for k, t, shp in zip(WEIGHT_KEYS, params, shapes):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{what}: {k} is a {type(t).__name__}, not a tensor")
+            if tuple(t.shape) != shp:
+                raise ValueError(f"{what}: {k} has shape {tuple(t.shape)}, this engine's is {shp}")
+            if t.dtype != torch.float32:
+                raise ValueError(f"{what}: {k} is {t.dtype}, not torch.float32")
+            if not t.is_contiguous():
+                raise ValueError(f"{what}: {k} is not contiguous")
+            if t.device != self.device:
+                raise ValueError(f"{what}: {k} is on {t.device}, the engine on {self.device}")
+        return params
+
+    def load_weights_from(self, params):
+        """mzh_load_weights_device: load_weights(flat_weights(...)) without the host round trip -- the blobs are
+        gathered on the device from the 20 parameter tensors as they are when the current stream reaches the
+        call (contiguous fp32 tensors of this engine's shape on its device; a state_dict or a sequence in
+        WEIGHT_KEYS order).  Same blob bytes, bit-identical results afterwards.  No torch.cuda.synchronize; a
+        33-bin engine waits for the current stream once (two scalars the kernels take by value)."""
+        params = self._param_pointers(params, "load_weights_from")
+        arr = (ctypes.c_void_p * len(params))(*[t.data_ptr() for t in params])
+        check(_lib.lib().mzh_load_weights_device(self._h, arr, self._stream()), "mzh_load_weights_device")
+        self._weight_src = params  # the gather reads them at stream time
+        self.weights_loaded = True
+
+    def load_weight_set_from(self, param_sets):
+        """mzh_load_weight_set_device: load_weight_set from the members' live parameter tensors (a sequence of
+        what load_weights_from takes).  Never waits."""
+        param_sets = list(param_sets)
+        if not 1 <= len(param_sets) <= 256:
+            raise ValueError(f"load_weight_set_from: a set has 1 to 256 networks, got {len(param_sets)}")
+        sets = [self._param_pointers(p, f"load_weight_set_from: network {m}") for m, p in enumerate(param_sets)]
+        flat = [t.data_ptr() for ps in sets for t in ps]
+        arr = (ctypes.c_void_p * len(flat))(*flat)
+        check(_lib.lib().mzh_load_weight_set_device(self._h, arr, len(sets), self._stream()),
+              "mzh_load_weight_set_device")
+        self._weight_set_src = sets
+        self.set_size = len(sets)
+
+    def debug_blob(self, which):
+        """mzh_weights_debug_blob: a copy of a weight buffer as the kernels read it ([n] float32 on the device).
+        which = 0 / 1 the engine's main / transposed blob, 2 / 3 the loaded set's (2 with its scalar tail)."""
+        n = ctypes.c_size_t()
+        fn = _lib.lib().mzh_weights_debug_blob
+        check(fn(self._h, int(which), None, ctypes.byref(n)), "mzh_weights_debug_blob")
+        out = self._f32(n.value)
+        check(fn(self._h, int(which), ptr(out), ctypes.byref(n)), "mzh_weights_debug_blob")
+        return out
+
+    def debug_counters(self):
+        """mzh_weights_debug_counters as a dict: allocations / frees of weight buffers and device-wide waits"""
+        c = (ctypes.c_uint64 * 3)()
+        check(_lib.lib().mzh_weights_debug_counters(self._h, c), "mzh_weights_debug_counters")
+        return {"allocs": c[0], "frees": c[1], "device_waits": c[2]}
 
     # ---------------------------------------------------------------- inference
     def _f32(self, *shape):

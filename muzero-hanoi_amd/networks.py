@@ -161,17 +161,53 @@ def _fast_signature(refs):
     return tuple([x for mod, name in refs for p in (mod._parameters[name],) for x in (p.data_ptr(), p._version)])
 
 
-def engine_for(net, max_sims, max_roots, device=None):
+WEIGHTS_MODES = ("auto", "host", "device")
+# what "auto" does with eligible parameters.  One refresh is 26x (a set of 8: 65x) faster on the device, far beyond
+# the host path's spread, but a whole training loop gained 2.2 % (median of six work-matched block pairs), inside
+# the host path's own block-to-block spread (profiles/reload_bench.json): the rule for
+# switching the default asks for both, so "auto" stays on the host path and weights="device" is the opt-in
+AUTO_DEVICE_RELOAD = False
+
+
+def _live_params(net, eng):
+    """the network's 20 parameter tensors in state_dict order (sharing the parameters' storage) and why the
+    device repack cannot read them as they stand (None: it can)"""
+    sd = net.state_dict()
+    params = [sd[k] for k in _engine.WEIGHT_KEYS]
+    for k, t in zip(_engine.WEIGHT_KEYS, params):
+        if t.device != eng.device or t.dtype != torch.float32 or not t.is_contiguous():
+            return params, f"{k} is a {'contiguous' if t.is_contiguous() else 'non-contiguous'} {t.dtype} tensor on {t.device}"
+    return params, None
+
+
+def _use_device_reload(weights, reasons):
+    """whether a refresh takes the device repack; reasons: per network, why it is not eligible (None: it is)"""
+    bad = [r for r in reasons if r is not None]
+    if weights == "device" and bad:
+        raise ValueError(f"weights='device': {bad[0]} (the device repack reads contiguous fp32 parameters on the "
+                         "engine's device)")
+    return weights == "device" or (weights == "auto" and AUTO_DEVICE_RELOAD and not bad)
+
+
+def engine_for(net, max_sims, max_roots, device=None, weights="auto"):
     """The libmzh engine bound to `net` (ours or any module with MuZeroNet's state_dict keys),
     with capacity >= (max_sims, max_roots) and the network's CURRENT weights loaded.
 
     Per call (MCTS.run_mcts makes one per environment step) only the capacity and the parameters' storage /
-    version counters are checked: the shape validation and the parameter list are cached per network."""
+    version counters are checked: the shape validation and the parameter list are cached per network.
+
+    weights: how changed parameters reach the engine.  "host": flat_weights + Engine.load_weights (copies to
+    the host, packs there, uploads).  "device": Engine.load_weights_from, the gather from the live tensors on
+    the current stream; a parameter it cannot read is a ValueError.  "auto": the device path when
+    AUTO_DEVICE_RELOAD is set and every parameter is eligible, else the host path.  All give the same blob bytes."""
+    if weights not in WEIGHTS_MODES:
+        raise ValueError(f"weights must be one of {WEIGHTS_MODES}, got {weights!r}")
     cache = _CACHE.get(net)
     if cache is not None and "refs" in cache:
         eng = cache.get("engine")
         if eng is not None and eng.max_sims >= max_sims and eng.max_roots >= max_roots:
-            if cache.get("sig") == _fast_signature(cache["refs"]):
+            # (a "device" request is not served by weights that came the host way: it checks eligibility below)
+            if cache.get("sig") == _fast_signature(cache["refs"]) and (weights != "device" or cache.get("how") == "device"):
                 return eng
     sd_keys = set(net.state_dict().keys())
     missing = [k for k in _engine.WEIGHT_KEYS if k not in sd_keys]
@@ -195,8 +231,14 @@ def engine_for(net, max_sims, max_roots, device=None):
     if "refs" not in cache:
         cache["refs"] = _param_refs(net)
     sig = _fast_signature(cache["refs"])
-    if cache.get("sig") != sig:
-        eng.load_weights(_engine.flat_weights(net.state_dict()))
+    if cache.get("sig") != sig or (weights == "device" and cache.get("how") != "device"):
+        params, why = (None, "host") if weights == "host" else _live_params(net, eng)
+        if _use_device_reload(weights, [why]):
+            eng.load_weights_from(params)
+            cache["how"] = "device"
+        else:
+            eng.load_weights(_engine.flat_weights(net.state_dict()))
+            cache["how"] = "host"
         cache["sig"] = sig
     return eng
 
@@ -240,11 +282,14 @@ class NetworkSet:
         return self.nets[i]
 
 
-def engine_for_set(nset, max_sims, max_roots, device=None):
+def engine_for_set(nset, max_sims, max_roots, device=None, weights="auto"):
     """engine_for for a NetworkSet: the libmzh engine bound to the set with capacity >= (max_sims, max_roots) and
     every member's CURRENT weights loaded as its weight set; reloaded when any member's parameter storage or
-    version counter changed (the signature scheme of engine_for)."""
-    cache = nset.__dict__.setdefault("_cache", {})
+    version counter changed (the signature scheme of engine_for).  weights: as in engine_for; the device path
+    needs every member's parameters eligible."""
+    if weights not in WEIGHTS_MODES:
+        raise ValueError(f"weights must be one of {WEIGHTS_MODES}, got {weights!r}")
+    cache =nset.__dict__.setdefault("_cache", {})
     eng = cache.get("engine")
     if eng is None or eng.max_sims < max_sims or eng.max_roots < max_roots:
         if eng is not None:
@@ -256,7 +301,13 @@ def engine_for_set(nset, max_sims, max_roots, device=None):
     if "refs" not in cache:
         cache["refs"] = [_param_refs(n) for n in nset.nets]
     sig = tuple(_fast_signature(r) for r in cache["refs"])
-    if cache.get("sig") != sig:
-        eng.load_weight_set([_engine.flat_weights(n.state_dict()) for n in nset.nets])
+    if cache.get("sig") != sig or (weights == "device" and cache.get("how") != "device"):
+        live = [] if weights == "host" else [_live_params(n, eng) for n in nset.nets]
+        if _use_device_reload(weights, [why for _, why in live] or ["host"]):
+            eng.load_weight_set_from([params for params, _ in live])
+            cache["how"] = "device"
+        else:
+            eng.load_weight_set([_engine.flat_weights(n.state_dict()) for n in nset.nets])
+            cache["how"] = "host"
         cache["sig"] = sig
     return eng
