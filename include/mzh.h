@@ -400,6 +400,40 @@ int mzh_memo_plan(int n_disks, int depth, int32_t* depth_out, int64_t* rows, int
 int mzh_memo_debug_table(mzh_engine* eng, float* latent /* nullable */, float* record /* nullable */, int64_t* rows,
                          int32_t* depth);
 
+/* The memo's grown extension.  Below depth D the roots of one state still walk almost
+ * the same subtrees, so the table grows from each wave search's own misses: extension rows (same latent and
+ * record as a dense row) follow the dense ones and are reached through a trie, link[row * 6 + action] = the
+ * child's row, hanging off the depth-D rows.  The search kernel only reads it: a root whose new node lies below
+ * D hits when its parent has a row and the link holds the child's.  Every root that missed logs the new node
+ * (a bounded per-root log; an entry that does not fit is dropped and the node inserted by a later launch), and
+ * mzh_search launches a harvest kernel on the same stream right after the search that claims a link per logged
+ * node, takes a row and copies the latent and the record the search computed -- so an extension row, like a
+ * dense one, is bit for bit what the search would compute, and results depend neither on the table's content
+ * nor on the order rows were given out.  A full extension stops growing.  It is made, dropped and freed with
+ * the dense table (a table of depth 0 has none) and has its scope: the wave kernels of mzh_search only.
+ *   budget_bytes: bytes of extension rows (288 each; 24 more per row of the whole table go to the links);
+ *     -1 the default (64 MiB), 0 off -- the search then behaves exactly as without the extension.
+ *   log_entries: entries of the per-root miss log (16 bytes each, allocated for max_roots); -1 the default (16).
+ * A change takes effect with the next search, which rebuilds the table when the capacity differs.  The
+ * environment variable MZH_MEMO_GROW_BYTES gives a new engine its initial budget_bytes; mzh_create refuses a
+ * value that is no integer or that this call would refuse. */
+int mzh_set_memo_grow(mzh_engine* eng, int64_t budget_bytes, int32_t log_entries);
+typedef struct mzh_memo_grow_info {
+  int64_t budget_bytes;       /* the request in force (the default's value for -1) */
+  int64_t capacity_rows;      /* extension rows of the built table (0: none built, or growth off) */
+  int64_t rows_used;          /* rows inserted since the build (the call waits for the device) */
+  int64_t rows_last_harvest;  /* rows the last harvest inserted */
+  int32_t log_entries;        /* per-root miss log entries in force */
+  int32_t reserved;
+} mzh_memo_grow_info;
+int mzh_memo_grow_stats(mzh_engine* eng, mzh_memo_grow_info* out);
+/* Debug: the built table's dense rows, extension capacity and rows in use and, where the device buffers are
+ * given, copies of the extension's latent [capacity][64] and record [capacity][8] (extension row i is table row
+ * dense_rows + i) and of the links [dense_rows + capacity][6] (the child's table row, 0 none).  Waits for the
+ * device. */
+int mzh_memo_debug_grow(mzh_engine* eng, float* latent /* nullable */, float* record /* nullable */,
+                        int32_t* link /* nullable */, int64_t* rows_used, int64_t* dense_rows, int64_t* capacity_rows);
+
 /* Search roots of several networks in one launch: root b is searched under network net_index[b] of the set
  * loaded by mzh_load_weight_set, with the result mzh_search gives on an engine holding that network alone
  * (bit for bit).  `args` is mzh_search's, unchanged: every input and output is indexed by root.  The roots of

@@ -67,6 +67,12 @@ class MemoInfo(ctypes.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class MemoGrowInfo(ctypes.Structure):
+    """mirror of struct mzh_memo_grow_info (include/mzh.h)"""
+    _fields_ = [("budget_bytes", ctypes.c_int64), ("capacity_rows", ctypes.c_int64), ("rows_used", ctypes.c_int64),
+                ("rows_last_harvest", ctypes.c_int64), ("log_entries", _i32), ("reserved", _i32)]
+
+
 class MultiArgs(ctypes.Structure):
     """mirror of struct mzh_multi_args (include/mzh.h)"""
     _fields_ = [("n_networks", _i32), ("net_index", _vp), ("status", _vp)]
@@ -179,6 +185,9 @@ SIGNATURES = {
     "mzh_memo_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(_i32), ctypes.POINTER(ctypes.c_int64),
                                      ctypes.POINTER(ctypes.c_int64)]),
     "mzh_memo_debug_table": (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(_i32)]),
+    "mzh_set_memo_grow": (ctypes.c_int, [_vp, ctypes.c_int64, _i32]),
+    "mzh_memo_grow_stats": (ctypes.c_int, [_vp, ctypes.POINTER(MemoGrowInfo)]),
+    "mzh_memo_debug_grow": (ctypes.c_int, [_vp, _vp, _vp, _vp] + [ctypes.POINTER(ctypes.c_int64)] * 3),
     "mzh_rng_predraw": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int,
                                        _vp, _vp, _vp]),
     "mzh_train_scratch_bytes": (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_size_t)]),

@@ -83,6 +83,17 @@ struct mzh_engine {
   float* memo_rec = nullptr;   // [rows][8]
   unsigned long long* memo_cnt = nullptr;  // [3] device counters, zeroed by mzh_create
   double memo_build_ms = 0.0;
+  // its grown extension (mzh_set_memo_grow): rows after the dense ones in memo_h / memo_rec, made and dropped
+  // with them; the per-root miss log is workspace (made by the first search that logs, kept across loads)
+  long long grow_want = -1;    // byte budget of the extension's rows: -1 the default, 0 off
+  int log_cap = MZH_MEMO_LOG_CAP;
+  long long memo_base = 0;     // dense rows of the built table
+  long long memo_cap = 0;      // extension rows of the built table (0: none)
+  int32_t* memo_link = nullptr;  // [memo_base + memo_cap][6]
+  int32_t* memo_ctr = nullptr;   // [2] rows in use, in use before the last harvest
+  uint4* memo_log = nullptr;     // [max_roots][memo_log_cap]
+  int32_t* memo_logn = nullptr;  // [max_roots]
+  int memo_log_cap = 0;          // what memo_log was allocated for
   // the transposed blobs of mzh_saliency (MzhPackedT; allocations of their own, uploaded with the weights they
   // are a function of and dropped with them)
   void* tbuf = nullptr;
@@ -178,6 +189,17 @@ extern "C" int mzh_create(int device, int n_disks, int max_sims, int max_roots, 
     }
     eng->memo_want = (int)d;
   }
+  // MZH_MEMO_GROW_BYTES: likewise the initial request of mzh_set_memo_grow (-1 the default budget, 0 off)
+  if (const char* v = getenv("MZH_MEMO_GROW_BYTES")) {
+    char* end = nullptr;
+    const long long b = strtoll(v, &end, 10);
+    if (end == v || *end != '\0' || b < -1 || b > MZH_MEMO_MAX_ROWS * MZH_MEMO_ROW_BYTES) {
+      delete eng;
+      return fail(MZH_ERR_ARG, "MZH_MEMO_GROW_BYTES='%s': expected an integer in [-1, %lld]", v,
+                  MZH_MEMO_MAX_ROWS * MZH_MEMO_ROW_BYTES);
+    }
+    eng->grow_want = b;
+  }
   const size_t nblk = (size_t)max_roots * eng->E;
   // MzhBlock (mzh_tree.h) / MzwBlock (mzh_wave.hip): one 128-B cache line per expanded node
   hipError_t e = hipMalloc(&eng->tree, nblk * 128);  // one 128-B block per expanded node
@@ -216,6 +238,10 @@ extern "C" int mzh_destroy(mzh_engine* eng) {
   if (eng->memo_h) (void)hipFree(eng->memo_h);
   if (eng->memo_rec) (void)hipFree(eng->memo_rec);
   if (eng->memo_cnt) (void)hipFree(eng->memo_cnt);
+  if (eng->memo_link) (void)hipFree(eng->memo_link);
+  if (eng->memo_ctr) (void)hipFree(eng->memo_ctr);
+  if (eng->memo_log) (void)hipFree(eng->memo_log);
+  if (eng->memo_logn) (void)hipFree(eng->memo_logn);
   if (eng->tbuf) (void)hipFree(eng->tbuf);
   if (eng->settbuf) (void)hipFree(eng->settbuf);
   if (eng->rmap) (void)hipFree(eng->rmap);
@@ -236,9 +262,14 @@ static hipError_t memo_drop(mzh_engine* eng) {
   if (e != hipSuccess) return e;
   if (eng->memo_h) (void)hipFree(eng->memo_h);
   if (eng->memo_rec) (void)hipFree(eng->memo_rec);
+  if (eng->memo_link) (void)hipFree(eng->memo_link);
+  if (eng->memo_ctr) (void)hipFree(eng->memo_ctr);
   eng->memo_h = nullptr;
   eng->memo_rec = nullptr;
+  eng->memo_link = nullptr;
+  eng->memo_ctr = nullptr;
   eng->memo_D = 0;
+  eng->memo_base = eng->memo_cap = 0;
   return hipSuccess;
 }
 
@@ -939,12 +970,18 @@ static int memo_effective_depth(const mzh_engine* eng, int* D) {
 // states through initial inference, then every (node, move) of the level above through recurrent inference.
 // Within a level the rows are ordered (state, node): child row = 6 * parent row + move.  Runs on `stream` and
 // waits for it (the temporaries are freed on return).
+// the extension rows the engine's request gives beside `dense_rows` dense ones
+static long long memo_grow_cap(const mzh_engine* eng, long long dense_rows) {
+  return mzh_memo_grow_rows(eng->grow_want < 0 ? MZH_MEMO_GROW_BUDGET_BYTES : eng->grow_want, dense_rows);
+}
+
 static int memo_build(mzh_engine* eng, int D, hipStream_t stream, bool* oom) {
   *oom = false;
   HIP_OK(memo_drop(eng));
   const auto t_start = std::chrono::steady_clock::now();
   const int N = eng->n_disks, in = eng->in_dim;
   const long long ST = mzh_memo_states(N), K = mzh_memo_nodes(D), rows = ST * K;
+  const long long cap = memo_grow_cap(eng, rows);  // the grown extension's rows follow the dense ones
   long long top = ST;  // rows of the deepest level
   for (int d = 0; d < D; ++d) top *= 6;
   std::vector<float> obs((size_t)ST * in, 0.0f);
@@ -964,8 +1001,10 @@ static int memo_build(mzh_engine* eng, int D, hipStream_t stream, bool* oom) {
     (void)memo_drop(eng);
     return hip_fail(e, what);
   };
-  hipError_t e = hipMalloc(&eng->memo_h, (size_t)rows * MZH_LATENT * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&eng->memo_rec, (size_t)rows * 8 * sizeof(float));
+  hipError_t e = hipMalloc(&eng->memo_h, (size_t)(rows + cap) * MZH_LATENT * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc(&eng->memo_rec, (size_t)(rows + cap) * 8 * sizeof(float));
+  if (e == hipSuccess && cap > 0) e = hipMalloc(&eng->memo_link, (size_t)(rows + cap) * 6 * sizeof(int32_t));
+  if (e == hipSuccess && cap > 0) e = hipMalloc(&eng->memo_ctr, 2 * sizeof(int32_t));
   if (e == hipSuccess) e = hipMalloc(&dobs, obs.size() * sizeof(float));
   if (e == hipSuccess) e = hipMalloc(&hA, (size_t)top * MZH_LATENT * sizeof(float));
   if (e == hipSuccess) e = hipMalloc(&hB, (size_t)(top / 6 + 1) * MZH_LATENT * sizeof(float));
@@ -981,6 +1020,9 @@ static int memo_build(mzh_engine* eng, int D, hipStream_t stream, bool* oom) {
   }
   e = hipMemcpyAsync(dobs, obs.data(), obs.size() * sizeof(float), hipMemcpyHostToDevice, stream);
   if (e == hipSuccess) e = hipMemsetAsync(rw, 0, (size_t)ST * sizeof(float), stream);  // a root has no reward
+  if (e == hipSuccess && cap > 0)  // every link MZH_LINK_NONE, no row in use
+    e = hipMemsetAsync(eng->memo_link, 0, (size_t)(rows + cap) * 6 * sizeof(int32_t), stream);
+  if (e == hipSuccess && cap > 0) e = hipMemsetAsync(eng->memo_ctr, 0, 2 * sizeof(int32_t), stream);
   if (e != hipSuccess) return bail(e, "memo build: upload");
   // the level's outputs go to hcur; levels alternate between hA and hB so that the deepest lands in hA
   float* hcur = (D % 2 == 0) ? hA : hB;
@@ -1008,6 +1050,8 @@ static int memo_build(mzh_engine* eng, int D, hipStream_t stream, bool* oom) {
   if (e != hipSuccess) return bail(e, "memo build: run");
   release();
   eng->memo_D = D;
+  eng->memo_base = rows;
+  eng->memo_cap = cap;
   // what the building search call paid: allocations, the fill, the wait and the frees, on the host's clock
   eng->memo_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
   return MZH_OK;
@@ -1022,7 +1066,7 @@ static int memo_ensure(mzh_engine* eng, hipStream_t stream) {
     int D = 0;
     const int st = memo_effective_depth(eng, &D);
     if (st) return st;
-    if (D == eng->memo_D) return MZH_OK;
+    if (D == eng->memo_D && (D == 0 || eng->memo_cap == memo_grow_cap(eng, eng->memo_base))) return MZH_OK;
     if (D == 0) {
       HIP_OK(memo_drop(eng));
       return MZH_OK;
@@ -1032,6 +1076,77 @@ static int memo_ensure(mzh_engine* eng, hipStream_t stream) {
     if (bs == MZH_OK || eng->memo_want >= 0 || !oom) return bs;
     eng->memo_auto_cap = D - 1;
   }
+}
+
+// the per-root miss log of the grown extension: workspace for max_roots roots at the engine's log cap
+static int memo_log_ensure(mzh_engine* eng) {
+  if (eng->memo_log && eng->memo_log_cap == eng->log_cap) return MZH_OK;
+  if ((long long)eng->max_roots * eng->log_cap >= (1ll << 31))  // the kernel indexes entries in 32 bits
+    return fail(MZH_ERR_CAPACITY, "memo miss log: %d roots x %d entries", eng->max_roots, eng->log_cap);
+  if (eng->memo_log) {
+    ++eng->n_wait;
+    HIP_OK(hipDeviceSynchronize());
+    (void)hipFree(eng->memo_log);
+    eng->memo_log = nullptr;
+  }
+  HIP_OK(hipMalloc(&eng->memo_log, (size_t)eng->max_roots * eng->log_cap * sizeof(uint4)));
+  eng->memo_log_cap = eng->log_cap;
+  if (!eng->memo_logn) {
+    HIP_OK(hipMalloc(&eng->memo_logn, (size_t)eng->max_roots * sizeof(int32_t)));
+    HIP_OK(hipMemset(eng->memo_logn, 0, (size_t)eng->max_roots * sizeof(int32_t)));
+  }
+  return MZH_OK;
+}
+
+extern "C" int mzh_set_memo_grow(mzh_engine* eng, int64_t budget_bytes, int32_t log_entries) {
+  if (budget_bytes < -1 || budget_bytes > MZH_MEMO_MAX_ROWS * MZH_MEMO_ROW_BYTES)
+    return fail(MZH_ERR_ARG, "memo growth budget must be -1 (default), 0 (off) or up to %lld bytes, got %lld",
+                MZH_MEMO_MAX_ROWS * MZH_MEMO_ROW_BYTES, (long long)budget_bytes);
+  if (log_entries < -1 || log_entries == 0 || log_entries > MZH_MEMO_LOG_CAP_MAX)
+    return fail(MZH_ERR_ARG, "memo miss log entries per root must be -1 (default) or 1..%d, got %d",
+                MZH_MEMO_LOG_CAP_MAX, (int)log_entries);
+  if (!eng) return fail(MZH_ERR_ARG, "engine NULL");
+  eng->grow_want = budget_bytes;
+  eng->log_cap = log_entries < 0 ? MZH_MEMO_LOG_CAP : log_entries;
+  return MZH_OK;
+}
+
+extern "C" int mzh_memo_grow_stats(mzh_engine* eng, mzh_memo_grow_info* out) {
+  if (!eng || !out) return fail(MZH_ERR_ARG, "memo_grow_stats: engine or out NULL");
+  memset(out, 0, sizeof(*out));
+  out->budget_bytes = eng->grow_want < 0 ? MZH_MEMO_GROW_BUDGET_BYTES : eng->grow_want;
+  out->log_entries = eng->log_cap;
+  out->capacity_rows = eng->memo_cap;
+  if (eng->memo_cap == 0) return MZH_OK;
+  DeviceGuard g(eng->device);
+  if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+  int32_t c[2] = {0, 0};
+  HIP_OK(hipDeviceSynchronize());
+  HIP_OK(hipMemcpy(c, eng->memo_ctr, sizeof(c), hipMemcpyDeviceToHost));
+  out->rows_used = c[0];
+  out->rows_last_harvest = c[0] - c[1];
+  return MZH_OK;
+}
+
+extern "C" int mzh_memo_debug_grow(mzh_engine* eng, float* latent, float* record, int32_t* link, int64_t* rows_used,
+                                   int64_t* dense_rows, int64_t* capacity_rows) {
+  if (!eng || !rows_used || !dense_rows || !capacity_rows) return fail(MZH_ERR_ARG, "memo_debug_grow: NULL argument");
+  *rows_used = 0;
+  *dense_rows = eng->memo_base;
+  *capacity_rows = eng->memo_cap;
+  if (eng->memo_cap == 0) return MZH_OK;
+  DeviceGuard g(eng->device);
+  if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+  int32_t used = 0;
+  HIP_OK(hipDeviceSynchronize());
+  HIP_OK(hipMemcpy(&used, eng->memo_ctr, sizeof(used), hipMemcpyDeviceToHost));
+  *rows_used = used;
+  const size_t b = (size_t)eng->memo_base, n = (size_t)eng->memo_cap;
+  if (latent) HIP_OK(hipMemcpy(latent, eng->memo_h + b * MZH_LATENT, n * MZH_LATENT * sizeof(float), hipMemcpyDeviceToDevice));
+  if (record) HIP_OK(hipMemcpy(record, eng->memo_rec + b * 8, n * 8 * sizeof(float), hipMemcpyDeviceToDevice));
+  if (link) HIP_OK(hipMemcpy(link, eng->memo_link, (b + n) * 6 * sizeof(int32_t), hipMemcpyDeviceToDevice));
+  HIP_OK(hipDeviceSynchronize());
+  return MZH_OK;
 }
 
 extern "C" int mzh_memo_stats(mzh_engine* eng, mzh_memo_info* out) {
@@ -1102,17 +1217,33 @@ static int search_common(mzh_engine* eng, const mzh_search_args* a, mzh_stream s
   DeviceGuard g(eng->device);
   if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
   MzhSearchParams p = search_params(eng, a);
+  bool harvest = false;
   if (pl.wave && !replay) {  // the expansion memo: wave MLP searches only, built on first use
     const int ms = memo_ensure(eng, (hipStream_t)stream);
     if (ms) return ms;
     if (eng->memo_D > 0) {
       p.memo_h = eng->memo_h; p.memo_rec = eng->memo_rec; p.memo_cnt = eng->memo_cnt;
       p.memo_D = eng->memo_D; p.memo_K = (int)mzh_memo_nodes(eng->memo_D);
+      if (eng->memo_cap > 0) {  // the grown extension: its links, and the miss log the harvest below reads
+        const int ls = memo_log_ensure(eng);
+        if (ls) return ls;
+        p.memo_link = eng->memo_link; p.memo_ctr = eng->memo_ctr; p.memo_cap = (int)eng->memo_cap;
+        p.memo_log = eng->memo_log; p.memo_logn = eng->memo_logn; p.memo_logcap = eng->memo_log_cap;
+        harvest = true;
+      }
     }
   }
   hipError_t e = pl.one ? mzh_launch_one(pl, eng->net, eng->onet, p, (hipStream_t)stream)
                  : pl.wave ? mzh_launch_wave_search(pl, eng->wnet, p, (hipStream_t)stream)
                            : mzh_launch_search(pl, eng->net, p, (hipStream_t)stream);
+  if (e == hipSuccess && harvest) {
+    MzhHarvestParams h{};
+    h.B = p.B; h.E = p.E; h.tree = p.tree; h.htree = p.htree;
+    h.log = p.memo_log; h.logn = p.memo_logn; h.logcap = p.memo_logcap;
+    h.link = eng->memo_link; h.ctr = eng->memo_ctr; h.base = (int)eng->memo_base; h.cap = (int)eng->memo_cap;
+    h.memo_h = eng->memo_h; h.memo_rec = eng->memo_rec;
+    e = mzh_launch_memo_harvest(h, (hipStream_t)stream);
+  }
   return e == hipSuccess ? MZH_OK : hip_fail(e, "search launch");
 }
 

@@ -42,7 +42,33 @@ struct MzhSearchParams {
   const float* memo_rec;  // [rows][8] 6 priors, reward, value
   unsigned long long* memo_cnt;  // [3] (wave, simulation) pairs without MLP / packed / full
   int memo_D, memo_K;     // depth, nodes per state 1 + 6 + ... + 6^D
+  // the memo's grown extension (all null / 0 with growth off): rows after the dense ones,
+  // reached through a trie of child links, filled between launches from the per-root miss log
+  const int32_t* memo_link;  // [dense rows + memo_cap][6] the child's row, MZH_LINK_NONE or MZH_LINK_CLAIM
+  uint4* memo_log;           // [B][memo_logcap] {new slot, parent slot e * 8 + a, value bits, reward bits}
+  int32_t* memo_logn;        // [B] entries of the root's log
+  int32_t* memo_ctr;         // [2] extension rows in use, and in use before the last harvest
+  int memo_cap, memo_logcap; // extension rows, log entries per root
 };
+#define MZH_LINK_NONE 0      // (a child's row is always > 0: extension rows follow the dense ones)
+#define MZH_LINK_CLAIM (-1)
+
+// the harvest after a wave search (mzh_memo_harvest_kernel, mzh_wave.hip): one thread per root inserts the
+// root's logged misses into the extension
+struct MzhHarvestParams {
+  int B, E;
+  unsigned char* tree;   // [B][E] MzwBlock
+  const float* htree;    // [B][E][64]
+  const uint4* log;
+  const int32_t* logn;
+  int logcap;
+  int32_t* link;
+  int32_t* ctr;
+  int base, cap;         // dense rows, extension rows
+  float* memo_h;
+  float* memo_rec;
+};
+hipError_t mzh_launch_memo_harvest(const MzhHarvestParams& h, hipStream_t stream);
 
 // Expansion-memo arithmetic (host): nodes per state, rows and bytes at depth D, the automatic depth
 static inline long long mzh_memo_nodes(int D) {  // K(D) = (6^(D+1) - 1) / 5
@@ -60,6 +86,16 @@ static inline long long mzh_memo_states(int n_disks) {
 #define MZH_MEMO_MAX_DEPTH 12
 // the byte budget of the automatic depth (N = 4 gets D = 5, N = 7 gets D = 3)
 #define MZH_MEMO_BUDGET_BYTES (256ll << 20)
+// the byte budget of the grown extension's rows (the default of mzh_set_memo_grow) and the per-root miss log's
+// default entries: a cold four-disc root misses about 15 times in 50 simulations
+#define MZH_MEMO_GROW_BUDGET_BYTES (64ll << 20)
+#define MZH_MEMO_LOG_CAP 16
+#define MZH_MEMO_LOG_CAP_MAX 1024
+static inline long long mzh_memo_grow_rows(long long budget_bytes, long long dense_rows) {
+  long long cap = budget_bytes / MZH_MEMO_ROW_BYTES;
+  if (cap > MZH_MEMO_MAX_ROWS) cap = MZH_MEMO_MAX_ROWS;  // (dense + cap) * 6 link indices stay inside int32
+  return dense_rows > 0 ? cap : 0;
+}
 static inline int mzh_memo_auto_depth(int n_disks) {
   const long long st = mzh_memo_states(n_disks);
   int D = 0;

@@ -471,13 +471,18 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
   const int half = lane >> 5;
   const int rroot = wr0 + rho;
   const bool rvalid = rho < ROOTS && rroot < p.B;
-  MzwBlock* tb = reinterpret_cast<MzwBlock*>(p.tree) + (size_t)(rvalid ? rroot : 0) * E;
+  // the root's tree blocks: block e is TB(e) (the root's first block as a 32-bit index, not a pointer: one register)
+  const int tb0 = (rvalid ? rroot : 0) * p.E;
+  auto TB = [&](int e) -> MzwBlock& { return reinterpret_cast<MzwBlock*>(p.tree)[(size_t)(unsigned)(tb0 + e)]; };
   MzhMinMax mm;
   if (rvalid && p.minmax_in)
     mm.set(p.minmax_in[2 * rroot], p.minmax_in[2 * rroot + 1]);
   else
     mm.set(-__builtin_inf(), __builtin_inf());
-  int firstTie = 0, extra = 0, steps = 0, rootN = 0, depth = 0, leafE = 0, leafA = 0;
+  int firstTie = 0, extra = 0, steps = 0, rootN = 0, depth = 0;
+  // the selected leaf as a path slot, its parent's expanded index * 8 + the move (below 2^18), and above it the
+  // entries of this root's miss log (at most MZH_MEMO_LOG_CAP_MAX): one register for both
+  int leaf = 0;
   int lsum = 0;  // p.lockstep_levels: the wave's deepest selection below the root, summed over simulations
   double rootW = 0.0;
   const int tie = (rvalid && p.tie_idx) ? p.tie_idx[rroot] : 0;
@@ -488,6 +493,10 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
   int sigma = -1;
   unsigned pid = 0;
   unsigned cnt = 0;  // simulations without an M phase (low 16 bits; S <= 32000) | with the packed one (high 16)
+  // the grown extension (wave-uniform): grow = its links are consulted below the dense depth; glog = this launch
+  // logs its misses for the harvest (not once the extension is full).  nlog: entries of this root's log
+  const bool grow = memo && p.memo_link != nullptr;
+  const bool glog = grow && p.memo_log != nullptr && p.memo_ctr[0] < p.memo_cap;
   if (memo && rvalid) {
     const unsigned* orow = reinterpret_cast<const unsigned*>(p.obs) + (size_t)rroot * p.in_dim;
     int sg = 0, w3 = 1;
@@ -659,7 +668,7 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
           // the picked child's fields come from the lane that holds them over v_permlane32_swap
           // (16,384 roots -1.4%; at 32 roots per wave, once the buffer-load weight stream freed the
           // registers it spilled in round 3: 65,536 roots -0.9%, 262,144 -1.3%)
-          const unsigned char* blk = reinterpret_cast<const unsigned char*>(&tb[e]);
+          const unsigned char* blk = reinterpret_cast<const unsigned char*>(&TB(e));
           const uint3 hnx = *reinterpret_cast<const uint3*>(blk + 12 * half);
           const uint3 hR = *reinterpret_cast<const uint3*>(blk + 24 + 12 * half);
           const uint3 hP = *reinterpret_cast<const uint3*>(blk + 48 + 12 * half);
@@ -676,9 +685,9 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
           if (kPF) {
             asm volatile("" ::"v"(pf0), "v"(pf1), "v"(pf2));
             const int x0 = hn[0] >> 16, x1 = hn[1] >> 16, x2 = hn[2] >> 16;
-            pf0 = *reinterpret_cast<const int*>(&tb[x0 >= 0 ? x0 : e]);
-            pf1 = *reinterpret_cast<const int*>(&tb[x1 >= 0 ? x1 : e]);
-            pf2 = *reinterpret_cast<const int*>(&tb[x2 >= 0 ? x2 : e]);
+            pf0 = *reinterpret_cast<const int*>(&TB(x0 >= 0 ? x0 : e));
+            pf1 = *reinterpret_cast<const int*>(&TB(x1 >= 0 ? x1 : e));
+            pf2 = *reinterpret_cast<const int*>(&TB(x2 >= 0 ? x2 : e));
           }
           const double tn = table[Np];
   #pragma unroll
@@ -721,8 +730,7 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
       }
       if (kPF) asm volatile("" ::"v"(pf0), "v"(pf1), "v"(pf2));
       depth = d;
-      leafE = e;
-      leafA = pick;
+      leaf = (leaf & ~0x3FFFF) | (e * 8 + pick);
       steps += d;
     }
     if (p.lockstep_levels) {  // wave-uniform: only when the caller asks for the latency model's input
@@ -796,8 +804,13 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
   };
 
   // the new nodes' blocks of the columns an M phase evaluated
-  auto phase_blocks = [&](int s, auto& C) {
+  // hrow (root lanes, the wave's own tiles only): the table row of a root that hit, or -1; its row + 1 goes into
+  // the block's pad[0] so that the node's children find their parent's row (0: not a table node)
+  auto phase_blocks = [&](int s, auto& C, bool own, int hrow) {
     constexpr int NC = sizeof(C.root) / sizeof(int);
+    unsigned trow[NC];
+#pragma unroll
+    for (int n = 0; n < NC; ++n) trow[n] = own ? (unsigned)(__shfl(hrow, 16 * n + col) + 1) : 0u;
     // the new node's 6 children (node.py:44-49): N = 0, X = -1, R = 0, P, W = 0.  The whole 128-B
     // line as eight 16-B stores, two per lane group (lane groups 0/1 hold pi[0..3] / pi[4..5]):
     // a line written whole is valid in L2 without a fill from HBM.  Chunk k = bytes 16k..16k+15:
@@ -817,7 +830,7 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
         c1 = make_uint4(__float_as_uint(C.cpi[n][0]), __float_as_uint(C.cpi[n][1]), 0u, 0u);
       } else {
         c0 = make_uint4(0u, 0u, 0u, 0u);
-        c1 = c0;
+        c1 = make_uint4(0u, 0u, g == 3 ? trow[n] : 0u, 0u);  // chunk 7: W5 | pad[0] pad[1]
       }
       // g0: chunks 0, 3; g1: chunks 1, 4; g2: chunks 2, 5; g3: chunks 6, 7
       const int k0 = g < 3 ? g : 6, k1 = g < 3 ? g + 3 : 7;
@@ -830,20 +843,23 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
   // fromrec (root lanes): the new node's outputs come from a 32-byte record -- the replay records, or the
   // memo's row of a root that hit it in a simulation that ran no MLP for it; else vcol / rcol: the value and
   // reward its column evaluated
-  auto phase_head = [&](int s, bool fromrec, float vcol, float rcol) {
+  // hrow: the memo row of a root that hit (dense or grown), -1 otherwise.  A root that missed although its
+  // observation is a state's appends the new node to its miss log (dropped when the log is full: the node is
+  // then inserted by a later launch)
+  auto phase_head = [&](int s, bool fromrec, float vcol, float rcol, int hrow) {
     // ---------------- expand bookkeeping + backup (node.py:30-70): one lane per root ----------------
     if (rvalid) {
       const int enew = s + 1;
+      const int leafE = (leaf & 0x3FFFF) >> 3, leafA = leaf & 7;
       float vv, rr;
       if (REPLAY || fromrec) {
         const uint4* rec = reinterpret_cast<const uint4*>(
-            REPLAY ? p.rp_sim + ((size_t)s * p.B + rroot) * 8
-                   : p.memo_rec + ((size_t)sigma * p.memo_K + (6u * pid + (unsigned)leafA + 1u)) * 8);
+            REPLAY ? p.rp_sim + ((size_t)s * p.B + rroot) * 8 : p.memo_rec + (size_t)hrow * 8);
         const uint4 r0 = rec[0], r1 = rec[1];  // priors 0-3 | priors 4, 5, reward, value
         rr = __uint_as_float(r1.z);
         vv = __uint_as_float(r1.w);
         // the whole 128-B line as eight 16-B stores (see phase_head's fused form)
-        uint4* nb = reinterpret_cast<uint4*>(&tb[enew]);
+        uint4* nb = reinterpret_cast<uint4*>(&TB(enew));
         const uint32_t nx = 0xFFFF0000u;
         const uint4 z = make_uint4(0u, 0u, 0u, 0u);
         nb[0] = make_uint4(nx, nx, nx, nx);
@@ -853,17 +869,27 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
         nb[4] = make_uint4(r1.x, r1.y, 0u, 0u);
         nb[5] = z;
         nb[6] = z;
-        nb[7] = z;
+        nb[7] = REPLAY ? z : make_uint4(0u, 0u, (unsigned)(hrow + 1), 0u);  // pad[0]: the node's row + 1
       } else {
         vv = vcol;
         rr = rcol;
+        if (!REPLAY && glog && sigma >= 0 && hrow < 0 && (leaf >> 18) < p.memo_logcap) {
+          // (the entry's address is made here from an opaque copy of the root: hoisted out of the simulation
+          // loop, the root's log pointer is two more registers across the M phase -- scratch at 32 roots per wave)
+          int ro = rroot;
+          asm volatile("" : "+v"(ro));
+          if (!half)
+            p.memo_log[(unsigned)(ro * p.memo_logcap + (leaf >> 18))] =
+                make_uint4((unsigned)enew, (unsigned)(leaf & 0x3FFFF), __float_as_uint(vv), __float_as_uint(rr));
+          leaf += 1 << 18;
+        }
       }
       if (leafE == 0) {
         ws.rX[leafA][rho] = enew;
         ws.rR[leafA][rho] = rr;
       } else {
-        tb[leafE].nx[leafA].X = (int16_t)enew;
-        tb[leafE].R[leafA] = rr;
+        TB(leafE).nx[leafA].X = (int16_t)enew;
+        TB(leafE).R[leafA] = rr;
       }
       double v = (double)vv;
       double lmax = -__builtin_inf(), lmin = __builtin_inf();
@@ -878,9 +904,9 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
       auto load_hbm = [&](int j, int& slot, double& W, float& R, int& N) {  // depths >= MZW_DC
         slot = p.pathx[(size_t)rroot * E + j];
         const int e = slot >> 3, a = slot & 7;
-        W = tb[e].W[a];
-        R = tb[e].R[a];
-        N = tb[e].nx[a].N;
+        W = TB(e).W[a];
+        R = TB(e).R[a];
+        N = TB(e).nx[a].N;
       };
       int slot;
       double Wj;
@@ -906,8 +932,8 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
         double Wn;
         int Nn;
         node(jn, Wn, Nn);
-        tb[e].W[a] = Wn;
-        tb[e].nx[a].N = (uint16_t)Nn;
+        TB(e).W[a] = Wn;
+        TB(e).nx[a].N = (uint16_t)Nn;
       };
       for (; j >= 1; --j) {
         int slot_n, Nj_n;
@@ -955,23 +981,38 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
     int mode = 2, nm = 0;
     unsigned mask = 0;
     bool hit = false;
+    // the memo rows (root lanes) of the leaf's parent and of the new node, -1 without one.  Down to the dense
+    // depth a row is arithmetic; below it the parent's comes from its block's pad[0] (the line selection just
+    // loaded) and the new node's from the parent's child link.  A memo node's latent is read from the table,
+    // never from htree
+    int prow_r = -1, hrow = -1;
+    const int leafE = (leaf & 0x3FFFF) >> 3, leafA = leaf & 7;
+    if (memo && sigma >= 0) {  // (sigma >= 0 only on valid root lanes)
+      if (depth - 1 <= p.memo_D) prow_r = sigma * p.memo_K + (int)pid;
+      else if (grow) prow_r = (int)TB(leafE).pad[0] - 1;
+      if (depth <= p.memo_D) {
+        hrow = sigma * p.memo_K + (int)(6u * pid + (unsigned)leafA + 1u);
+      } else if (grow && prow_r >= 0) {
+        const int l = p.memo_link[prow_r * 6 + leafA];
+        hrow = l > 0 ? l : -1;
+      }
+    }
     if (memo) {
-      hit = rvalid && sigma >= 0 && depth <= p.memo_D;
+      hit = hrow >= 0;
       // bit rho: lanes 0-31 (lanes 32-63 mirror them)
       mask = __builtin_amdgcn_readfirstlane((unsigned)__ballot(rvalid && !hit));
       nm = __popc(mask);
       mode = nm == 0 ? 0 : (NT == 2 && nm <= 16) ? 1 : 2;
       cnt = __builtin_amdgcn_readfirstlane(cnt + (mode == 0 ? 1u : mode == 1 ? 0x10000u : 0u));
     }
-    // the parent's memo row (root lanes): a memo node's latent is read from the table, never from htree
-    const int prow_r = (memo && sigma >= 0 && depth - 1 <= p.memo_D) ? sigma * p.memo_K + (int)pid : -1;
     float vcol = 0.0f, rcol = 0.0f;
     if (mode == 2) {
       if (!REPLAY) {
 #pragma unroll
         for (int n = 0; n < NT; ++n) {
-          cf.en[n] = __shfl(leafE, 16 * n + col);
-          cf.an[n] = __shfl(leafA, 16 * n + col);
+          const int lf = __shfl(leaf, 16 * n + col);
+          cf.en[n] = (lf & 0x3FFFF) >> 3;
+          cf.an[n] = lf & 7;
           if (memo) cf.prow[n] = __shfl(prow_r, 16 * n + col);
         }
         phase_mlp(s, cf);
@@ -999,8 +1040,9 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
       const int r = pv ? rs : (int)__builtin_ctz(mask);  // spare columns repeat the first missing root
       cp.root[0] = wr0 + r;
       cp.valid[0] = pv;
-      cp.en[0] = __shfl(leafE, r);
-      cp.an[0] = __shfl(leafA, r);
+      const int lf = __shfl(leaf, r);
+      cp.en[0] = (lf & 0x3FFFF) >> 3;
+      cp.an[0] = lf & 7;
       cp.prow[0] = __shfl(prow_r, r);
       phase_mlp(s, cp);
       vcol = __shfl(cp.val[0], rank);  // a missing root's column is its rank (every row holds the scalars)
@@ -1010,10 +1052,10 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
     __builtin_amdgcn_s_setprio(0);
     MZH_STAMP(1);
     if (!REPLAY) {
-      if (mode == 2) phase_blocks(s, cf);
-      else if (NT == 2 && mode == 1) phase_blocks(s, cp);  // (cp is never valid in a 16-root wave)
+      if (mode == 2) phase_blocks(s, cf, true, hrow);  // (the own tiles evaluate the roots that hit as well)
+      else if (NT == 2 && mode == 1) phase_blocks(s, cp, false, -1);  // (cp is never valid in a 16-root wave)
     }
-    phase_head(s, mode != 2 && hit, vcol, rcol);
+    phase_head(s, mode != 2 && hit, vcol, rcol, hrow);
     MZH_STAMP(2);
     // this simulation's tree stores (other lanes' new-block writes) before the next selection
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
@@ -1027,8 +1069,11 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
     atomicAdd(p.memo_cnt + 0, (unsigned long long)nskip);
     atomicAdd(p.memo_cnt + 1, (unsigned long long)npack);
     atomicAdd(p.memo_cnt + 2, (unsigned long long)((unsigned)S - nskip - npack));
+    // the extension's rows before this launch's harvest (nothing changes them while a search runs)
+    if (p.memo_logn && blockIdx.x == 0 && wave == 0) p.memo_ctr[1] = p.memo_ctr[0];
   }
   if (!rvalid || half) return;
+  if (!REPLAY && p.memo_logn) p.memo_logn[rroot] = leaf >> 18;
   int vis[MZH_A];
   for (int a = 0; a < MZH_A; ++a) vis[a] = ws.rN[a][rho];
   mzh_write_results(p, rroot, vis, rootW, rootN, mm.mmax, mm.mmin, extra, steps, depth, [&](int j) {
@@ -1101,6 +1146,61 @@ hipError_t mzh_launch_memo_scatter(const float* h, const float* pi, const float*
   const long long blocks = (n * 64 + 255) / 256;
   hipLaunchKernelGGL(mzh_memo_scatter_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, h, pi, reward, value, n,
                      per_state, K, first_id, memo_h, memo_rec);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// Harvest (after a wave search, same stream): one thread per root walks the root's miss log in simulation order
+// and inserts each node whose parent has a row into the extension.  A node's parent was expanded in an earlier
+// simulation, so its row may have been assigned a moment ago by this thread (pad[0] of the parent's block).
+// The child link is claimed with one compare-and-swap; a loser whose node is already published adopts that row
+// for its own chain, one whose node is still being claimed skips it (the content would be the same; the node is
+// inserted by a later launch if it recurs).  A row is the latent the search stored in htree and the record it
+// put in the tree: bit for bit what the kernel computed.  The next search sees all of it through the kernel
+// boundary; within this kernel only row indices travel between threads.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void mzh_memo_harvest_kernel(MzhHarvestParams h) {
+  const int root = blockIdx.x * 256 + threadIdx.x;
+  if (root >= h.B) return;
+  int n = h.logn[root];
+  if (n <= 0) return;
+  n = min(n, h.logcap);
+  MzwBlock* tb = reinterpret_cast<MzwBlock*>(h.tree) + (size_t)root * h.E;
+  const uint4* log = h.log + (size_t)root * h.logcap;
+  for (int i = 0; i < n; ++i) {
+    const uint4 en = log[i];
+    const int e = (int)en.x, pe = (int)(en.y >> 3), a = (int)(en.y & 7u);
+    if (e < 1 || e >= h.E || pe < 1 || pe >= h.E || a >= MZH_A) continue;  // (never: the kernel's own entries)
+    const int prow = (int)tb[pe].pad[0] - 1;
+    if (prow < 0 || prow >= h.base + h.cap) continue;  // the parent has no row
+    int32_t* lk = h.link + prow * 6 + a;
+    const int old = atomicCAS(lk, MZH_LINK_NONE, MZH_LINK_CLAIM);
+    if (old > 0) {  // published by another root of this state: chain through it
+      tb[e].pad[0] = (uint32_t)(old + 1);
+      continue;
+    }
+    if (old != MZH_LINK_NONE) continue;  // being claimed
+    const int r = atomicAdd(h.ctr, 1);
+    if (r >= h.cap) {  // full: give the row and the claim back
+      atomicSub(h.ctr, 1);
+      atomicExch(lk, MZH_LINK_NONE);
+      return;
+    }
+    const int row = h.base + r;
+    const float4* src = reinterpret_cast<const float4*>(h.htree + ((size_t)root * h.E + e) * MZH_H);
+    float4* dst = reinterpret_cast<float4*>(h.memo_h + (size_t)row * MZH_H);
+#pragma unroll
+    for (int k = 0; k < MZH_H / 4; ++k) dst[k] = src[k];
+    const float* P = tb[e].P;
+    float4* rec = reinterpret_cast<float4*>(h.memo_rec + (size_t)row * 8);
+    rec[0] = make_float4(P[0], P[1], P[2], P[3]);
+    rec[1] = make_float4(P[4], P[5], __uint_as_float(en.w), __uint_as_float(en.z));  // reward, value
+    atomicExch(lk, row);
+    tb[e].pad[0] = (uint32_t)(row + 1);
+  }
+}
+hipError_t mzh_launch_memo_harvest(const MzhHarvestParams& h, hipStream_t stream) {
+  hipLaunchKernelGGL(mzh_memo_harvest_kernel, dim3((unsigned)((h.B + 255) / 256)), dim3(256), 0, stream, h);
   return hipGetLastError();
 }
 

@@ -320,10 +320,38 @@ class Engine:
 
     def memo_stats(self):
         """mzh_memo_stats as a dict: depth, built, rows, table_bytes, build_ms and the cumulative
-        pairs_skipped / pairs_packed / pairs_full of the wave searches (waits for the device)"""
+        pairs_skipped / pairs_packed / pairs_full of the wave searches (waits for the device); and, of the grown
+        extension (mzh_memo_grow_stats): grow_budget_bytes, grow_capacity, grow_rows (in use), grow_rows_last
+        (inserted by the last harvest), grow_log_entries"""
         info = _lib.MemoInfo()
         check(_lib.lib().mzh_memo_stats(self._h, ctypes.byref(info)), "mzh_memo_stats")
-        return info.as_dict()
+        g = _lib.MemoGrowInfo()
+        check(_lib.lib().mzh_memo_grow_stats(self._h, ctypes.byref(g)), "mzh_memo_grow_stats")
+        return dict(info.as_dict(), grow_budget_bytes=g.budget_bytes, grow_capacity=g.capacity_rows,
+                    grow_rows=g.rows_used, grow_rows_last=g.rows_last_harvest, grow_log_entries=g.log_entries)
+
+    def set_memo_grow(self, budget_bytes=-1, log_entries=-1):
+        """mzh_set_memo_grow: the byte budget of the memo's grown extension (-1 the default, 0 off) and the per-root
+        miss log's entries (-1 the default); takes effect with the next search"""
+        check(_lib.lib().mzh_set_memo_grow(self._h, int(budget_bytes), int(log_entries)), "mzh_set_memo_grow")
+
+    def memo_grow_table(self):
+        """debug: the grown extension as (latent [used, 64] in natural unit order, record [used, 8], link
+        [dense_rows + capacity, 6] of table rows (0: none), dense_rows); None without one.  Extension row i is
+        table row dense_rows + i."""
+        used, base, cap = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        fn = _lib.lib().mzh_memo_debug_grow
+        refs = (ctypes.byref(used), ctypes.byref(base), ctypes.byref(cap))
+        check(fn(self._h, None, None, None, *refs), "mzh_memo_debug_grow")
+        if cap.value == 0:
+            return None
+        n = cap.value
+        h, rec = self._f32(n, LATENT), self._f32(n, 8)
+        link = torch.empty((base.value + n, 6), dtype=torch.int32, device=self.device)
+        check(fn(self._h, ptr(h), ptr(rec), ptr(link), *refs), "mzh_memo_debug_grow")
+        u = used.value
+        h = h[:u].view(u, 4, 4, 4).transpose(2, 3).reshape(u, LATENT).contiguous()
+        return h, rec[:u].contiguous(), link, base.value
 
     def memo_table(self):
         """debug: copies of the built table as (latent [rows, 64] in natural unit order, record [rows, 8], depth);

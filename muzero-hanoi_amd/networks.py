@@ -189,7 +189,7 @@ def _use_device_reload(weights, reasons):
     return weights == "device" or (weights == "auto" and AUTO_DEVICE_RELOAD and not bad)
 
 
-def engine_for(net, max_sims, max_roots, device=None, weights="auto"):
+def engine_for(net, max_sims, max_roots, device=None, weights="auto", memo_grow=None):
     """The libmzh engine bound to `net` (ours or any module with MuZeroNet's state_dict keys),
     with capacity >= (max_sims, max_roots) and the network's CURRENT weights loaded.
 
@@ -199,9 +199,16 @@ def engine_for(net, max_sims, max_roots, device=None, weights="auto"):
     weights: how changed parameters reach the engine.  "host": flat_weights + Engine.load_weights (copies to
     the host, packs there, uploads).  "device": Engine.load_weights_from, the gather from the live tensors on
     the current stream; a parameter it cannot read is a ValueError.  "auto": the device path when
-    AUTO_DEVICE_RELOAD is set and every parameter is eligible, else the host path.  All give the same blob bytes."""
+    AUTO_DEVICE_RELOAD is set and every parameter is eligible, else the host path.  All give the same blob bytes.
+
+    memo_grow: the byte budget of the expansion memo's grown extension (Engine.set_memo_grow; 0 off), given to the
+    engine whenever it is not None; None leaves the engine's setting as it is."""
     if weights not in WEIGHTS_MODES:
         raise ValueError(f"weights must be one of {WEIGHTS_MODES}, got {weights!r}")
+    if memo_grow is not None:
+        eng = engine_for(net, max_sims, max_roots, device=device, weights=weights)
+        eng.set_memo_grow(memo_grow)
+        return eng
     cache = _CACHE.get(net)
     if cache is not None and "refs" in cache:
         eng = cache.get("engine")
