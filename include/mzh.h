@@ -536,6 +536,65 @@ typedef struct mzh_saliency_args {
 int mzh_saliency(mzh_engine* eng, const mzh_saliency_args* args, const mzh_multi_args* multi /* nullable */,
                  mzh_stream stream);
 
+/* Parameter gradients of the five sub-networks (monosemanticity_analysis/gradient_analysis.py get_results, lines
+ * 274-338): per row, for each of representation, dynamic, reward, policy and value (this order everywhere), the
+ * gradient of one scalar of that sub-network's output with respect to that sub-network's own parameters, in one
+ * launch (mzh_pgrad_kernel; with `multi` mzh_pgrad_multi_kernel).  With x = obs, a = one_hot(action):
+ *   representation  z0 = rep(x), h0 = normalize(z0)           objective h0.mean()
+ *   dynamic         z1 = dyn(cat(h0, a)), h1 = normalize(z1)  objective h1.mean()
+ *   reward          lr = rwd(z1) (the raw z1, networks.py:131-132); objective the transformed scalar (33 bins) or lr
+ *   policy          lp = pol(h0); objective softmax(lp).mean() where policy_logit[env] is -1 or the array is NULL
+ *                   (the reference's: mathematically constant, its gradient is autograd's rounding noise
+ *                   p_i (1/6 - sum_j p_j / 6)), else the logit policy_logit[env] (compute_saliency's objective)
+ *   value           lv = val(h0); objective the transformed scalar (33 bins) or lv
+ * Each net is Linear0 -> ReLU -> Linear2, and every weight gradient of one row is rank one, so the outputs are
+ * the factors: delta2 = d objective / d (Linear2 output) (= the b2 gradient), act = relu(Linear0(in)),
+ * delta1 = (delta2 . W2) * [act > 0] (= the b0 gradient); grad W2 = delta2 (x) act, grad W0 = delta1 (x) in with
+ * in = x, cat(h0, a), z1, h0, h0.  The seeds of representation and dynamic are normalize_h_state's backward of a
+ * constant 1/64 (min and max differentiable, lowest index on a tie), those of reward and value the softmax
+ * expectation and signed parabolic transform as autograd differentiates them (1 for a scalar head).  With `grad`
+ * a second launch on the same stream (mzh_pgrad_expand_kernel) writes row j's dense gradients in the layout of
+ * mzh_weights_size: each weight element the single fp32 product delta[i] * in[j], each bias a copy.
+ * The forward is the inference calls': h0 / pi0 / value0 are bit-identical to mzh_initial_inference, h1 / reward
+ * to mzh_recurrent_inference(h0, action).  The backward runs Linear2 transposed as fp32 MFMA products; there is
+ * no bit contract on its summation order, but a row's outputs depend on that row and its network alone: the same
+ * bits in any position, at either tile size, with or without env_index, single network or set.  Rows, env_index,
+ * `multi`, the tile table and the grid are mzh_probe_actions'; every array but env_index, grad (and multi's
+ * net_index) is indexed by env, rows outside the call are left untouched.  The first call after a weight load
+ * gathers dynamic_net.2 and rwd_net.2 transposed from the loaded blob into a buffer of the engine's (one more
+ * launch on `stream`).
+ * MZH_ERR_ARG, before any launch and before a device or an engine is needed: a NULL required pointer (args,
+ * obs, action, delta1, delta2, act, h0, z1), n < 1, B < 1 (B < n without env_index), a flag other than
+ * MZH_FLAG_COOP_TILE16 / 32 (default tile: 16 rows while n <= 4096, else 32); with multi a NULL net_index or
+ * n_networks outside [1, 256]; then a NULL engine, and n_networks above the loaded set's M.
+ * MZH_ERR_STATE: weights not loaded (without multi), no set loaded (with multi).  MZH_ERR_CAPACITY: n > max_roots.
+ * On the device: a row whose env index is outside [0, B), whose action is outside [0, 6) or whose policy_logit
+ * entry is outside [-1, 6) is skipped (its grad row too) and adds 1 to *err_count; a refused net_index writes
+ * nothing and sets multi->status[0] = 1. */
+typedef struct mzh_pgrad_args {
+  int32_t B;                   /* envs of the full batch */
+  int32_t n;                   /* rows of this call */
+  uint32_t flags;              /* MZH_FLAG_COOP_TILE16 / 32 only */
+  const int32_t* env_index;    /* [n] or NULL: row j is env env_index[j] (distinct), else env j */
+  const float* obs;            /* [B][3 n_disks], indexed by env */
+  const int32_t* action;       /* [B] 0..5, indexed by env */
+  const int32_t* policy_logit; /* [B] nullable: -1 the reference's mean(softmax), k the logit k */
+  float* delta1;               /* [B][5][256] d objective / d Linear0 output (= the b0 gradients) */
+  float* delta2;               /* [B][5][64]  d objective / d Linear2 output: 64 / 64 / S / 6 / S entries, the rest +0 */
+  float* act;                  /* [B][5][256] hidden activations after the ReLU */
+  float* h0;                   /* [B][64] normalised root latent */
+  float* z1;                   /* [B][64] raw (un-normalised) dynamics output, the reward net's input */
+  float* h1;                   /* [B][64] nullable: normalised next latent */
+  float* pi0;                  /* [B][6]  nullable: root policy */
+  float* value0;               /* [B]     nullable: root value  */
+  float* reward;               /* [B]     nullable */
+  float* objective;            /* [B][5]  nullable: the five scalars */
+  float* grad;                 /* [n][n_floats] nullable, by ROW of the call: the dense gradients */
+  int32_t* err_count;          /* nullable: += 1 per skipped row */
+} mzh_pgrad_args;
+int mzh_param_grads(mzh_engine* eng, const mzh_pgrad_args* args, const mzh_multi_args* multi /* nullable */,
+                    mzh_stream stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Reference-order host pre-draw (HOST pointers only; no device, no engine).  Replaces the NumPy
  * calls B sequential run_mcts calls make on the global legacy stream, in their order per call:

@@ -145,6 +145,15 @@ class SaliencyArgs(ctypes.Structure):
                 ("h0", _vp), ("pi0", _vp), ("value0", _vp), ("err_count", _vp)]
 
 
+class PgradArgs(ctypes.Structure):
+    """mirror of struct mzh_pgrad_args (include/mzh.h)"""
+    _fields_ = [("B", _i32), ("n", _i32), ("flags", ctypes.c_uint32),
+                ("env_index", _vp), ("obs", _vp), ("action", _vp), ("policy_logit", _vp),
+                ("delta1", _vp), ("delta2", _vp), ("act", _vp), ("h0", _vp), ("z1", _vp),
+                ("h1", _vp), ("pi0", _vp), ("value0", _vp), ("reward", _vp), ("objective", _vp), ("grad", _vp),
+                ("err_count", _vp)]
+
+
 # name -> (restype, argtypes); every symbol include/mzh.h declares
 SIGNATURES = {
     "mzh_abi_version": (ctypes.c_int, []),
@@ -178,6 +187,7 @@ SIGNATURES = {
     "mzh_search_multi": (ctypes.c_int, [_vp, ctypes.POINTER(SearchArgs), ctypes.POINTER(MultiArgs), _vp]),
     "mzh_probe_actions": (ctypes.c_int, [_vp, ctypes.POINTER(ProbeArgs), ctypes.POINTER(MultiArgs), _vp]),
     "mzh_saliency": (ctypes.c_int, [_vp, ctypes.POINTER(SaliencyArgs), ctypes.POINTER(MultiArgs), _vp]),
+    "mzh_param_grads": (ctypes.c_int, [_vp, ctypes.POINTER(PgradArgs), ctypes.POINTER(MultiArgs), _vp]),
     "mzh_search_plan_query": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int,
                                              ctypes.c_int, ctypes.POINTER(SearchPlan)]),
     "mzh_set_memo_depth": (ctypes.c_int, [_vp, ctypes.c_int]),

@@ -22,6 +22,9 @@ fused kernel launch, every env step the integer kernel).
   compute_saliency / aggregate_saliency_per_disk  monosemanticity_analysis/gradient_analysis.py:354-391 / 569-592
                        (d(policy logit at its argmax)/d(obs) and d(value)/d(obs) of one state: one mzh_saliency
                        launch; selfplay.evaluate_saliency is the batched form over states and networks)
+  gradient_get_results  monosemanticity_analysis/gradient_analysis.py:274-338, that script's get_results (the
+                       parameter gradients of the five sub-networks for one state and action: one mzh_param_grads
+                       call; selfplay.evaluate_gradients is the batched form over networks, states and actions)
 
 They run one decision at a time, exactly as the reference does (same RNG stream, same MinMaxStats
 chain); selfplay.evaluate is the batched form (sequential=True reproduces get_results, and with
@@ -40,7 +43,7 @@ from .checkpoint import ablate_networks  # noqa: F401  (acting_ablations.py:29-4
 from .hanoi_utils import hanoi_solver
 from .mcts import RecordedNetwork
 from .networks import engine_for
-from .selfplay import START_STATES
+from .selfplay import GRADIENT_NETS, START_STATES
 from .staging import Packed
 from .utils import oneHot_encoding
 
@@ -348,6 +351,32 @@ def compute_saliency(state, N, networks, action):
         raise ValueError(f"compute_saliency: a state of {len(state)} discs on a {eng.n_disks}-disc network, N={N}")
     out = eng.saliency(obs)
     return {"policy": out["policy"][0].cpu().numpy(), "value": out["value"][0].cpu().numpy()}
+
+
+def gradient_get_results(networks, state, action):
+    """gradient_analysis.py get_results (:274-338; acting.get_results is acting_ablations.py's): {"representation", "dynamic", "reward", "policy", "value"}, each the tuple of
+    four float32 tensors (Linear0 weight and bias, Linear2 weight and bias, parameters() order and shapes) the
+    reference's autograd.grad of h0.mean() / h1.mean() / reward / softmax(pi_logits).mean() / value returns for that
+    sub-network -- forward, backward and the dense expansion one mzh_param_grads call.  The tensors are on the CPU
+    and carry no graph (the reference's create_graph=True graph is never used by the script)."""
+    eng = engine_for(networks, 0, 1)
+    if len(state) != eng.n_disks or any(int(p) not in (0, 1, 2) for p in state):
+        raise ValueError(f"gradient_get_results: state {tuple(state)} on a {eng.n_disks}-disc network")
+    if int(action) != action or not 0 <= int(action) < 6:
+        raise ValueError(f"gradient_get_results: action {action} outside 0..5")
+    obs = torch.as_tensor(oneHot_encoding(state, n_integers=3), dtype=torch.float32)[None].to(eng.device)
+    act = torch.tensor([int(action)], dtype=torch.int32, device=eng.device)
+    flat = eng.param_grads(obs, act, dense=True)["grad"][0].cpu()
+    shapes = _engine.weight_shapes(eng.n_disks, eng.support)
+    data, lo = {}, 0
+    for i, name in enumerate(GRADIENT_NETS):
+        ts = []
+        for shp in shapes[4 * i: 4 * i + 4]:
+            size = int(np.prod(shp))
+            ts.append(flat[lo: lo + size].reshape(shp).clone())
+            lo += size
+        data[name] = tuple(ts)
+    return data
 
 
 def aggregate_saliency_per_disk(saliency_vector, num_disks=3, num_rods=3):

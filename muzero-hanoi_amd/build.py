@@ -17,7 +17,7 @@ REPO = os.path.dirname(HERE)
 LIB = os.path.join(HERE, "libmzh.so")
 OBJ = os.path.join(HERE, "_obj")
 SOURCES = ["mzh_api.hip", "mzh_search.hip", "mzh_wave.hip", "mzh_one.hip", "mzh_env.hip", "mzh_train.hip",
-           "mzh_replay.hip", "mzh_ingest.hip", "mzh_saliency.hip", "mzh_repack.hip"]
+           "mzh_replay.hip", "mzh_ingest.hip", "mzh_saliency.hip", "mzh_repack.hip", "mzh_pgrad.hip"]
 # host-only sources, compiled by g++: mzh_rng.cpp like the NumPy C code it restates (no -march: no FMA;
 # see csrc/mzh_rng.cpp), mzh_pack.cpp (the weight packers: copies only, no HIP) so that a plain C++
 # program can link and check it (tests/pack_check.cpp)
@@ -35,9 +35,11 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-ffp-contract=
 # it packs the interleaved policy / value chains into v_pk_fma_f32, which needs each weight pair in adjacent
 # registers and copies the rows it shares with the other chains (231 spilled VGPRs with it, none in the loop
 # without it)
-# mzh_saliency.hip runs the same cooperative MLP (mzh_mlp_initial) and is built like mzh_search.hip.
+# mzh_saliency.hip and mzh_pgrad.hip run the same cooperative MLP (mzh_mlp_initial / mzh_mlp_recurrent) and are
+# built like mzh_search.hip.
 SOURCE_FLAGS = {"mzh_search.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
-                "mzh_saliency.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "mzh_one.hip": ["-fno-slp-vectorize"]}
+                "mzh_saliency.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+                "mzh_pgrad.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "mzh_one.hip": ["-fno-slp-vectorize"]}
 
 
 BUILD_ID_MARKER = b"MZH_BUILD_ID:"

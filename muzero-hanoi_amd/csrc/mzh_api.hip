@@ -100,6 +100,16 @@ struct mzh_engine {
   MzhSalNetT tnet{};
   void* settbuf = nullptr;
   MzhSalNetT settnet{};
+  // dynamic_net.2 and rwd_net.2 transposed (MzhPackedG) for mzh_param_grads: gathered from the main blob(s) by
+  // the first such call after a load of either kind (every load clears the valid flag); workspace, not a
+  // weight buffer of the load calls (their debug counters do not count it)
+  MzhPgradMap* gmaps = nullptr;    // host: the layout and the gather's source map
+  int32_t* gmap = nullptr;         // device: the source map
+  size_t gstride = 0;              // floats of one network's buffer (rounded up to 256 bytes)
+  float* gbuf = nullptr;           // the single network's
+  float* setgbuf = nullptr;        // [setg_m] at gstride
+  int setg_m = 0;
+  bool g_valid = false, setg_valid = false;
   // floats of wbuf / tbuf / setbuf (tail included) / settbuf (mzh_weights_debug_blob)
   size_t wn = 0, tn = 0, setn = 0, settn = 0;
   // the device repack (mzh_load_weights_device / mzh_load_weight_set_device): made by the first such call, kept
@@ -249,6 +259,10 @@ extern "C" int mzh_destroy(mzh_engine* eng) {
   if (eng->set_ptab) (void)hipFree(eng->set_ptab);
   if (eng->scal2) (void)hipFree(eng->scal2);
   if (eng->scal2_host) (void)hipHostFree(eng->scal2_host);
+  if (eng->gmap) (void)hipFree(eng->gmap);
+  if (eng->gbuf) (void)hipFree(eng->gbuf);
+  if (eng->setgbuf) (void)hipFree(eng->setgbuf);
+  delete eng->gmaps;
   delete eng->maps;
   delete eng;
   return MZH_OK;
@@ -364,6 +378,7 @@ extern "C" int mzh_load_weights(mzh_engine* eng, const float* flat, size_t n_flo
 
   DeviceGuard g(eng->device);
   if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+  eng->g_valid = false;
   if (eng->wbuf) {
     ++eng->n_wait;
     HIP_OK(hipDeviceSynchronize());
@@ -441,6 +456,7 @@ extern "C" int mzh_load_weight_set(mzh_engine* eng, const float* flat, size_t n_
 
   DeviceGuard g(eng->device);
   if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+  eng->setg_valid = false;
   HIP_OK(set_release(eng));
   HIP_OK(set_workspace(eng));
   HIP_OK(hipMalloc(&eng->setbuf, ps.blob.size() * sizeof(float)));
@@ -534,6 +550,7 @@ extern "C" int mzh_load_weights_device(mzh_engine* eng, const float* const* para
   const int st = repack_ensure(eng);
   if (st) return st;
   const MzhPackMaps& mp = *eng->maps;
+  eng->g_valid = false;
   if (!eng->wbuf) {
     HIP_OK(hipMalloc(&eng->wbuf, mp.main.size() * sizeof(float)));
     ++eng->n_alloc;
@@ -576,6 +593,7 @@ extern "C" int mzh_load_weight_set_device(mzh_engine* eng, const float* const* p
   const int st = repack_ensure(eng);
   if (st) return st;
   const MzhPackMaps& mp = *eng->maps;
+  eng->setg_valid = false;
   const size_t setn = (size_t)M * eng->rstride + 2 * (size_t)M, settn = (size_t)M * eng->rtstride;
   if (eng->setbuf && eng->set_m != M) HIP_OK(set_release(eng));
   HIP_OK(set_workspace(eng));
@@ -1416,6 +1434,116 @@ extern "C" int mzh_saliency(mzh_engine* eng, const mzh_saliency_args* a, const m
     e = mzh_launch_saliency(R, eng->net, eng->tnet, p, nullptr, (hipStream_t)stream);
   }
   return e == hipSuccess ? MZH_OK : hip_fail(e, "saliency launch");
+}
+
+// the MzhPackedG buffer of the loaded network (set = false) or set, current for the loaded weights: the map once
+// per engine, the buffer once per size, the gather once per load, on `stream` ahead of the kernel that reads it
+static int pgrad_ensure(mzh_engine* eng, bool set, hipStream_t stream) {
+  if (set ? eng->setg_valid : eng->g_valid) return MZH_OK;
+  if (!eng->gmaps) {
+    MzhPgradMap* m = new MzhPgradMap();
+    if (!mzh_pgrad_map(eng->in_dim, eng->support, m)) {
+      delete m;
+      return fail(MZH_ERR_STATE, "param_grads: no gather map for this shape");
+    }
+    eng->gmaps = m;
+  }
+  const MzhPgradMap& gm = *eng->gmaps;
+  const size_t n = gm.src.size();
+  // every source lies inside one network's main blob: the gather's reads stay in bounds
+  const size_t blob = set ? eng->set_stride / sizeof(float) : eng->wn;
+  for (size_t j = 0; j < n; ++j)
+    if (gm.src[j] >= 0 && (size_t)gm.src[j] >= blob) return fail(MZH_ERR_STATE, "param_grads: gather map entry %zu out of range", j);
+  if (!eng->gmap) {
+    int32_t* d = nullptr;
+    HIP_OK(hipMalloc(&d, n * sizeof(int32_t)));
+    hipError_t e = hipMemcpy(d, gm.src.data(), n * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(d);
+      return hip_fail(e, "hipMemcpy (gather map)");
+    }
+    eng->gmap = d;
+    eng->gstride = (n + 63) & ~(size_t)63;
+  }
+  if (!set) {
+    if (!eng->gbuf) HIP_OK(hipMalloc(&eng->gbuf, eng->gstride * sizeof(float)));
+    hipError_t e = mzh_launch_pgrad_gather(eng->gmap, (int)n, static_cast<const float*>(eng->wbuf), 0, eng->gbuf, 0, 1, stream);
+    if (e != hipSuccess) return hip_fail(e, "param_grads gather launch");
+    eng->g_valid = true;
+    return MZH_OK;
+  }
+  if (eng->setgbuf && eng->setg_m != eng->set_m) {
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipFree(eng->setgbuf));
+    eng->setgbuf = nullptr;
+  }
+  if (!eng->setgbuf) {
+    HIP_OK(hipMalloc(&eng->setgbuf, (size_t)eng->set_m * eng->gstride * sizeof(float)));
+    eng->setg_m = eng->set_m;
+  }
+  hipError_t e = mzh_launch_pgrad_gather(eng->gmap, (int)n, static_cast<const float*>(eng->setbuf),
+                                         eng->set_stride / sizeof(float), eng->setgbuf, eng->gstride, eng->set_m, stream);
+  if (e != hipSuccess) return hip_fail(e, "param_grads gather launch");
+  eng->setg_valid = true;
+  return MZH_OK;
+}
+
+// Parameter gradients of the five sub-networks of a batch of rows (mzh_pgrad_kernel; with `m` the rows of a loaded
+// network set, mzh_pgrad_multi_kernel; with args.grad then mzh_pgrad_expand_kernel).  Refusals in mzh_saliency's
+// order: what the arguments alone decide first, so those need neither a device nor an engine.
+extern "C" int mzh_param_grads(mzh_engine* eng, const mzh_pgrad_args* a, const mzh_multi_args* m, mzh_stream stream) {
+  if (!a) return fail(MZH_ERR_ARG, "param_grads: args is NULL");
+  if (a->n < 1 || a->B < 1 || (!a->env_index && a->B < a->n))
+    return fail(MZH_ERR_ARG, "param_grads: bad n=%d rows for B=%d envs", a->n, a->B);
+  if (!a->obs || !a->action || !a->delta1 || !a->delta2 || !a->act || !a->h0 || !a->z1)
+    return fail(MZH_ERR_ARG, "param_grads: required buffer is NULL (obs, action, delta1, delta2, act, h0, z1)");
+  if (a->flags & ~(MZH_FLAG_COOP_TILE16 | MZH_FLAG_COOP_TILE32))
+    return fail(MZH_ERR_ARG, "param_grads: flags=0x%x, only MZH_FLAG_COOP_TILE16 / 32 apply", a->flags);
+  if (m) {
+    if (!m->net_index) return fail(MZH_ERR_ARG, "param_grads: net_index is NULL");
+    if (m->n_networks < 1 || m->n_networks > MZH_MULTI_MAX_NETS)
+      return fail(MZH_ERR_ARG, "param_grads: n_networks=%d outside [1, %d]", m->n_networks, MZH_MULTI_MAX_NETS);
+  }
+  if (!eng) return fail(MZH_ERR_ARG, "param_grads: engine NULL");
+  if (m) {
+    if (eng->set_m == 0) return fail(MZH_ERR_STATE, "no weight set loaded (mzh_load_weight_set)");
+    if (m->n_networks > eng->set_m)
+      return fail(MZH_ERR_ARG, "param_grads: n_networks=%d outside [1, %d], the loaded set", m->n_networks, eng->set_m);
+  } else if (!eng->loaded) {
+    return fail(MZH_ERR_STATE, "weights not loaded");
+  }
+  if (a->n > eng->max_roots) return fail(MZH_ERR_CAPACITY, "param_grads: n=%d > max_roots=%d", a->n, eng->max_roots);
+  DeviceGuard g(eng->device);
+  if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+  const int st = pgrad_ensure(eng, m != nullptr, (hipStream_t)stream);
+  if (st) return st;
+  MzhPgNetT gt{};
+  gt.base = reinterpret_cast<const float4*>(m ? eng->setgbuf : eng->gbuf);
+  for (int i = 0; i < MZH_G_LAYERS; ++i) gt.off[i] = (int)(eng->gmaps->layout.off[i] / 4);
+  gt.kb_rwd2 = eng->gmaps->layout.kb[MZH_G_RWD2];
+  gt.stride = eng->gstride * sizeof(float);
+  MzhPgradParams p{};
+  p.B = a->B; p.n = a->n; p.in_dim = eng->in_dim; p.kin = eng->kin;
+  p.env_index = a->env_index; p.obs = a->obs; p.action = a->action; p.policy_logit = a->policy_logit;
+  p.delta1 = a->delta1; p.delta2 = a->delta2; p.act = a->act; p.h0 = a->h0; p.z1 = a->z1; p.h1 = a->h1;
+  p.pi0 = a->pi0; p.value0 = a->value0; p.reward = a->reward; p.objective = a->objective; p.grad = a->grad;
+  p.err_count = a->err_count;
+  const int R = pick_tile(a->n, a->flags);
+  hipError_t e;
+  if (m) {
+    MzhMultiParams mp{};
+    mp.net_index = m->net_index;
+    mp.M = m->n_networks;
+    mp.tiles = eng->mtiles;
+    mp.ntiles = eng->mntiles;
+    mp.status = m->status;
+    mp.stride = eng->set_stride;
+    mp.scal = eng->set_scal;
+    e = mzh_launch_pgrad(R, eng->setnet, eng->settnet, gt, p, eng->support, &mp, (hipStream_t)stream);
+  } else {
+    e = mzh_launch_pgrad(R, eng->net, eng->tnet, gt, p, eng->support, nullptr, (hipStream_t)stream);
+  }
+  return e == hipSuccess ? MZH_OK : hip_fail(e, "param_grads launch");
 }
 
 // ---------------------------------------------------------------------------------------------

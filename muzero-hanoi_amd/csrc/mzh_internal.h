@@ -337,6 +337,43 @@ size_t mzh_saliency_smem_bytes(int R);
 hipError_t mzh_launch_saliency(int R, const MzhNet& net, const MzhSalNetT& nt, const MzhSalParams& p,
                                const MzhMultiParams* mp, hipStream_t stream);
 
+// mzh_param_grads (mzh_pgrad_kernel / mzh_pgrad_multi_kernel / mzh_pgrad_expand_kernel, mzh_pgrad.hip): rows
+// as in MzhProbeParams
+struct MzhPgNetT {  // dynamic_net.2 and rwd_net.2 transposed (MzhPackedG) of one network; a set's at `stride` bytes
+  const float4* base;
+  int off[MZH_G_LAYERS];  // float4 offsets of the layers' fragments
+  int kb_rwd2;            // k-blocks of the reward head's outputs: 3 (33 bins) or 1
+  size_t stride;
+};
+struct MzhPgradParams {
+  int B, n;
+  int in_dim, kin;
+  const int32_t* env_index;     // [n] nullable
+  const float* obs;             // [B][in_dim]
+  const int32_t* action;        // [B]
+  const int32_t* policy_logit;  // [B] nullable
+  float* delta1;                // [B][5][256]
+  float* delta2;                // [B][5][64]
+  float* act;                   // [B][5][256]
+  float* h0;                    // [B][64]
+  float* z1;                    // [B][64]
+  float* h1;                    // [B][64] nullable
+  float* pi0;                   // [B][6] nullable
+  float* value0;                // [B] nullable
+  float* reward;                // [B] nullable
+  float* objective;             // [B][5] nullable
+  float* grad;                  // [n][n_floats] nullable
+  int32_t* err_count;           // nullable
+};
+size_t mzh_pgrad_smem_bytes(int R);
+// the gather that fills a network's (M networks') MzhPackedG buffer from the main blob(s): dst[m][j] =
+// src[m][map[j]], +0 where map[j] < 0; strides in floats
+hipError_t mzh_launch_pgrad_gather(const int32_t* map, int n, const float* src, size_t src_stride, float* dst,
+                                   size_t dst_stride, int M, hipStream_t stream);
+// the factor kernel (mp as in mzh_launch_probe), then with p.grad the expansion of the call's rows
+hipError_t mzh_launch_pgrad(int R, const MzhNet& net, const MzhSalNetT& nt, const MzhPgNetT& gt, const MzhPgradParams& p,
+                            int support, const MzhMultiParams* mp, hipStream_t stream);
+
 // mzh_probe_actions (mzh_probe_kernel / mzh_probe_multi_kernel, mzh_search.hip): row j of the call is env
 // env_index[j] (or j) of a batch of B; every array but env_index (and a set's net_index) is indexed by env
 struct MzhProbeParams {

@@ -316,6 +316,51 @@ bool mzh_pack_maps(int in_dim, int support, MzhPackMaps* out) {
   return true;
 }
 
+// ---- the parameter-gradient kernel's two further transposed layers (MzhPackedG, mzh_pack.h) ----
+MzhPackedG mzh_pack_pgrad(const MzhCanon& c) {
+  static constexpr int kLayers[MZH_G_LAYERS] = {MZH_DYN2, MZH_RWD2};
+  MzhPackedG T;
+  for (int t = 0; t < MZH_G_LAYERS; ++t) {
+    const int l = kLayers[t], O = c.out[l], I = c.in[l];
+    const float* W = c.w[l];
+    T.nt[t] = (I + 15) / 16;
+    T.kb[t] = (O + 15) / 16;
+    T.off[t] = append_zeros(T.blob, (size_t)T.nt[t] * T.kb[t] * 64 * 4);
+    float* dst = T.blob.data() + T.off[t];
+    for (int nt = 0; nt < T.nt[t]; ++nt)
+      for (int kb = 0; kb < T.kb[t]; ++kb)
+        for (int lane = 0; lane < 64; ++lane)
+          for (int j = 0; j < 4; ++j) {
+            const int i = 16 * nt + (lane & 15);
+            const int o = 16 * kb + 4 * j + (lane >> 4);
+            dst[(((size_t)nt * T.kb[t] + kb) * 64 + lane) * 4 + j] = (o < O && i < I) ? W[(size_t)o * I + i] : 0.0f;
+          }
+  }
+  return T;
+}
+
+bool mzh_pgrad_map(int in_dim, int support, MzhPgradMap* out) {
+  MzhPackMaps mp;
+  if (!mzh_pack_maps(in_dim, support, &mp)) return false;
+  const size_t n = mzh_canon_view(nullptr, in_dim, support).total;
+  std::vector<int32_t> where(n, -1);  // canonical index -> the first main-blob float holding it
+  for (size_t j = 0; j < mp.main.size(); ++j)
+    if (mp.main[j] >= 0 && where[mp.main[j]] < 0) where[mp.main[j]] = (int32_t)j;
+  std::vector<float> id(n);
+  for (size_t i = 0; i < n; ++i) id[i] = (float)(i + 1);
+  MzhPackedG G = mzh_pack_pgrad(mzh_canon_view(id.data(), in_dim, support));
+  out->src.assign(G.blob.size(), -1);
+  for (size_t j = 0; j < G.blob.size(); ++j) {
+    const int32_t ci = map_entry(G.blob[j]);
+    if (ci < 0) continue;
+    if (where[ci] < 0) return false;
+    out->src[j] = where[ci];
+  }
+  G.blob.clear();
+  out->layout = G;
+  return true;
+}
+
 int32_t mzh_pack_map_encode(const MzhCanon& sizes, int64_t canon_index) {
   if (canon_index < 0) return -1;
   size_t first = 0;

@@ -102,6 +102,25 @@ bool mzh_pack_maps(int in_dim, int support, MzhPackMaps* out);
 // 2 * layer + 1 (bias) in state_dict order; -1 stays -1.  The largest tensor has 256 * 96 < 2^24 elements
 int32_t mzh_pack_map_encode(const MzhCanon& sizes, int64_t canon_index);
 
+// The two further transposed layers of the parameter-gradient kernel (mzh_pgrad.hip): dynamic_net.2 and
+// rwd_net.2 in MzhPackedT's fragment format (all 33 bins of a 33-bin reward head as tiles, KB = 3).  No load
+// packs them: the engine gathers them on the device from the main blob through `src`, which composes this
+// layout with the inverse of mzh_pack_maps' main map (every canonical element lies somewhere in the main blob).
+enum { MZH_G_DYN2, MZH_G_RWD2, MZH_G_LAYERS };
+struct MzhPackedG {
+  std::vector<float> blob;
+  size_t off[MZH_G_LAYERS];  // float offsets, each a multiple of 4
+  int nt[MZH_G_LAYERS], kb[MZH_G_LAYERS];
+};
+// the direct pack from the canonical vector (what the gather must reproduce; tests/pgrad_map_check.cpp)
+MzhPackedG mzh_pack_pgrad(const MzhCanon& c);
+struct MzhPgradMap {
+  std::vector<int32_t> src;  // entry j: the main-blob float that buffer float j copies, -1 where it is +0.0f
+  MzhPackedG layout;         // blob empty
+};
+// false (nothing written) where mzh_pack_maps refuses the shape, or an element is missing from the main blob
+bool mzh_pgrad_map(int in_dim, int support, MzhPgradMap* out);
+
 // the latency layout's LDS image `l2`: offsets in float4 units
 #define MZH_ONE_D2 0                        // dynamic_net.2 [64 k4][64 lanes]
 #define MZH_ONE_A2 (64 * 64)                // rwd_net.2 bins 0-31 (lanes 0-31) | value_net.2 bins 0-31 (lanes 32-63)

@@ -313,6 +313,63 @@ class Engine:
                                       self._stream()), "mzh_saliency")
         return out
 
+    def param_grads(self, obs, action, *, env_index=None, net_index=None, policy_logit=None, out=None, full=False,
+                    tile=None, dense=False, err=None):
+        """mzh_param_grads: for every row the parameter gradients of the five sub-networks (representation, dynamic,
+        reward, policy, value; gradient_analysis.py:274-338) as rank-one factors, in one launch.  obs [B, 3N]
+        float32 and action [B] int32 are the full batch's; row j of the call is env env_index[j] ([n] int32,
+        distinct; None: every env, n = B); every output but grad is indexed by env and rows outside the call are
+        left as they are.  policy_logit [B] int32: -1 (or None) the reference's mean(softmax) objective of the
+        policy net, k its logit k; net_index [n] int32 runs row j under network net_index[j] of the loaded weight
+        set (non-decreasing).  out: a dict of output tensors to write into (delta1 / act [B, 5, 256], delta2
+        [B, 5, 64], h0 / z1 [B, 64] float32, and with them any of h1 [B, 64], pi0 [B, 6], value0 / reward [B],
+        objective [B, 5], grad [n, n_floats]); the first five are allocated where missing, the others only with
+        full=True, grad with dense=True (row j of the CALL: the dense gradients in load_weights' flat layout).
+        tile = None | 16 | 32.  err: [1] int32, += 1 per skipped row.  Returns the dict; with net_index, "_status"
+        is the device's [2] int32 verdict as in search_multi."""
+        dev = self.device
+        B = int(obs.shape[0])
+        N = self.n_disks
+        checks = [("obs", obs, torch.float32, (B, 3 * N)), ("action", action, torch.int32, (B,))]
+        n = B
+        if env_index is not None:
+            n = int(env_index.shape[0])
+            checks.append(("env_index", env_index, torch.int32, (n,)))
+        if policy_logit is not None:
+            checks.append(("policy_logit", policy_logit, torch.int32, (B,)))
+        if net_index is not None:
+            checks.append(("net_index", net_index, torch.int32, (n,)))
+        out = dict(out) if out is not None else {}
+        required = ("delta1", "delta2", "act", "h0", "z1")
+        shapes = dict(delta1=(B, 5, HIDDEN), delta2=(B, 5, LATENT), act=(B, 5, HIDDEN), h0=(B, LATENT), z1=(B, LATENT),
+                      h1=(B, LATENT), pi0=(B, ACTIONS), value0=(B,), reward=(B,), objective=(B, 5),
+                      grad=(n, sum(int(np.prod(s)) for s in weight_shapes(N, self.support))))
+        for k, shp in shapes.items():
+            if k not in out and (k in required or (dense if k == "grad" else full)):
+                out[k] = torch.empty(shp, dtype=torch.float32, device=dev)
+            if k in out:
+                checks.append((k, out[k], torch.float32, shp))
+        for name, t, dt, shp in checks:
+            if t.dtype != dt or tuple(t.shape) != shp or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"param_grads: {name} must be a contiguous {dt} {shp} tensor on {dev}")
+        a = _lib.PgradArgs()
+        a.B, a.n, a.flags = B, n, search_flags(None, tile)
+        for k, t in (("env_index", env_index), ("obs", obs), ("action", action), ("policy_logit", policy_logit),
+                     ("err_count", err)):
+            setattr(a, k, ptr(t))
+        for k in shapes:
+            setattr(a, k, ptr(out.get(k)))
+        m = None
+        if net_index is not None:
+            if getattr(self, "set_size", 0) < 1:
+                raise RuntimeError("param_grads: no weight set loaded (load_weight_set)")
+            out["_status"] = torch.zeros(2, dtype=torch.int32, device=dev)
+            m = _lib.MultiArgs()
+            m.n_networks, m.net_index, m.status = self.set_size, ptr(net_index), ptr(out["_status"])
+        check(_lib.lib().mzh_param_grads(self._h, ctypes.byref(a), None if m is None else ctypes.byref(m),
+                                         self._stream()), "mzh_param_grads")
+        return out
+
     # ---------------------------------------------------------------- expansion memo (wave kernel)
     def set_memo_depth(self, depth):
         """mzh_set_memo_depth: -1 automatic (default), 0 off, d > 0 forced; takes effect with the next search"""

@@ -40,7 +40,7 @@ import numpy as np
 import torch
 
 from . import rng as _rng
-from .engine import hanoi_solver_batch
+from .engine import ACTIONS, LATENT, hanoi_solver_batch
 from .env import HanoiBatch
 from .mcts import RecordedNetwork, _replay_engine
 from .networks import NetworkSet, engine_for, engine_for_set
@@ -808,4 +808,78 @@ def evaluate_saliency(networks, n_disks, *, states=None, start_idx=None):
     res = {k: out[k].cpu().numpy().reshape((M, S) + tuple(out[k].shape[1:]))
            for k in ("policy", "value", "picked", "disc_policy", "disc_value")}
     res["states"] = idx
+    return res
+
+
+# ------------------------------------------------------------------------------------------------
+# parameter gradients of the five sub-networks (gradient_analysis.py get_results)
+# ------------------------------------------------------------------------------------------------
+GRADIENT_NETS = ("representation", "dynamic", "reward", "policy", "value")
+_FACTOR_KEYS = ("delta1", "delta2", "act", "h0", "z1", "h1", "pi0", "value0", "reward", "objective")
+
+
+def dense_gradients(factors, obs, action, support):
+    """The dense gradients of rank-one factors, in torch: [...][n_floats] float32 in load_weights' flat layout
+    (weight then bias of Linear0 and Linear2 of the five nets), what mzh_pgrad_expand_kernel writes -- every
+    weight element the single fp32 product delta[i] * in[j] (Linear0: delta1 (x) in with in = obs,
+    cat(h0, one_hot(action)), z1, h0, h0; Linear2: delta2 (x) act), every bias a copy.  factors: a dict with
+    delta1 / act [...][5][256], delta2 [...][5][64], h0 / z1 [...][64] (torch tensors or arrays, as
+    Engine.param_grads or evaluate_gradients return them); obs [...][3N] float32, action [...] integers."""
+    f = {k: torch.as_tensor(factors[k]) for k in ("delta1", "delta2", "act", "h0", "z1")}
+    lead = tuple(f["h0"].shape[:-1])
+    dev = f["h0"].device
+    obs = torch.as_tensor(obs).to(dev, torch.float32).reshape(lead + (-1,))
+    onehot = torch.nn.functional.one_hot(torch.as_tensor(action).to(dev, torch.int64).reshape(lead), ACTIONS).to(torch.float32)
+    ins = (obs, torch.cat([f["h0"], onehot], dim=-1), f["z1"], f["h0"], f["h0"])
+    outs = (LATENT, LATENT, int(support), ACTIONS, int(support))
+    parts = []
+    for i in range(5):
+        d1, d2 = f["delta1"][..., i, :], f["delta2"][..., i, :outs[i]]
+        parts += [(d1[..., :, None] * ins[i][..., None, :]).reshape(lead + (-1,)), d1,
+                  (d2[..., :, None] * f["act"][..., i, None, :]).reshape(lead + (-1,)), d2]
+    return torch.cat(parts, dim=-1)
+
+
+def evaluate_gradients(networks, n_disks, *, states=None, start_idx=None, actions=range(6), policy_logit=None,
+                       dense=False):
+    """gradient_analysis.py's main loop over get_results (one state, one action and one network per call) as one
+    mzh_param_grads call on a network set: every given state (states = state tuples, or start_idx = state indices;
+    default all 3^n_disks states in state_index order) x every action of `actions` under every network of the
+    list, rows network-major, then state, then action.  policy_logit: None the reference's mean(softmax) objective
+    of the policy net, an integer k its logit k for every row, or an [S][A] array.  networks: one network, a
+    sequence of networks or a networks.NetworkSet.
+    Returns numpy arrays: the factors delta1 / act [M][S][A][5][256], delta2 [M][S][A][5][64], h0 / z1 / h1
+    [M][S][A][64], pi0 [M][S][A][6], value0 / reward [M][S][A], objective [M][S][A][5], and states [S] int64,
+    actions [A] int32; with dense=True also grad [M][S][A][n_floats] (dense_gradients expands kept factors)."""
+    nset = _network_set("evaluate_gradients", networks)
+    M = len(nset)
+    if nset.in_dim != 3 * n_disks:
+        raise ValueError(f"evaluate_gradients: the networks do not read {3 * n_disks} inputs (n_disks={n_disks})")
+    if states is None and start_idx is None:
+        start_idx = np.arange(3 ** n_disks)
+    idx = _start_indices("evaluate_gradients", n_disks, states, start_idx, None, 0, 2)
+    acts = np.asarray(list(actions), np.int32)
+    if acts.ndim != 1 or acts.size < 1 or ((acts < 0) | (acts >= ACTIONS)).any():
+        raise ValueError(f"evaluate_gradients: actions must be a non-empty sequence of 0..5, got {acts.tolist()}")
+    S, A = int(idx.shape[0]), int(acts.shape[0])
+    pl = None
+    if policy_logit is not None:
+        pl = np.broadcast_to(np.asarray(policy_logit, np.int32), (S, A))
+        if ((pl < -1) | (pl >= ACTIONS)).any():
+            raise ValueError("evaluate_gradients: policy_logit outside [-1, 6)")
+    eng = engine_for_set(nset, 0, M * S * A)
+    st = np.array([index_state(int(i), n_disks) for i in idx], np.int64)  # [S][N]
+    obs1 = np.zeros((S, n_disks, 3), np.float32)
+    obs1[np.arange(S)[:, None], np.arange(n_disks)[None, :], st] = 1.0
+    obs = torch.from_numpy(np.tile(np.repeat(obs1.reshape(S, 3 * n_disks), A, axis=0), (M, 1))).to(eng.device)
+    action = torch.from_numpy(np.tile(acts, M * S)).to(eng.device)
+    net_index = torch.from_numpy(np.repeat(np.arange(M, dtype=np.int32), S * A)).to(eng.device)
+    plt = None if pl is None else torch.from_numpy(np.tile(pl.reshape(-1), M)).to(eng.device)
+    out = eng.param_grads(obs, action, net_index=net_index, policy_logit=plt, full=True, dense=dense)
+    if int(out["_status"][0].item()) != 0:
+        raise RuntimeError("evaluate_gradients: the device refused net_index")
+    res = {k: out[k].cpu().numpy().reshape((M, S, A) + tuple(out[k].shape[1:]))
+           for k in _FACTOR_KEYS + (("grad",) if dense else ())}
+    res["states"] = idx
+    res["actions"] = acts
     return res
