@@ -754,6 +754,62 @@ typedef struct mzh_ingest_args {
 
 int mzh_episode_ingest(const mzh_ingest_args* args, mzh_stream stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Whole self-play episodes in one launch on the latency kernel (the episode form of mzh_search_one_kernel, mzh_one.hip: 512
+ * threads, min(B, 256) workgroups, a workgroup plays env blockIdx.x, blockIdx.x + gridDim.x, ...).  Env b
+ * starts from state[b] with step_counter 0 and plays moves t = 0, 1, ... until it is done (the goal, or
+ * max_steps moves; Muzero._play_game's loop, Muzero.py:153-186).  Move t of env b:
+ *   obs     oneHot_encoding(c_state) (utils.py:9-25), the float32 values of mzh_encode_obs;
+ *   search  one MCTS.run_mcts (mcts.py:34-126) from it, as mzh_search runs it on the latency kernel, with the
+ *           inputs of row t * B + b of noise / tie_idx / action_u and the agent's MinMaxStats: minmax_in[b]
+ *           (fresh where NULL) at t = 0, then carried from search to search on the device as a caller would
+ *           pass minmax_out on as minmax_in; pi, root_q, action (visits, obs) of row t * B + b are written;
+ *   step    one TowersOfHanoi.step (env/hanoi.py:47-84) on the chosen action, as mzh_env_step: its reward
+ *           code goes to reward[t * B + b].
+ * Rows t >= steps[b] of every [T][B] array are neither read nor written.  At an episode's end steps[b] (moves
+ * played), illegal[b] (illegal moves among them), solved[b] (1: a step returned reward 100), final_state[b]
+ * (c_state: not advanced by the goal step, hanoi.py:65-69) and minmax_out[b] are written.
+ * T >= max_steps is required, so every env ends inside the tables.  A start state with a peg outside 0..2 is
+ * refused on the device: that env plays nothing (steps = illegal = solved = 0, final_state = state, minmax_out
+ * = minmax_in or fresh) and *err_count += 1.
+ * Refused before any launch -- MZH_ERR_ARG: args NULL, a NULL required pointer (state, tie_idx, pi, root_q,
+ * action, reward, steps, illegal, solved, final_state, minmax_out; action_u unless deterministic), B < 1,
+ * n_sims < 0, max_steps < 1, T < max_steps, T * B rows beyond int32, goal_peg outside 0..2, a flag other than
+ * MZH_FLAG_NP1_UCB, engine NULL; MZH_ERR_TEMPERATURE as mzh_search; MZH_ERR_CAPACITY: B > max_roots, n_sims >
+ * max_sims, or n_sims beyond the latency kernel's LDS (the MZH_FLAG_KERNEL_ONE rule); MZH_ERR_STATE: weights
+ * not loaded.  The checks that need no engine come first.  Weight sets and replay have no episode form.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct mzh_episode_args {
+  int32_t B;             /* envs */
+  int32_t T;             /* rows (moves) of the [T][B] tables, >= max_steps */
+  int32_t n_sims;        /* n_simulations (mcts.py:30) */
+  int32_t goal_peg;      /* TowersOfHanoi(N, max_steps): N is the engine's n_disks */
+  int32_t max_steps;
+  int32_t deterministic; /* as mzh_search_args */
+  uint32_t flags;        /* 0 or MZH_FLAG_NP1_UCB */
+  double discount, eps, temperature; /* as mzh_search_args */
+  const uint8_t* state;     /* [B][n_disks] start states (peg of disc d) */
+  const double* noise;      /* [T][B][6] Dirichlet draws, NULL = no noise */
+  const int32_t* tie_idx;   /* [T][B] */
+  const double* action_u;   /* [T][B]; NULL if deterministic */
+  const double* minmax_in;  /* [B][2] (maximum, minimum) or NULL (fresh) */
+  const double* pow_table;  /* as mzh_search_args (nullable) */
+  double* pi;           /* [T][B][6] */
+  double* root_q;       /* [T][B] */
+  int32_t* action;      /* [T][B] */
+  int8_t* reward;       /* [T][B] codes of mzh_env_step */
+  int32_t* visits;      /* [T][B][6] nullable */
+  float* obs;           /* [T][B][3 n_disks] nullable: the observation searched */
+  int32_t* steps;       /* [B] */
+  int32_t* illegal;     /* [B] */
+  uint8_t* solved;      /* [B] */
+  uint8_t* final_state; /* [B][n_disks] */
+  double* minmax_out;   /* [B][2] */
+  int32_t* err_count;   /* nullable device int32 accumulator */
+} mzh_episode_args;
+
+int mzh_play_episodes(mzh_engine* eng, const mzh_episode_args* args, mzh_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -113,6 +113,17 @@ class IngestArgs(ctypes.Structure):
                 ("pi_probs", _vp), ("returns", _vp), ("prio", _vp), ("first", _vp), ("status", _vp)]
 
 
+class EpisodeArgs(ctypes.Structure):
+    """mirror of struct mzh_episode_args (include/mzh.h)"""
+    _fields_ = [("B", _i32), ("T", _i32), ("n_sims", _i32), ("goal_peg", _i32), ("max_steps", _i32),
+                ("deterministic", _i32), ("flags", ctypes.c_uint32),
+                ("discount", ctypes.c_double), ("eps", ctypes.c_double), ("temperature", ctypes.c_double),
+                ("state", _vp), ("noise", _vp), ("tie_idx", _vp), ("action_u", _vp), ("minmax_in", _vp),
+                ("pow_table", _vp), ("pi", _vp), ("root_q", _vp), ("action", _vp), ("reward", _vp), ("visits", _vp),
+                ("obs", _vp), ("steps", _vp), ("illegal", _vp), ("solved", _vp), ("final_state", _vp),
+                ("minmax_out", _vp), ("err_count", _vp)]
+
+
 class PlanArgs(ctypes.Structure):
     """mirror of struct mzh_plan_args (include/mzh.h)"""
     _fields_ = [("n_disks", _i32), ("goal_peg", _i32), ("max_steps", _i32), ("B", _i32), ("n", _i32),
@@ -206,6 +217,7 @@ SIGNATURES = {
     "mzh_replay_sample": (ctypes.c_int, [ctypes.POINTER(ReplayArgs), _vp]),
     "mzh_replay_set_priorities": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, ctypes.c_int, _vp, _vp]),
     "mzh_episode_ingest": (ctypes.c_int, [ctypes.POINTER(IngestArgs), _vp]),
+    "mzh_play_episodes": (ctypes.c_int, [_vp, ctypes.POINTER(EpisodeArgs), _vp]),
 }
 
 _lib = None

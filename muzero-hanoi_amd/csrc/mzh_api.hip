@@ -1720,3 +1720,45 @@ extern "C" int mzh_episode_ingest(const mzh_ingest_args* a, mzh_stream stream) {
   hipError_t e = mzi_launch_ingest(*a, (hipStream_t)stream);
   return e == hipSuccess ? MZH_OK : hip_fail(e, "episode ingest launch");
 }
+
+// Whole episodes in one launch on the latency kernel (mzh.h).  The checks that need no engine come first.
+extern "C" int mzh_play_episodes(mzh_engine* eng, const mzh_episode_args* a, mzh_stream stream) {
+  if (!a) return fail(MZH_ERR_ARG, "play_episodes: args is NULL");
+  if (a->B < 1 || a->n_sims < 0) return fail(MZH_ERR_ARG, "play_episodes: B=%d n_sims=%d", a->B, a->n_sims);
+  if (a->goal_peg < 0 || a->goal_peg > 2) return fail(MZH_ERR_ARG, "play_episodes: goal_peg=%d outside 0..2", a->goal_peg);
+  if (a->max_steps < 1 || a->T < a->max_steps)
+    return fail(MZH_ERR_ARG, "play_episodes: T=%d rows cannot hold max_steps=%d moves (T >= max_steps >= 1)", a->T,
+                a->max_steps);
+  if ((int64_t)a->T * a->B > 0x7fffffff)
+    return fail(MZH_ERR_ARG, "play_episodes: T=%d x B=%d rows exceed int32", a->T, a->B);
+  if (a->flags & ~MZH_FLAG_NP1_UCB)
+    return fail(MZH_ERR_ARG, "play_episodes: flags=0x%x (only MZH_FLAG_NP1_UCB applies)", a->flags);
+  if (!(a->temperature >= 0.0 && a->temperature <= 1.0))
+    return fail(MZH_ERR_TEMPERATURE, "Expect `temperature` to be in the range [0.0, 1.0], got %g", a->temperature);
+  if (!a->state || !a->tie_idx || !a->pi || !a->root_q || !a->action || !a->reward || !a->steps || !a->illegal ||
+      !a->solved || !a->final_state || !a->minmax_out)
+    return fail(MZH_ERR_ARG, "play_episodes: required buffer is NULL");
+  if (!a->deterministic && !a->action_u) return fail(MZH_ERR_ARG, "play_episodes: stochastic action selection needs action_u");
+  if (!eng) return fail(MZH_ERR_ARG, "play_episodes: engine is NULL");
+  if (a->B > eng->max_roots) return fail(MZH_ERR_CAPACITY, "play_episodes: B=%d > max_roots=%d", a->B, eng->max_roots);
+  if (a->n_sims > eng->max_sims) return fail(MZH_ERR_CAPACITY, "play_episodes: n_sims=%d > max_sims=%d", a->n_sims, eng->max_sims);
+  MzhSearchPlan pl;  // the latency kernel's plan: its grid, the latents in LDS where they fit, or its capacity error
+  const int st = make_plan(a->B, a->n_sims, MZH_FLAG_KERNEL_ONE, false, eng->support, true, &pl);
+  if (st) return st;
+  if (!eng->loaded) return fail(MZH_ERR_STATE, "weights not loaded");
+  DeviceGuard g(eng->device);
+  if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+  MzhSearchParams p{};
+  p.B = a->B; p.S = a->n_sims; p.E = eng->E; p.in_dim = eng->in_dim; p.kin = eng->kin;
+  p.deterministic = a->deterministic; p.np1 = (a->flags & MZH_FLAG_NP1_UCB) ? 1 : 0;
+  p.discount = a->discount; p.eps = a->eps; p.temperature = a->temperature;
+  p.noise = a->noise; p.tie_idx = a->tie_idx; p.action_u = a->action_u; p.minmax_in = a->minmax_in;
+  p.htree = eng->htree; p.table = eng->table;
+  p.visits = a->visits; p.root_q = a->root_q; p.action = a->action; p.pi = a->pi; p.pow_table = a->pow_table;
+  MzhEpisodeParams ep{};
+  ep.T = a->T; ep.n_disks = eng->n_disks; ep.goal_peg = a->goal_peg; ep.max_steps = a->max_steps;
+  ep.start = a->state; ep.obs = a->obs; ep.reward = a->reward; ep.steps = a->steps; ep.illegal = a->illegal;
+  ep.solved = a->solved; ep.final_state = a->final_state; ep.minmax_out = a->minmax_out; ep.err_count = a->err_count;
+  hipError_t e = mzh_launch_episodes(pl, eng->net, eng->onet, p, ep, (hipStream_t)stream);
+  return e == hipSuccess ? MZH_OK : hip_fail(e, "play_episodes launch");
+}

@@ -28,3 +28,48 @@ __device__ __forceinline__ uint8_t mzh_legal_mask_row(const uint8_t* src, int n)
   }
   return (uint8_t)((t0 < t1) | (t0 < t2) << 1 | (t1 < t0) << 2 | (t1 < t2) << 3 | (t2 < t0) << 4 | (t2 < t1) << 5);
 }
+
+// the moves' pegs; one copy per translation unit (mzh_env.hip's kernels, the episode kernel of mzh_one.hip)
+__attribute__((unused)) static __constant__ int8_t kMoveFrom[6] = {0, 0, 1, 1, 2, 2};  // permutations(range(3), 2),
+__attribute__((unused)) static __constant__ int8_t kMoveTo[6] = {1, 2, 0, 2, 0, 1};   // env/hanoi.py:39-41
+
+// One TowersOfHanoi.step (hanoi.py:47-84) of an active env for a move a in 0..5.  st (in: c_state, out: the
+// moved state the returned observation encodes) and top (of c_state) are the lane's registers; c_state is the
+// env's row of `state` and active its reset_check byte, stored to where the reference assigns them; ctr
+// (step_counter) is the caller's to load and store.  Returns the reward code (0 -> 0, 1 -> 100,
+// -1 -> -100/1000) and sets dn / ill; advanced tells whether c_state moved (not on an illegal move, and not
+// on the goal step, hanoi.py:65-69).
+__device__ __forceinline__ int8_t env_transition(int n, int goal_peg, int max_steps, int a, uint8_t* st,
+                                                 const int top[3], uint8_t* c_state, uint8_t* active, int& ctr,
+                                                 uint8_t& dn, uint8_t& ill, bool& advanced) {
+  const int f = kMoveFrom[a], t = kMoveTo[a];
+  int8_t code;
+  dn = 0;
+  advanced = false;
+  ill = !(top[f] < top[t]);
+  ctr += 1;  // hanoi.py:61
+  if (!ill) {
+    const int disc = top[f];  // smallest disc on the from-peg (hanoi.py:148-150)
+    st[disc] = (uint8_t)t;
+    bool goal = true;
+    for (int d = 0; d < n; ++d) goal = goal && (st[d] == goal_peg);
+    if (!goal) {
+      code = 0;
+      c_state[disc] = (uint8_t)t;  // c_state = moved_state
+      advanced = true;
+    } else {
+      code = 1;  // rwd 100, done, reset_check False, counter 0; c_state NOT advanced (hanoi.py:65-69)
+      dn = 1;
+      *active = 0;
+      ctr = 0;
+    }
+  } else {
+    code = -1;  // rwd -100/1000, state unchanged (hanoi.py:70-74)
+  }
+  if (ctr == max_steps) {  // hanoi.py:77-80
+    dn = 1;
+    *active = 0;
+    ctr = 0;
+  }
+  return code;
+}

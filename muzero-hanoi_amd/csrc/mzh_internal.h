@@ -398,6 +398,22 @@ size_t mzh_probe_smem_bytes(int R);
 // mzh_probe_multi_kernel<R> on mzh_multi_max_tiles(n, R, mp->M) workgroups (net: the set's network 0)
 hipError_t mzh_launch_probe(int R, const MzhNet& net, const MzhProbeParams& p, const MzhMultiParams* mp, hipStream_t stream);
 
+// the env side of mzh_play_episodes (the episode form of mzh_search_one_kernel, mzh_one.hip); the search side is a MzhSearchParams
+// whose per-search arrays have T * B rows (row t * B + b: move t of env b) and whose minmax_in is per env
+struct MzhEpisodeParams {
+  int T, n_disks, goal_peg, max_steps;
+  const uint8_t* start;  // [B][n_disks]
+  float* obs;            // [T][B][3 n_disks] nullable
+  int8_t* reward;        // [T][B]
+  int32_t* steps;        // [B]
+  int32_t* illegal;      // [B]
+  uint8_t* solved;       // [B]
+  uint8_t* final_state;  // [B][n_disks]
+  double* minmax_out;    // [B][2]
+  int32_t* err_count;    // nullable
+};
+hipError_t mzh_launch_episodes(const MzhSearchPlan& pl, const MzhNet& net, const MzhOneNet& on, const MzhSearchParams& p,
+                               const MzhEpisodeParams& ep, hipStream_t stream);
 size_t mzh_one_smem_bytes(int S, bool latl);
 hipError_t mzh_launch_one(const MzhSearchPlan& pl, const MzhNet& net, const MzhOneNet& on, const MzhSearchParams& p,
                           hipStream_t stream);

@@ -84,6 +84,47 @@ __device__ __forceinline__ double mzh_root_prior(float pr, bool noised, double e
   return (double)scaled + eps * noise;
 }
 
+// generate_play_policy (mcts.py:154-176) and the action draw (mcts.py:115-122) of one root from its visit
+// counts, by one lane: writes pi where given and returns the action (the episode kernel steps its env with it)
+__device__ __forceinline__ int mzh_play_policy(const MzhSearchParams& p, const int root, const int (&vis)[MZH_A]) {
+  double v[MZH_A];
+  for (int a = 0; a < MZH_A; ++a) v[a] = (double)vis[a];
+  if (p.temperature > 0.0) {
+    double ex = 1.0 / p.temperature;
+    ex = ex < 5.0 ? ex : 5.0;  // max(1.0, min(5.0, 1/T))
+    ex = ex > 1.0 ? ex : 1.0;
+    for (int a = 0; a < MZH_A; ++a) v[a] = mzh_pow(v[a], vis[a], ex, p.pow_table);
+  }
+  double sum = 0.0;
+  for (int a = 0; a < MZH_A; ++a) sum = sum + v[a];
+  double pi[MZH_A];
+  for (int a = 0; a < MZH_A; ++a) pi[a] = v[a] / sum;
+  if (p.pi)
+    for (int a = 0; a < MZH_A; ++a) p.pi[(size_t)root * MZH_A + a] = pi[a];
+  int act = 0;
+  if (p.deterministic || !p.action_u) {
+    for (int a = 1; a < MZH_A; ++a)
+      if (vis[a] > vis[act]) act = a;
+  } else {
+    double cdf[MZH_A];
+    double acc = 0.0;
+    for (int a = 0; a < MZH_A; ++a) {
+      acc = acc + pi[a];
+      cdf[a] = acc;
+    }
+    const double last = cdf[MZH_A - 1];
+    const double u = p.action_u[root];
+    act = MZH_A - 1;
+    for (int a = 0; a < MZH_A; ++a) {
+      if (cdf[a] / last > u) {
+        act = a;
+        break;
+      }
+    }
+  }
+  return act;
+}
+
 // The results of one root (mcts.py:111-126, generate_play_policy mcts.py:154-176), written by one lane:
 // visits, root Q, MinMaxStats bounds, the tie and step counters, the last simulation's action path
 // (path_at(j) = path entry j of that selection, its low 3 bits the child), pi and the action.
@@ -107,41 +148,7 @@ __device__ __forceinline__ void mzh_write_results(const MzhSearchParams& p, cons
   }
   if (p.latent_len) p.latent_len[root] = p.S > 0 ? depth : 0;
   if (p.pi || p.action) {
-    double v[MZH_A];
-    for (int a = 0; a < MZH_A; ++a) v[a] = (double)vis[a];
-    if (p.temperature > 0.0) {
-      double ex = 1.0 / p.temperature;
-      ex = ex < 5.0 ? ex : 5.0;  // max(1.0, min(5.0, 1/T))
-      ex = ex > 1.0 ? ex : 1.0;
-      for (int a = 0; a < MZH_A; ++a) v[a] = mzh_pow(v[a], vis[a], ex, p.pow_table);
-    }
-    double sum = 0.0;
-    for (int a = 0; a < MZH_A; ++a) sum = sum + v[a];
-    double pi[MZH_A];
-    for (int a = 0; a < MZH_A; ++a) pi[a] = v[a] / sum;
-    if (p.pi)
-      for (int a = 0; a < MZH_A; ++a) p.pi[(size_t)root * MZH_A + a] = pi[a];
-    int act = 0;
-    if (p.deterministic || !p.action_u) {
-      for (int a = 1; a < MZH_A; ++a)
-        if (vis[a] > vis[act]) act = a;
-    } else {
-      double cdf[MZH_A];
-      double acc = 0.0;
-      for (int a = 0; a < MZH_A; ++a) {
-        acc = acc + pi[a];
-        cdf[a] = acc;
-      }
-      const double last = cdf[MZH_A - 1];
-      const double u = p.action_u[root];
-      act = MZH_A - 1;
-      for (int a = 0; a < MZH_A; ++a) {
-        if (cdf[a] / last > u) {
-          act = a;
-          break;
-        }
-      }
-    }
+    const int act = mzh_play_policy(p, root, vis);
     if (p.action) p.action[root] = act;
   }
 }

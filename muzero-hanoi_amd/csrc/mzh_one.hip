@@ -22,6 +22,7 @@
 //   rwd2 / val2 bins 0-31 (wave 0), pol2 (wave 1), bin-32 chains (wave 2) |
 //   heads + backup + the next selection + the parent-latent gather (wave 0; the root's 8-lane group)
 #include "mzh_device.h"
+#include "mzh_env_kernels.h"
 #include "mzh_internal.h"
 #include "mzh_tree.h"
 
@@ -41,7 +42,7 @@ struct MzhOneSmem {
   float hidRQ[272], hidVQ[272];         // reward / value hidden for bin 32's chains (Q)
   float lrwd[40], lval[40], lpol[16];   // logits (natural order)
   int act;                              // the leaf's action (one-hot column of the next dyn0)
-  int pad[3];
+  int pad[3];                           // the episode kernel's env: reset_check, step_counter, 2 * illegal moves + solved
   MzhRootBlk root;                      // the root's 6 children (slots 6, 7 padding)
   MzhRootReg rsv;                       // the root's search state between tree phases (not live in registers
                                         // across the MLP: every register there holds weights or chain operands)
@@ -510,9 +511,21 @@ __device__ __forceinline__ int one_fresh(int v) {
   return v;
 }
 
-// LATL: the latents in LDS (when the launcher finds room; otherwise in the engine's HBM workspace)
-template <bool SUP33, bool MMIN, bool LATL>
-__global__ __launch_bounds__(512, 2) void mzh_search_one_kernel(MzhNet net, MzhOneNet on, MzhSearchParams p) {
+// the episode form's fourth kernel argument
+__device__ __forceinline__ const MzhEpisodeParams& one_ep(const MzhEpisodeParams& e) { return e; }
+
+// LATL: the latents in LDS (when the launcher finds room; otherwise in the engine's HBM workspace).
+// EPA: empty, the search form mzh_search_one_kernel<SUP33, MMIN, LATL>(net, on, p): root r of p, one search.
+// EPA = MzhEpisodeParams, the episode form (mzh_play_episodes; a fourth kernel argument, so the search form's
+// own arguments and code stay what they are): env r of p plays its episode -- move mv searches from the env's own
+// state with the inputs and outputs of p at row mv * B + r, then lane 0 of wave 0 takes one TowersOfHanoi.step on
+// the chosen action, until the env is done.  Between the steps c_state lives one-hot in sm.obs, reset_check /
+// step_counter / the tallies in sm.pad, the MinMaxStats in sm.rsv; "done" is sm.pad[0], written by that one lane
+// before the move's last barrier and read by every thread after it.  Always launched with MMIN: from its second
+// move on an agent's MinMaxStats are carried bounds, as a caller's minmax_in are.
+template <bool SUP33, bool MMIN, bool LATL, class... EPA>
+__global__ __launch_bounds__(512, 2) void mzh_search_one_kernel(MzhNet net, MzhOneNet on, MzhSearchParams p, EPA... epa) {
+  constexpr bool EP = sizeof...(EPA) != 0;
   extern __shared__ __align__(128) unsigned char smem_raw[];
   MzhOneSmem& sm = *reinterpret_cast<MzhOneSmem*>(smem_raw);
   float4* l2 = reinterpret_cast<float4*>(smem_raw + kSmBytes);
@@ -565,13 +578,42 @@ __global__ __launch_bounds__(512, 2) void mzh_search_one_kernel(MzhNet net, MzhO
   __syncthreads();
 
   for (int r = blockIdx.x; r < p.B; r += gridDim.x) {
+    if constexpr (EP) {  // env r: oneHot_encoding(c_state) (utils.py:9-25) of its start; a peg outside 0..2 skips it
+      const MzhEpisodeParams& ep = one_ep(epa...);
+      if (wave == 0) {
+        const int lane = one_fresh(t) & 63, d = lane / 3;
+        const int peg = lane < p.in_dim ? ep.start[(size_t)r * ep.n_disks + d] : 0;
+        sm.obs[lane] = (lane < p.in_dim && peg == lane - 3 * d) ? 1.0f : 0.0f;
+        const bool bad = __ballot(peg > 2) != 0;
+        if (lane == 0) {
+          sm.pad[0] = bad ? 0 : 1;
+          sm.pad[1] = 0;
+          sm.pad[2] = 0;
+        }
+      }
+      __syncthreads();
+    }
+    int mv = 0;  // EP: the env's moves so far
+    // EP: one trip per move; the search form: one trip and no back edge (`while (false)`).  The body keeps the
+    // search form's indentation and text on purpose: that form must compile to the instructions it had before the
+    // episode form existed ("Sharing the body").
+    do {
     // this root's latents [E][64] in the engine's workspace: lane j stores and re-reads element j
     const __amdgpu_buffer_rsrc_t lres = mzh_rsrc(p.htree + (size_t)r * p.E * MZH_H);
     const int tr = one_fresh(t), lane = tr & 63, n = tr & 255, c = lane & 7;
     const bool grp = wave == 0 && lane < 8;  // the root's 8-lane group (tree phases)
     MzhOneTree tree{p, sm.root, tb, path, pc, pcv, table, inv, lane, disc, noised};
+    const size_t ri = EP ? (size_t)mv * p.B + r : (size_t)r;  // the row of p's per-search arrays
+    if constexpr (EP) {
+      if (sm.pad[0] == 0) break;  // uniform: written before the last barrier
+    }
     // ---------------- root: initial_inference (mcts.py:49-50, networks.py:71-94) ----------------
-    if (t < 64) sm.obs[lane] = lane < p.in_dim ? p.obs[(size_t)r * p.in_dim + lane] : 0.0f;
+    if constexpr (EP) {
+      const MzhEpisodeParams& ep = one_ep(epa...);
+      if (t < p.in_dim && ep.obs) ep.obs[ri * p.in_dim + t] = sm.obs[t];
+    } else {
+      if (t < 64) sm.obs[lane] = lane < p.in_dim ? p.obs[(size_t)r * p.in_dim + lane] : 0.0f;
+    }
     // representation_net.2 into the dynamic_net.2 region (reloaded below, before the first simulation)
 #pragma unroll
     for (int i = 0; i < 8; ++i)
@@ -640,10 +682,13 @@ __global__ __launch_bounds__(512, 2) void mzh_search_one_kernel(MzhNet net, MzhO
       rb.R[c] = 0.0f;
       rb.W[c] = 0.0;
       const bool mix = noised && c < MZH_A;
-      rb.P64[c] = mzh_root_prior(pr, mix, p.eps, mix ? p.noise[(size_t)r * MZH_A + c] : 0.0);
+      rb.P64[c] = mzh_root_prior(pr, mix, p.eps, mix ? p.noise[ri * MZH_A + c] : 0.0);
       MzhRootReg rs;
       double mx = -__builtin_inf(), mn = __builtin_inf();
-      if (p.minmax_in) {
+      if (EP && mv > 0) {  // the agent's MinMaxStats, carried from its last search (as minmax_out -> minmax_in)
+        mx = sm.rsv.mm.mmax;
+        mn = sm.rsv.mm.mmin;
+      } else if (p.minmax_in) {
         mx = p.minmax_in[2 * r];
         mn = p.minmax_in[2 * r + 1];
       }
@@ -652,7 +697,7 @@ __global__ __launch_bounds__(512, 2) void mzh_search_one_kernel(MzhNet net, MzhO
       rs.rootN = 0;
       rs.firstTie = 0;
       rs.extra = 0;
-      rs.tie = p.tie_idx ? p.tie_idx[r] : 0;
+      rs.tie = p.tie_idx ? p.tie_idx[ri] : 0;
       rs.steps = 0;
       rs.depth = 0;
       rs.leafE = 0;
@@ -780,10 +825,75 @@ __global__ __launch_bounds__(512, 2) void mzh_search_one_kernel(MzhNet net, MzhO
     // ---------------- results (mcts.py:111-126, 154-176) ----------------
     if (wave == 0 && lane == 0) {
       const MzhRootReg rs = sm.rsv;
-      tree.results(r, rs);
-      if (p.lockstep_levels) p.lockstep_levels[r] = lsum;
+      if constexpr (EP) {
+        // the record's row (mzh_write_results' visits, root Q, pi and action), then the env's step on that action
+        const MzhEpisodeParams& ep = one_ep(epa...);
+        int vis[MZH_A];
+        for (int a = 0; a < MZH_A; ++a) vis[a] = sm.root.N[a];
+        if (p.visits)
+          for (int a = 0; a < MZH_A; ++a) p.visits[ri * MZH_A + a] = vis[a];
+        p.root_q[ri] = rs.rootN == 0 ? 0.0 : rs.rootW / (double)rs.rootN;
+        const int act = mzh_play_policy(p, (int)ri, vis);
+        p.action[ri] = act;
+        // c_state, the moved state and the tops as bytes / ints in the (now dead) reward logits
+        uint8_t* cs = reinterpret_cast<uint8_t*>(sm.lrwd);
+        uint8_t* st = cs + 32;
+        int* top = reinterpret_cast<int*>(cs + 64);
+        const int nd = ep.n_disks;
+        top[0] = top[1] = top[2] = nd;
+        for (int d = nd - 1; d >= 0; --d) {
+          const int peg = sm.obs[3 * d + 1] != 0.0f ? 1 : sm.obs[3 * d + 2] != 0.0f ? 2 : 0;
+          cs[d] = st[d] = (uint8_t)peg;
+          top[peg] = d;
+        }
+        int ctr = sm.pad[1];
+        uint8_t dn, ill;
+        bool advanced;
+        const int8_t code = env_transition(nd, ep.goal_peg, ep.max_steps, act, st, top, cs,
+                                           reinterpret_cast<uint8_t*>(&sm.pad[0]), ctr, dn, ill, advanced);
+        sm.pad[1] = ctr;
+        sm.pad[2] += 2 * ill + (code == 1 ? 1 : 0);
+        ep.reward[ri] = code;
+        if (advanced)
+          for (int d = 0; d < nd; ++d)
+            for (int k = 0; k < 3; ++k) sm.obs[3 * d + k] = cs[d] == k ? 1.0f : 0.0f;
+      } else {
+        tree.results(r, rs);
+        if (p.lockstep_levels) p.lockstep_levels[r] = lsum;
+      }
     }
     __syncthreads();  // the next root reuses the LDS tree and activations
+    if constexpr (EP) {
+      if (++mv >= one_ep(epa...).T) break;
+    }
+    } while (EP);
+    if constexpr (EP) {  // the episode's end (mv moves; 0: a refused start state, nothing played)
+      const MzhEpisodeParams& ep = one_ep(epa...);
+      if (wave == 0) {
+        const int lane = one_fresh(t) & 63;
+        if (lane < ep.n_disks)
+          ep.final_state[(size_t)r * ep.n_disks + lane] =
+              mv == 0 ? ep.start[(size_t)r * ep.n_disks + lane]
+                      : (uint8_t)(sm.obs[3 * lane + 1] != 0.0f ? 1 : sm.obs[3 * lane + 2] != 0.0f ? 2 : 0);
+        if (lane == 0) {
+          double mx = -__builtin_inf(), mn = __builtin_inf();
+          if (mv > 0) {
+            mx = sm.rsv.mm.mmax;
+            mn = sm.rsv.mm.mmin;
+          } else if (p.minmax_in) {
+            mx = p.minmax_in[2 * r];
+            mn = p.minmax_in[2 * r + 1];
+          }
+          ep.minmax_out[2 * r] = mx;
+          ep.minmax_out[2 * r + 1] = mn;
+          ep.steps[r] = mv;
+          ep.illegal[r] = mv == 0 ? 0 : sm.pad[2] >> 1;
+          ep.solved[r] = mv == 0 ? 0 : (uint8_t)(sm.pad[2] & 1);
+          if (mv == 0 && ep.err_count) atomicAdd(ep.err_count, 1);
+        }
+      }
+      __syncthreads();  // the next env rewrites sm.obs and sm.pad
+    }
   }
 }
 
@@ -810,6 +920,28 @@ hipError_t mzh_launch_one(const MzhSearchPlan& pl, const MzhNet& net, const MzhO
                           hipStream_t stream) {
   if (pl.sup33) return pl.mmin ? launch_one_l<true, true>(pl, net, on, p, stream) : launch_one_l<true, false>(pl, net, on, p, stream);
   return pl.mmin ? launch_one_l<false, true>(pl, net, on, p, stream) : launch_one_l<false, false>(pl, net, on, p, stream);
+}
+
+template <bool SUP33, bool LATL>
+static hipError_t launch_episode_t(const MzhNet& net, const MzhOneNet& on, const MzhSearchParams& p,
+                                   const MzhEpisodeParams& ep, int grid, hipStream_t stream) {
+  const size_t smem = mzh_one_smem_bytes(p.S, LATL);
+  const void* fn = reinterpret_cast<const void*>(&mzh_search_one_kernel<SUP33, true, LATL, MzhEpisodeParams>);
+  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((mzh_search_one_kernel<SUP33, true, LATL, MzhEpisodeParams>), dim3(grid), dim3(kThreads), smem,
+                     stream, net, on, p, ep);
+  return hipGetLastError();
+}
+
+// the episode form of the plan's kernel (a latency-kernel plan: pl.one; its grid, sup33 and ohl)
+hipError_t mzh_launch_episodes(const MzhSearchPlan& pl, const MzhNet& net, const MzhOneNet& on, const MzhSearchParams& p,
+                               const MzhEpisodeParams& ep, hipStream_t stream) {
+  if (pl.sup33)
+    return pl.ohl ? launch_episode_t<true, true>(net, on, p, ep, pl.grid, stream)
+                  : launch_episode_t<true, false>(net, on, p, ep, pl.grid, stream);
+  return pl.ohl ? launch_episode_t<false, true>(net, on, p, ep, pl.grid, stream)
+                : launch_episode_t<false, false>(net, on, p, ep, pl.grid, stream);
 }
 
 #ifdef MZH_STAMPS

@@ -501,6 +501,70 @@ class Engine:
         out["_status"] = status
         return out
 
+    def play_episodes(self, n_sims, state, max_steps, *, tie_idx, noise=None, action_u=None, minmax_in=None,
+                      goal_peg=2, temperature=1.0, deterministic=False, discount=0.8, eps=0.25, np1_ucb=False,
+                      record_obs=False, visits=False, out=None, err=None):
+        """Whole episodes in one launch (mzh_play_episodes): env b starts from state[b] ([B, n_disks] uint8) and
+        plays until it is done; move t of env b searches with row [t, b] of tie_idx [T, B] int32, noise [T, B, 6]
+        float64 (None: no root noise) and action_u [T, B] float64 (None when deterministic), its MinMaxStats
+        starting from minmax_in[b] ([B, 2]; None: fresh) and carried on the device.  T >= max_steps.  All tensors
+        on the engine's device.
+        Returns the record -- pi [T, B, 6], root_q [T, B], action [T, B] int32, reward [T, B] int8 codes (0 -> 0,
+        1 -> 100, -1 -> -0.1), with record_obs the observations searched obs [T, B, 3 n_disks], with visits=True
+        visits [T, B, 6] -- whose rows t >= steps[b] the kernel leaves as they are (allocated here: action -1,
+        everything else 0; or the caller's tensors of the same names in `out`), and per env steps, illegal
+        (int32), solved (uint8), final_state [B, n_disks] and minmax [B, 2].  err [1] int32 counts the envs
+        refused on the device (a start state with a peg outside 0..2; such an env plays nothing)."""
+        d = self.device
+        if tie_idx.dim() != 2:
+            raise ValueError(f"play_episodes: tie_idx must be [T, B], got {tuple(tie_idx.shape)}")
+        T, B = (int(x) for x in tie_idx.shape)
+        keep = []
+
+        def dev(name, t, dtype, shape):
+            if t is None:
+                return None
+            if tuple(t.shape) != shape or t.dtype != dtype:
+                raise ValueError(f"play_episodes: {name} must be {dtype} {shape}, got {t.dtype} {tuple(t.shape)}")
+            t = t.to(d).contiguous()
+            keep.append(t)
+            return t
+
+        res = dict(out or {})
+        for k, shape, dt, fill in (("pi", (T, B, ACTIONS), torch.float64, 0), ("root_q", (T, B), torch.float64, 0),
+                                   ("action", (T, B), torch.int32, -1), ("reward", (T, B), torch.int8, 0),
+                                   ("obs", (T, B, 3 * self.n_disks), torch.float32, 0),
+                                   ("visits", (T, B, ACTIONS), torch.int32, 0)):
+            if k in res:
+                if not res[k].is_contiguous() or res[k].device != d:  # written in place: no silent copy
+                    raise ValueError(f"play_episodes: out[{k!r}] must be contiguous on {d}")
+                res[k] = dev(k, res[k], dt, shape)
+            elif k not in ("obs", "visits") or (record_obs if k == "obs" else visits):
+                res[k] = torch.full(shape, fill, dtype=dt, device=d)
+        res.update(steps=torch.empty(B, dtype=torch.int32, device=d), illegal=torch.empty(B, dtype=torch.int32, device=d),
+                   solved=torch.empty(B, dtype=torch.uint8, device=d),
+                   final_state=torch.empty((B, self.n_disks), dtype=torch.uint8, device=d),
+                   minmax=torch.empty((B, 2), dtype=torch.float64, device=d),
+                   err=torch.zeros(1, dtype=torch.int32, device=d) if err is None else err)
+        a = _lib.EpisodeArgs()
+        a.B, a.T, a.n_sims, a.goal_peg, a.max_steps = B, T, int(n_sims), int(goal_peg), int(max_steps)
+        a.deterministic, a.flags = (1 if deterministic else 0), search_flags(None, None, np1_ucb)
+        a.discount, a.eps, a.temperature = float(discount), float(eps), float(temperature)
+        a.state = ptr(dev("state", state, torch.uint8, (B, self.n_disks)))
+        a.noise = ptr(dev("noise", noise, torch.float64, (T, B, ACTIONS)))
+        a.tie_idx = ptr(dev("tie_idx", tie_idx, torch.int32, (T, B)))
+        a.action_u = ptr(dev("action_u", action_u, torch.float64, (T, B)))
+        a.minmax_in = ptr(dev("minmax_in", minmax_in, torch.float64, (B, 2)))
+        pt = self.pow_table(n_sims, float(temperature))
+        a.pow_table = ptr(pt)
+        for k, f in (("pi", "pi"), ("root_q", "root_q"), ("action", "action"), ("reward", "reward"), ("visits", "visits"),
+                     ("obs", "obs"), ("steps", "steps"), ("illegal", "illegal"), ("solved", "solved"),
+                     ("final_state", "final_state"), ("minmax_out", "minmax"), ("err_count", "err")):
+            setattr(a, k, ptr(res.get(f)))
+        check(_lib.lib().mzh_play_episodes(self._h, ctypes.byref(a), self._stream()), "mzh_play_episodes")
+        res["_keep"] = keep + [pt]
+        return res
+
     def _search_args(self, n_sims, *, obs, replay, tie_idx, noise, action_u, minmax_in, temperature, deterministic,
                      discount, eps, out, flags):
         """the mzh_search_args of a search / search_multi call and its result dict (outputs allocated unless given;

@@ -6,7 +6,9 @@ Same constructor and `training_loop(n_loops, min_replay_size, print_acc)` as the
     environment step is the reference's (selfplay.play_game); with selfplay="batched" the
     n_ep_x_loop episodes of a loop play in lockstep -- one search launch and one env-kernel launch
     per step for all of them (selfplay.BatchedSelfPlay), each episode an agent whose MinMaxStats
-    starts from the MCTS instance's, then the reference's per-episode bookkeeping
+    starts from the MCTS instance's -- or, with selfplay="device", to their ends in one kernel launch
+    (BatchedSelfPlay.play_episodes: for n_ep_x_loop = 1 the same episodes, buffer and RNG stream as
+    "batched"), then the reference's per-episode bookkeeping
     (selfplay.episode_records) and buffer filter -- or, with ingest="device", that bookkeeping, the
     filter and the buffer writes as one device call on the play's record (selfplay.ingest_records:
     the same buffer, priorities and RNG stream).  With n_ep_x_loop > 1 that is NOT the
@@ -33,6 +35,7 @@ from torch.autograd.graph import increment_version
 from .buffer import Buffer
 from .mcts import MCTS
 from .networks import MuZeroNet
+from .rng import predraw
 from .selfplay import BatchedSelfPlay, episode_records, ingest_records, play_game
 from .utils import adjust_temperature, organise_transitions
 
@@ -49,12 +52,21 @@ class Muzero:
         if ingest not in ("host", "device"):
             raise ValueError(f"ingest must be 'host' or 'device', not {ingest!r}")
         if ingest == "device":
-            if selfplay != "batched":
-                raise ValueError("Muzero(ingest='device') ingests a batched play's record: it needs selfplay='batched'")
+            if selfplay not in ("batched", "device"):
+                raise ValueError("Muzero(ingest='device') ingests a batched play's record: it needs selfplay='batched' "
+                                 "or selfplay='device'")
             if not TD_return:
                 raise ValueError("Muzero(ingest='device') implements the n-step TD returns: it needs TD_return=True")
             if torch.device(device).type != "cuda":
                 raise ValueError("Muzero(ingest='device') needs a GPU device")
+        if selfplay == "device" and torch.device(device).type != "cuda":
+            raise ValueError("Muzero(selfplay='device') plays its episodes in a GPU kernel: it needs a GPU device")
+        if selfplay == "device" and n_ep_x_loop > 1:
+            # not the reference's algorithm, as with "batched" below; said before anything touches the device
+            warnings.warn("Muzero(selfplay='device') with n_ep_x_loop > 1 plays the loop's episodes side by side, each "
+                          "from the same MinMaxStats (the union kept afterwards), env b on row b of a move-major "
+                          "draw table: not the reference's sequential schedule; use selfplay='sequential' for "
+                          "parity runs", RuntimeWarning, stacklevel=2)
         self.ingest = ingest
         self.n_ep_x_loop = n_ep_x_loop  # episodes collected per training loop
         self.discount = discount
@@ -84,9 +96,11 @@ class Muzero:
         if self._graphed is not None:
             self._graphed = self._graphed(self)
         # selfplay (not in the reference's signature): "sequential" = one episode after another as
-        # Muzero._play_game runs them; "batched" = a loop's n_ep_x_loop episodes in lockstep
-        if selfplay not in ("sequential", "batched"):
-            raise ValueError(f"selfplay must be 'sequential' or 'batched', not {selfplay!r}")
+        # Muzero._play_game runs them; "batched" = a loop's n_ep_x_loop episodes in lockstep; "device" = those
+        # episodes played to their ends in one kernel launch (BatchedSelfPlay.play_episodes)
+        if selfplay not in ("sequential", "batched", "device"):
+            raise ValueError(f"selfplay must be 'sequential' or 'batched', not {selfplay!r}: the accepted values are "
+                             "'sequential', 'batched' and 'device'")
         if selfplay == "batched" and n_ep_x_loop > 1:
             # not the reference's algorithm: the reference threads ONE MinMaxStats through its
             # episodes in order (Muzero.py:55) and interleaves the per-step draws differently
@@ -107,7 +121,7 @@ class Muzero:
                 ep_steps = [int(s) for s in self._play_games(self.n_ep_x_loop, episode=n * self.n_ep_x_loop,
                                                              deterministic=False)]
                 episodes = ()
-            elif self.selfplay == "batched":
+            elif self.selfplay in ("batched", "device"):
                 episodes = self._play_games(self.n_ep_x_loop, episode=n * self.n_ep_x_loop, deterministic=False)
             else:
                 episodes = (self._play_game(episode=n * self.n_ep_x_loop, deterministic=False)
@@ -155,9 +169,17 @@ class Muzero:
                              discount=self.discount, dirichlet_alpha=self.mcts.root_dirichlet_alpha,
                              root_exploration_eps=self.mcts.root_exploration_eps, goal_peg=env.goal[0],
                              np1_ucb=self.mcts.np1_ucb)
-        res = sp.play([env.init_state_idx] * n_games, temperature=adjust_temperature(episode),
-                      deterministic=deterministic, legacy_rng=True,
-                      minmax=[[mm.maximum, mm.minimum]] * n_games, record_obs=True)
+        kw = dict(temperature=adjust_temperature(episode), deterministic=deterministic,
+                  minmax=[[mm.maximum, mm.minimum]] * n_games)
+        if self.selfplay != "device":
+            res = sp.play([env.init_state_idx] * n_games, legacy_rng=True, record_obs=True, **kw)
+        elif n_games == 1:  # one launch; the global stream is left where the lockstep play leaves it
+            res = sp.play_episodes([env.init_state_idx], legacy_rng=True, **kw)
+        else:  # the whole draw table from the global stream, move-major: row t * n_games + b for move t of env b
+            T = int(env.max_steps)
+            flat = predraw(T * n_games, deterministic=deterministic, alpha=sp.alpha, eps=sp.eps)
+            draws = tuple(None if x is None else x.reshape((T, n_games) + x.shape[1:]) for x in flat)
+            res = sp.play_episodes([env.init_state_idx] * n_games, draws=draws, **kw)
         fin = res["minmax"].cpu().numpy()
         mm.maximum, mm.minimum = float(fin[:, 0].max()), float(fin[:, 1].min())
         if self.ingest == "device":

@@ -275,6 +275,72 @@ class BatchedSelfPlay:
         res = {k: torch.stack(v) if v else torch.empty(0, device=dev) for k, v in rec.items()}
         return dict(res, steps=env.steps_total, illegal=env.illegal_total, start_idx=run.start, minmax=run.mm)
 
+    def play_episodes(self, start_idx, temperature=1.0, deterministic=False, seed=0, legacy_rng=False, minmax=None,
+                      draws=None):
+        """`play(record_obs=True)` as ONE launch (Engine.play_episodes, mzh_play_episodes): a workgroup of the
+        latency kernel takes an env and plays it to its end -- search, action draw, env step and record -- without
+        returning to the host.  One network (no NetworkSet, no RecordedNetwork).  Returns the dict
+        play(record_obs=True) returns: the same keys, dtypes, shapes and fill values (action -1 and everything
+        else 0 at rows past an episode's end, reward as float64 through HanoiBatch.reward_value, active derived
+        from steps), the record trimmed to max(steps) rows -- the call's one host read.
+
+        Draw schedule: the draws are a table of max_steps x B rows, and env b takes row b of move t's draws at
+        every move, whichever envs are still playing.  At B = 1 that is play's schedule; at B > 1 it differs
+        (play gives row j of a move's draws to the j-th unfinished env).
+        draws = (noise [T, B, 6] float64, tie [T, B] int32, u [T, B] float64), T = max_steps: an explicit table
+        (arrays or tensors; noise None exactly when the searches take no root noise, rng.uses_noise, and u None
+        exactly when deterministic).  draws = None: one vectorised draw of the whole table,
+        rng.synthetic_draws(T * B, seed=seed) reshaped -- three child streams of `seed`, not play's per-move
+        seeds (200 per-move generator constructions would cost as much as the launch).
+        legacy_rng = True (B = 1 only, without draws): the table is rng.predraw(T) from NumPy's global stream;
+        after the launch the stream is put back and advanced by rng.predraw(steps), so it is left exactly
+        where play(legacy_rng=True) leaves it.
+        RuntimeError if the kernel refused a start state (a peg outside 0..2: not reachable from start_idx)."""
+        start = np.asarray(start_idx, np.int64).reshape(-1)
+        B, T = int(start.shape[0]), int(self.max_steps)
+        kw = dict(deterministic=deterministic, alpha=self.alpha, eps=self.eps)
+        if isinstance(self.network, (NetworkSet, RecordedNetwork)):
+            raise ValueError("play_episodes: one live network only (no NetworkSet, no RecordedNetwork)")
+        if legacy_rng and (B != 1 or draws is not None):
+            raise ValueError("play_episodes: legacy_rng=True is the one-env schedule: it needs B = 1 and draws=None, "
+                             f"got B = {B}")
+        if T < 1:
+            raise ValueError(f"play_episodes: max_steps must be >= 1, got {T}")
+        if draws is not None:
+            draws = _episode_draws(draws, T, B, _rng.uses_noise(**kw), not deterministic)
+        if B == 0:  # nothing to play and (a checked [T, 0] table) nothing to draw: play's empty records
+            return self.play(start, temperature, deterministic, seed, legacy_rng, minmax, record_obs=True)
+        state0 = None
+        if draws is None:  # one flat draw of T * B rows, row t * B + b for move t of env b
+            if legacy_rng:
+                state0 = np.random.get_state()
+            flat = _rng.predraw(T, **kw) if legacy_rng else _rng.synthetic_draws(T * B, seed=seed, **kw)
+            draws = tuple(None if x is None else torch.from_numpy(x).reshape((T, B) + x.shape[1:]) for x in flat)
+        t_max = 0
+        try:
+            eng = engine_for(self.network, self.S, B)
+            dev = eng.device
+            noise, tie, u = (None if x is None else x.to(dev) for x in draws)
+            pw = 3 ** np.arange(self.N - 1, -1, -1, dtype=np.int64)
+            state = torch.from_numpy(((start[:, None] // pw) % 3).astype(np.uint8)).to(dev)
+            mm = None if minmax is None else torch.as_tensor(np.asarray(minmax, np.float64)).reshape(B, 2).to(dev)
+            out = eng.play_episodes(self.S, state, T, tie_idx=tie, noise=noise, action_u=u, minmax_in=mm,
+                                    goal_peg=self.goal_peg, temperature=float(temperature),
+                                    deterministic=bool(deterministic), discount=self.discount, eps=self.eps,
+                                    np1_ucb=self.np1_ucb, record_obs=True)
+            steps = out["steps"]
+            t_max, n_err = (int(x) for x in torch.stack([steps.max(), out["err"][0]]).cpu())  # the one host read
+        finally:
+            if state0 is not None:  # the stream as the moves played leave it (none, if the call failed)
+                np.random.set_state(state0)
+                _rng.predraw(t_max, **kw)
+        if n_err:
+            raise RuntimeError(f"mzh_play_episodes refused {n_err} start state(s)")
+        active = torch.arange(t_max, device=dev)[:, None] < steps[None, :]
+        return dict(action=out["action"][:t_max], reward=HanoiBatch.reward_value(out["reward"][:t_max]),
+                    pi=out["pi"][:t_max], root_q=out["root_q"][:t_max], active=active, obs=out["obs"][:t_max],
+                    steps=steps, illegal=out["illegal"], start_idx=torch.from_numpy(start).to(dev), minmax=out["minmax"])
+
     def play_plans(self, start_idx, max_plan_len, temperature=1.0, deterministic=False, seed=0, legacy_rng=False,
                    minmax=None, net_index=None):
         """Plan-ahead episodes (acting_experiments/planning_multiple_actions.py:111-183): every env searches
@@ -394,6 +460,26 @@ class BatchedSelfPlay:
             run.advance("mzh_env_step_observe", mzh_probe_actions=err)
             t += 1
         return dict(reward=rec_r[:t], value=rec_v[:t], legal=rec_l[:t], action=rec_a[:t], steps=env.steps_total)
+
+
+def _episode_draws(draws, T, B, noisy, stochastic):
+    """play_episodes' explicit draw table, checked on the host: (noise, tie, u) -> tensors noise [T, B, 6] float64
+    (None exactly when not noisy), tie [T, B] int32, u [T, B] float64 (None exactly when not stochastic).
+    ValueError for anything else: a wrong shape or dtype is not converted."""
+    if not isinstance(draws, (tuple, list)) or len(draws) != 3:
+        raise ValueError("play_episodes: draws must be (noise, tie, u)")
+    out = []
+    for name, x, dt, shape, want in (("noise", draws[0], torch.float64, (T, B, ACTIONS), noisy),
+                                     ("tie", draws[1], torch.int32, (T, B), True),
+                                     ("u", draws[2], torch.float64, (T, B), stochastic)):
+        if (x is not None) != want:
+            raise ValueError(f"play_episodes: draws' {name} must be {'given' if want else 'None'} for these searches")
+        if x is not None:
+            x = torch.as_tensor(x)
+            if x.dtype != dt or tuple(x.shape) != shape:
+                raise ValueError(f"play_episodes: draws' {name} must be {dt} {shape}, got {x.dtype} {tuple(x.shape)}")
+        out.append(x)
+    return tuple(out)
 
 
 def perturbation_arrays(B, n_disks, noise_std, permute_disc):
