@@ -1204,14 +1204,17 @@ extern "C" int mzh_memo_debug_table(mzh_engine* eng, float* latent, float* recor
   return MZH_OK;
 }
 
-static int search_common(mzh_engine* eng, const mzh_search_args* a, mzh_stream stream, bool replay) {
-  if (!eng || !a) return fail(MZH_ERR_ARG, "engine or args NULL");
+// What mzh_search, mzh_search_replay and mzh_search_multi (single = false: it needs no engine network) refuse of a
+// search's arguments, in this order.  *launch = false with MZH_OK: B = 0, nothing launches and the plan says so (a
+// caller naming the kernel sees "none").
+static int search_args_check(const mzh_engine* eng, const mzh_search_args* a, bool replay, bool single, bool* launch) {
+  *launch = false;
   if (a->B < 0 || a->n_sims < 0) return fail(MZH_ERR_ARG, "B=%d n_sims=%d", a->B, a->n_sims);
   if (a->B > eng->max_roots) return fail(MZH_ERR_CAPACITY, "B=%d > max_roots=%d", a->B, eng->max_roots);
   if (a->n_sims > eng->max_sims) return fail(MZH_ERR_CAPACITY, "n_sims=%d > max_sims=%d", a->n_sims, eng->max_sims);
   if (!(a->temperature >= 0.0 && a->temperature <= 1.0))
     return fail(MZH_ERR_TEMPERATURE, "Expect `temperature` to be in the range [0.0, 1.0], got %g", a->temperature);
-  if (a->B == 0) {  // nothing launches: the plan says so (a caller naming the kernel sees "none")
+  if (a->B == 0) {
     if (a->plan_out) {
       memset(a->plan_out, 0, sizeof(*a->plan_out));
       snprintf(a->plan_out->kernel, sizeof(a->plan_out->kernel), "none");
@@ -1223,11 +1226,33 @@ static int search_common(mzh_engine* eng, const mzh_search_args* a, mzh_stream s
     if (!a->rp_root_pi || (a->n_sims > 0 && !a->rp_sim))
       return fail(MZH_ERR_ARG, "replay search needs rp_root_pi and rp_sim");
   } else {
-    if (!eng->loaded) return fail(MZH_ERR_STATE, "weights not loaded");
+    if (single && !eng->loaded) return fail(MZH_ERR_STATE, "weights not loaded");
     if (!a->obs) return fail(MZH_ERR_ARG, "obs is required");
   }
   if (!a->deterministic && !a->action_u && a->action)
     return fail(MZH_ERR_ARG, "stochastic action selection needs action_u");
+  *launch = true;
+  return MZH_OK;
+}
+
+// the device side of a call's mzh_multi_args: the caller's net_index and status, the engine's tile workspace and set
+static MzhMultiParams multi_params(const mzh_engine* eng, const mzh_multi_args* m) {
+  MzhMultiParams mp{};
+  mp.net_index = m->net_index;
+  mp.M = m->n_networks;
+  mp.tiles = eng->mtiles;
+  mp.ntiles = eng->mntiles;
+  mp.status = m->status;
+  mp.stride = eng->set_stride;
+  mp.scal = eng->set_scal;
+  return mp;
+}
+
+static int search_common(mzh_engine* eng, const mzh_search_args* a, mzh_stream stream, bool replay) {
+  if (!eng || !a) return fail(MZH_ERR_ARG, "engine or args NULL");
+  bool launch;
+  const int ck = search_args_check(eng, a, replay, true, &launch);
+  if (!launch) return ck;
   MzhSearchPlan pl;
   const int st = make_plan(a->B, a->n_sims, a->flags, replay, eng->support, a->minmax_in != nullptr, &pl);
   if (st) return st;
@@ -1284,22 +1309,9 @@ extern "C" int mzh_search_multi(mzh_engine* eng, const mzh_search_args* a, const
   if (a->rp_sim || a->rp_root_pi) return fail(MZH_ERR_ARG, "a multi-network search has no replay (tree-only) form");
   if (a->flags & (MZH_FLAG_KERNEL_WAVE | MZH_FLAG_KERNEL_WAVE16 | MZH_FLAG_KERNEL_ONE | MZH_FLAG_COOP_OCC2))
     return fail(MZH_ERR_ARG, "a multi-network search runs the cooperative kernel only (flags=0x%x)", a->flags);
-  if (a->B < 0 || a->n_sims < 0) return fail(MZH_ERR_ARG, "B=%d n_sims=%d", a->B, a->n_sims);
-  if (a->B > eng->max_roots) return fail(MZH_ERR_CAPACITY, "B=%d > max_roots=%d", a->B, eng->max_roots);
-  if (a->n_sims > eng->max_sims) return fail(MZH_ERR_CAPACITY, "n_sims=%d > max_sims=%d", a->n_sims, eng->max_sims);
-  if (!(a->temperature >= 0.0 && a->temperature <= 1.0))
-    return fail(MZH_ERR_TEMPERATURE, "Expect `temperature` to be in the range [0.0, 1.0], got %g", a->temperature);
-  if (a->B == 0) {
-    if (a->plan_out) {
-      memset(a->plan_out, 0, sizeof(*a->plan_out));
-      snprintf(a->plan_out->kernel, sizeof(a->plan_out->kernel), "none");
-    }
-    return MZH_OK;
-  }
-  if (!a->visits) return fail(MZH_ERR_ARG, "visits output is required");
-  if (!a->obs) return fail(MZH_ERR_ARG, "obs is required");
-  if (!a->deterministic && !a->action_u && a->action)
-    return fail(MZH_ERR_ARG, "stochastic action selection needs action_u");
+  bool launch;
+  const int ck = search_args_check(eng, a, false, false, &launch);
+  if (!launch) return ck;
   const int S = a->n_sims;
   MzhSearchPlan pl{};
   pl.R = pick_tile(a->B, a->flags);
@@ -1323,116 +1335,81 @@ extern "C" int mzh_search_multi(mzh_engine* eng, const mzh_search_args* a, const
   DeviceGuard g(eng->device);
   if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
   const MzhSearchParams p = search_params(eng, a);
-  MzhMultiParams mp{};
-  mp.net_index = m->net_index;
-  mp.M = m->n_networks;
-  mp.tiles = eng->mtiles;
-  mp.ntiles = eng->mntiles;
-  mp.status = m->status;
-  mp.stride = eng->set_stride;
-  mp.scal = eng->set_scal;
-  hipError_t e = mzh_launch_search_multi(pl, eng->setnet, p, mp, (hipStream_t)stream);
+  hipError_t e = mzh_launch_search_multi(pl, eng->setnet, p, multi_params(eng, m), (hipStream_t)stream);
   return e == hipSuccess ? MZH_OK : hip_fail(e, "multi search launch");
 }
 
-// The six one-step lookaheads of a batch of roots in one launch (mzh_probe_kernel; with `m` the rows of a
-// loaded network set, mzh_probe_multi_kernel).  What the arguments alone decide is refused first, so those
-// refusals need neither a device nor an engine.
-extern "C" int mzh_probe_actions(mzh_engine* eng, const mzh_probe_args* a, const mzh_multi_args* m, mzh_stream stream) {
-  if (!a) return fail(MZH_ERR_ARG, "probe_actions: args is NULL");
-  if (a->n < 1 || a->B < 1 || (!a->env_index && a->B < a->n))
-    return fail(MZH_ERR_ARG, "probe_actions: bad n=%d rows for B=%d envs", a->n, a->B);
-  if (!a->obs || !a->reward || !a->value || (a->legal && !a->state))
-    return fail(MZH_ERR_ARG, "probe_actions: required buffer is NULL (obs, reward, value; state for legal)");
-  if (a->flags & ~(MZH_FLAG_COOP_TILE16 | MZH_FLAG_COOP_TILE32))
-    return fail(MZH_ERR_ARG, "probe_actions: flags=0x%x, only MZH_FLAG_COOP_TILE16 / 32 apply", a->flags);
+// ---- the calls over rows of a sub-batch: mzh_probe_actions, mzh_saliency, mzh_param_grads ----
+// What all three refuse, in this order: what the arguments alone decide first (those refusals need neither a device
+// nor an engine), then the engine, its weights or set, its capacity.  `who` prefixes the text; have / need: whether
+// the call's required buffers are there, and their names.
+static int rows_check(const char* who, int B, int n, const int32_t* env_index, uint32_t flags, bool have, const char* need,
+                      const mzh_multi_args* m, const mzh_engine* eng) {
+  if (n < 1 || B < 1 || (!env_index && B < n)) return fail(MZH_ERR_ARG, "%s: bad n=%d rows for B=%d envs", who, n, B);
+  if (!have) return fail(MZH_ERR_ARG, "%s: required buffer is NULL (%s)", who, need);
+  if (flags & ~(MZH_FLAG_COOP_TILE16 | MZH_FLAG_COOP_TILE32))
+    return fail(MZH_ERR_ARG, "%s: flags=0x%x, only MZH_FLAG_COOP_TILE16 / 32 apply", who, flags);
   if (m) {
-    if (!m->net_index) return fail(MZH_ERR_ARG, "probe_actions: net_index is NULL");
+    if (!m->net_index) return fail(MZH_ERR_ARG, "%s: net_index is NULL", who);
     if (m->n_networks < 1 || m->n_networks > MZH_MULTI_MAX_NETS)
-      return fail(MZH_ERR_ARG, "probe_actions: n_networks=%d outside [1, %d]", m->n_networks, MZH_MULTI_MAX_NETS);
+      return fail(MZH_ERR_ARG, "%s: n_networks=%d outside [1, %d]", who, m->n_networks, MZH_MULTI_MAX_NETS);
   }
-  if (!eng) return fail(MZH_ERR_ARG, "probe_actions: engine NULL");
+  if (!eng) return fail(MZH_ERR_ARG, "%s: engine NULL", who);
   if (m) {
     if (eng->set_m == 0) return fail(MZH_ERR_STATE, "no weight set loaded (mzh_load_weight_set)");
     if (m->n_networks > eng->set_m)
-      return fail(MZH_ERR_ARG, "probe_actions: n_networks=%d outside [1, %d], the loaded set", m->n_networks, eng->set_m);
+      return fail(MZH_ERR_ARG, "%s: n_networks=%d outside [1, %d], the loaded set", who, m->n_networks, eng->set_m);
   } else if (!eng->loaded) {
     return fail(MZH_ERR_STATE, "weights not loaded");
   }
-  if (a->n > eng->max_roots) return fail(MZH_ERR_CAPACITY, "probe_actions: n=%d > max_roots=%d", a->n, eng->max_roots);
+  if (n > eng->max_roots) return fail(MZH_ERR_CAPACITY, "%s: n=%d > max_roots=%d", who, n, eng->max_roots);
+  return MZH_OK;
+}
+
+// the fields every row call's parameter block starts with (mzh_probe_args, mzh_saliency_args, mzh_pgrad_args)
+template <class P, class ARGS>
+static void row_params(P& p, const mzh_engine* eng, const ARGS* a) {
+  p.B = a->B; p.n = a->n; p.in_dim = eng->in_dim; p.kin = eng->kin; p.n_disks = eng->n_disks;
+  p.env_index = a->env_index; p.obs = a->obs; p.err_count = a->err_count;
+}
+
+// The six one-step lookaheads of a batch of roots in one launch (mzh_probe_kernel; with `m` the rows of a loaded
+// network set, mzh_probe_multi_kernel)
+extern "C" int mzh_probe_actions(mzh_engine* eng, const mzh_probe_args* a, const mzh_multi_args* m, mzh_stream stream) {
+  if (!a) return fail(MZH_ERR_ARG, "probe_actions: args is NULL");
+  const int st = rows_check("probe_actions", a->B, a->n, a->env_index, a->flags,
+                            a->obs && a->reward && a->value && (!a->legal || a->state),
+                            "obs, reward, value; state for legal", m, eng);
+  if (st) return st;
   DeviceGuard g(eng->device);
   if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
   MzhProbeParams p{};
-  p.B = a->B; p.n = a->n; p.in_dim = eng->in_dim; p.kin = eng->kin; p.n_disks = eng->n_disks;
-  p.env_index = a->env_index; p.obs = a->obs; p.state = a->state; p.reward = a->reward; p.value = a->value;
+  row_params(p, eng, a);
+  p.state = a->state; p.reward = a->reward; p.value = a->value;
   p.legal = a->legal; p.h0 = a->h0; p.pi0 = a->pi0; p.value0 = a->value0; p.h1 = a->h1; p.pi1 = a->pi1;
-  p.err_count = a->err_count;
-  const int R = pick_tile(a->n, a->flags);
-  hipError_t e;
-  if (m) {
-    MzhMultiParams mp{};
-    mp.net_index = m->net_index;
-    mp.M = m->n_networks;
-    mp.tiles = eng->mtiles;
-    mp.ntiles = eng->mntiles;
-    mp.status = m->status;
-    mp.stride = eng->set_stride;
-    mp.scal = eng->set_scal;
-    e = mzh_launch_probe(R, eng->setnet, p, &mp, (hipStream_t)stream);
-  } else {
-    e = mzh_launch_probe(R, eng->net, p, nullptr, (hipStream_t)stream);
-  }
+  const MzhMultiParams mp = m ? multi_params(eng, m) : MzhMultiParams{};
+  hipError_t e = mzh_launch_probe(pick_tile(a->n, a->flags), m ? eng->setnet : eng->net, p, m ? &mp : nullptr, (hipStream_t)stream);
   return e == hipSuccess ? MZH_OK : hip_fail(e, "probe_actions launch");
 }
 
-// Input saliency of the policy and value heads of a batch of rows in one launch (mzh_saliency_kernel; with `m`
-// the rows of a loaded network set, mzh_saliency_multi_kernel).  Refusals in mzh_probe_actions' order: what the
-// arguments alone decide first, so those need neither a device nor an engine.
+// Input saliency of the policy and value heads of a batch of rows in one launch (mzh_saliency_kernel; with `m` the
+// rows of a loaded network set, mzh_saliency_multi_kernel)
 extern "C" int mzh_saliency(mzh_engine* eng, const mzh_saliency_args* a, const mzh_multi_args* m, mzh_stream stream) {
   if (!a) return fail(MZH_ERR_ARG, "saliency: args is NULL");
-  if (a->n < 1 || a->B < 1 || (!a->env_index && a->B < a->n))
-    return fail(MZH_ERR_ARG, "saliency: bad n=%d rows for B=%d envs", a->n, a->B);
-  if (!a->obs || !a->sal_policy || !a->sal_value)
-    return fail(MZH_ERR_ARG, "saliency: required buffer is NULL (obs, sal_policy, sal_value)");
-  if (a->flags & ~(MZH_FLAG_COOP_TILE16 | MZH_FLAG_COOP_TILE32))
-    return fail(MZH_ERR_ARG, "saliency: flags=0x%x, only MZH_FLAG_COOP_TILE16 / 32 apply", a->flags);
-  if (m) {
-    if (!m->net_index) return fail(MZH_ERR_ARG, "saliency: net_index is NULL");
-    if (m->n_networks < 1 || m->n_networks > MZH_MULTI_MAX_NETS)
-      return fail(MZH_ERR_ARG, "saliency: n_networks=%d outside [1, %d]", m->n_networks, MZH_MULTI_MAX_NETS);
-  }
-  if (!eng) return fail(MZH_ERR_ARG, "saliency: engine NULL");
-  if (m) {
-    if (eng->set_m == 0) return fail(MZH_ERR_STATE, "no weight set loaded (mzh_load_weight_set)");
-    if (m->n_networks > eng->set_m)
-      return fail(MZH_ERR_ARG, "saliency: n_networks=%d outside [1, %d], the loaded set", m->n_networks, eng->set_m);
-  } else if (!eng->loaded) {
-    return fail(MZH_ERR_STATE, "weights not loaded");
-  }
-  if (a->n > eng->max_roots) return fail(MZH_ERR_CAPACITY, "saliency: n=%d > max_roots=%d", a->n, eng->max_roots);
+  const int st = rows_check("saliency", a->B, a->n, a->env_index, a->flags, a->obs && a->sal_policy && a->sal_value,
+                            "obs, sal_policy, sal_value", m, eng);
+  if (st) return st;
   DeviceGuard g(eng->device);
   if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
   MzhSalParams p{};
-  p.B = a->B; p.n = a->n; p.in_dim = eng->in_dim; p.kin = eng->kin; p.n_disks = eng->n_disks;
-  p.env_index = a->env_index; p.obs = a->obs; p.logit_index = a->logit_index;
+  row_params(p, eng, a);
+  p.logit_index = a->logit_index;
   p.sal_policy = a->sal_policy; p.sal_value = a->sal_value; p.picked = a->picked;
   p.disc_policy = a->disc_policy; p.disc_value = a->disc_value;
-  p.h0 = a->h0; p.pi0 = a->pi0; p.value0 = a->value0; p.err_count = a->err_count;
-  const int R = pick_tile(a->n, a->flags);
-  hipError_t e;
-  if (m) {
-    MzhMultiParams mp{};
-    mp.net_index = m->net_index;
-    mp.M = m->n_networks;
-    mp.tiles = eng->mtiles;
-    mp.ntiles = eng->mntiles;
-    mp.status = m->status;
-    mp.stride = eng->set_stride;
-    mp.scal = eng->set_scal;
-    e = mzh_launch_saliency(R, eng->setnet, eng->settnet, p, &mp, (hipStream_t)stream);
-  } else {
-    e = mzh_launch_saliency(R, eng->net, eng->tnet, p, nullptr, (hipStream_t)stream);
-  }
+  p.h0 = a->h0; p.pi0 = a->pi0; p.value0 = a->value0;
+  const MzhMultiParams mp = m ? multi_params(eng, m) : MzhMultiParams{};
+  hipError_t e = mzh_launch_saliency(pick_tile(a->n, a->flags), m ? eng->setnet : eng->net, m ? eng->settnet : eng->tnet, p,
+                                     m ? &mp : nullptr, (hipStream_t)stream);
   return e == hipSuccess ? MZH_OK : hip_fail(e, "saliency launch");
 }
 
@@ -1489,33 +1466,16 @@ static int pgrad_ensure(mzh_engine* eng, bool set, hipStream_t stream) {
 }
 
 // Parameter gradients of the five sub-networks of a batch of rows (mzh_pgrad_kernel; with `m` the rows of a loaded
-// network set, mzh_pgrad_multi_kernel; with args.grad then mzh_pgrad_expand_kernel).  Refusals in mzh_saliency's
-// order: what the arguments alone decide first, so those need neither a device nor an engine.
+// network set, mzh_pgrad_multi_kernel; with args.grad then mzh_pgrad_expand_kernel)
 extern "C" int mzh_param_grads(mzh_engine* eng, const mzh_pgrad_args* a, const mzh_multi_args* m, mzh_stream stream) {
   if (!a) return fail(MZH_ERR_ARG, "param_grads: args is NULL");
-  if (a->n < 1 || a->B < 1 || (!a->env_index && a->B < a->n))
-    return fail(MZH_ERR_ARG, "param_grads: bad n=%d rows for B=%d envs", a->n, a->B);
-  if (!a->obs || !a->action || !a->delta1 || !a->delta2 || !a->act || !a->h0 || !a->z1)
-    return fail(MZH_ERR_ARG, "param_grads: required buffer is NULL (obs, action, delta1, delta2, act, h0, z1)");
-  if (a->flags & ~(MZH_FLAG_COOP_TILE16 | MZH_FLAG_COOP_TILE32))
-    return fail(MZH_ERR_ARG, "param_grads: flags=0x%x, only MZH_FLAG_COOP_TILE16 / 32 apply", a->flags);
-  if (m) {
-    if (!m->net_index) return fail(MZH_ERR_ARG, "param_grads: net_index is NULL");
-    if (m->n_networks < 1 || m->n_networks > MZH_MULTI_MAX_NETS)
-      return fail(MZH_ERR_ARG, "param_grads: n_networks=%d outside [1, %d]", m->n_networks, MZH_MULTI_MAX_NETS);
-  }
-  if (!eng) return fail(MZH_ERR_ARG, "param_grads: engine NULL");
-  if (m) {
-    if (eng->set_m == 0) return fail(MZH_ERR_STATE, "no weight set loaded (mzh_load_weight_set)");
-    if (m->n_networks > eng->set_m)
-      return fail(MZH_ERR_ARG, "param_grads: n_networks=%d outside [1, %d], the loaded set", m->n_networks, eng->set_m);
-  } else if (!eng->loaded) {
-    return fail(MZH_ERR_STATE, "weights not loaded");
-  }
-  if (a->n > eng->max_roots) return fail(MZH_ERR_CAPACITY, "param_grads: n=%d > max_roots=%d", a->n, eng->max_roots);
+  int st = rows_check("param_grads", a->B, a->n, a->env_index, a->flags,
+                      a->obs && a->action && a->delta1 && a->delta2 && a->act && a->h0 && a->z1,
+                      "obs, action, delta1, delta2, act, h0, z1", m, eng);
+  if (st) return st;
   DeviceGuard g(eng->device);
   if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
-  const int st = pgrad_ensure(eng, m != nullptr, (hipStream_t)stream);
+  st = pgrad_ensure(eng, m != nullptr, (hipStream_t)stream);
   if (st) return st;
   MzhPgNetT gt{};
   gt.base = reinterpret_cast<const float4*>(m ? eng->setgbuf : eng->gbuf);
@@ -1523,26 +1483,13 @@ extern "C" int mzh_param_grads(mzh_engine* eng, const mzh_pgrad_args* a, const m
   gt.kb_rwd2 = eng->gmaps->layout.kb[MZH_G_RWD2];
   gt.stride = eng->gstride * sizeof(float);
   MzhPgradParams p{};
-  p.B = a->B; p.n = a->n; p.in_dim = eng->in_dim; p.kin = eng->kin;
-  p.env_index = a->env_index; p.obs = a->obs; p.action = a->action; p.policy_logit = a->policy_logit;
+  row_params(p, eng, a);
+  p.action = a->action; p.policy_logit = a->policy_logit;
   p.delta1 = a->delta1; p.delta2 = a->delta2; p.act = a->act; p.h0 = a->h0; p.z1 = a->z1; p.h1 = a->h1;
   p.pi0 = a->pi0; p.value0 = a->value0; p.reward = a->reward; p.objective = a->objective; p.grad = a->grad;
-  p.err_count = a->err_count;
-  const int R = pick_tile(a->n, a->flags);
-  hipError_t e;
-  if (m) {
-    MzhMultiParams mp{};
-    mp.net_index = m->net_index;
-    mp.M = m->n_networks;
-    mp.tiles = eng->mtiles;
-    mp.ntiles = eng->mntiles;
-    mp.status = m->status;
-    mp.stride = eng->set_stride;
-    mp.scal = eng->set_scal;
-    e = mzh_launch_pgrad(R, eng->setnet, eng->settnet, gt, p, eng->support, &mp, (hipStream_t)stream);
-  } else {
-    e = mzh_launch_pgrad(R, eng->net, eng->tnet, gt, p, eng->support, nullptr, (hipStream_t)stream);
-  }
+  const MzhMultiParams mp = m ? multi_params(eng, m) : MzhMultiParams{};
+  hipError_t e = mzh_launch_pgrad(pick_tile(a->n, a->flags), m ? eng->setnet : eng->net, m ? eng->settnet : eng->tnet, gt, p,
+                                  eng->support, m ? &mp : nullptr, (hipStream_t)stream);
   return e == hipSuccess ? MZH_OK : hip_fail(e, "param_grads launch");
 }
 

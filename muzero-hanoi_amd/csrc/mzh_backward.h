@@ -1,5 +1,5 @@
 // mzh_backward.h -- what the backward kernels share (mzh_saliency.hip, mzh_pgrad.hip): the transposed product
-// dX = dY . W on v_mfma_f32_16x16x4_f32 over MzhPackedT-format fragments, and the seed of a 33-bin head.
+// dX = dY . W on v_mfma_f32_16x16x4_f32 over MzhPackedT-format fragments, and the seed of a reward / value head.
 #pragma once
 #include "mzh_device.h"
 
@@ -52,5 +52,14 @@ __device__ __forceinline__ void sal_value_seed33(const float* l, float* seed) {
     float v = 0.0f;
     if (i < 33) v = dv * (mzh_expf(l[i] - m) / s) * ((float)(i - 16) - E);
     seed[mzh_kpos(i)] = v;
+  }
+}
+
+// the seed of a reward / value head from its logits: d scalar / d logits of 33 bins, the unit seed of one bin
+__device__ __forceinline__ void sal_head_seed(int support, const float* l, float* seed) {
+  if (support == 33) {
+    sal_value_seed33(l, seed);
+  } else {
+    for (int i = 0; i < 16; ++i) seed[i] = i == 0 ? 1.0f : 0.0f;
   }
 }

@@ -308,7 +308,20 @@ __device__ __forceinline__ void mzh_net_select(MzhNet& n, const MzhMultiParams& 
   }
 }
 
-// mzh_saliency (mzh_saliency_kernel / mzh_saliency_multi_kernel, mzh_saliency.hip): rows as in MzhProbeParams
+// What the kernels over R rows of a sub-batch share (mzh_rows.h: the probe, saliency and gradient kernels): row j
+// of the call is env env_index[j] (or j) of a batch of B; every array but env_index (and a set's net_index) is
+// indexed by env
+// (the eighth common field, err_count, is the last member of each block below, where it has always been: moved up
+// here it changes the kernels' kernarg loads and with them their register allocation and measured time)
+struct MzhRowParams {
+  int B, n;                  // envs of the batch, rows of the call
+  int in_dim, kin;           // observation width 3N and its zero-padded width (16 * rep0.kb)
+  int n_disks;
+  const int32_t* env_index;  // [n] nullable
+  const float* obs;          // [B][in_dim]
+};
+
+// mzh_saliency (mzh_saliency_kernel / mzh_saliency_multi_kernel, mzh_saliency.hip): rows as in MzhRowParams
 struct MzhSalNetT {  // the transposed blob (MzhPackedT) of one network; a set's at `stride` bytes
   const float4* base;
   int off[MZH_T_LAYERS];  // float4 offsets of the layers' fragments
@@ -316,12 +329,7 @@ struct MzhSalNetT {  // the transposed blob (MzhPackedT) of one network; a set's
   int nt_rep0;            // 16-column tiles of the observation
   size_t stride;
 };
-struct MzhSalParams {
-  int B, n;
-  int in_dim, kin;
-  int n_disks;
-  const int32_t* env_index;    // [n] nullable
-  const float* obs;            // [B][in_dim]
+struct MzhSalParams : MzhRowParams {
   const int32_t* logit_index;  // [B] nullable
   float* sal_policy;           // [B][in_dim]
   float* sal_value;            // [B][in_dim]
@@ -331,25 +339,21 @@ struct MzhSalParams {
   float* h0;                   // [B][64] nullable
   float* pi0;                  // [B][6] nullable
   float* value0;               // [B] nullable
-  int32_t* err_count;          // nullable
+  int32_t* err_count;          // nullable: += 1 per skipped row
 };
 size_t mzh_saliency_smem_bytes(int R);
 hipError_t mzh_launch_saliency(int R, const MzhNet& net, const MzhSalNetT& nt, const MzhSalParams& p,
                                const MzhMultiParams* mp, hipStream_t stream);
 
 // mzh_param_grads (mzh_pgrad_kernel / mzh_pgrad_multi_kernel / mzh_pgrad_expand_kernel, mzh_pgrad.hip): rows
-// as in MzhProbeParams
+// as in MzhRowParams
 struct MzhPgNetT {  // dynamic_net.2 and rwd_net.2 transposed (MzhPackedG) of one network; a set's at `stride` bytes
   const float4* base;
   int off[MZH_G_LAYERS];  // float4 offsets of the layers' fragments
   int kb_rwd2;            // k-blocks of the reward head's outputs: 3 (33 bins) or 1
   size_t stride;
 };
-struct MzhPgradParams {
-  int B, n;
-  int in_dim, kin;
-  const int32_t* env_index;     // [n] nullable
-  const float* obs;             // [B][in_dim]
+struct MzhPgradParams : MzhRowParams {
   const int32_t* action;        // [B]
   const int32_t* policy_logit;  // [B] nullable
   float* delta1;                // [B][5][256]
@@ -363,7 +367,7 @@ struct MzhPgradParams {
   float* reward;                // [B] nullable
   float* objective;             // [B][5] nullable
   float* grad;                  // [n][n_floats] nullable
-  int32_t* err_count;           // nullable
+  int32_t* err_count;           // nullable: += 1 per skipped row
 };
 size_t mzh_pgrad_smem_bytes(int R);
 // the gather that fills a network's (M networks') MzhPackedG buffer from the main blob(s): dst[m][j] =
@@ -374,24 +378,18 @@ hipError_t mzh_launch_pgrad_gather(const int32_t* map, int n, const float* src, 
 hipError_t mzh_launch_pgrad(int R, const MzhNet& net, const MzhSalNetT& nt, const MzhPgNetT& gt, const MzhPgradParams& p,
                             int support, const MzhMultiParams* mp, hipStream_t stream);
 
-// mzh_probe_actions (mzh_probe_kernel / mzh_probe_multi_kernel, mzh_search.hip): row j of the call is env
-// env_index[j] (or j) of a batch of B; every array but env_index (and a set's net_index) is indexed by env
-struct MzhProbeParams {
-  int B, n;         // envs of the batch, rows of the call
-  int in_dim, kin;  // observation width 3N and its zero-padded width (16 * rep0.kb)
-  int n_disks;
-  const int32_t* env_index;  // [n] nullable
-  const float* obs;          // [B][in_dim]
-  const uint8_t* state;      // [B][n_disks] nullable
-  float* reward;             // [B][6]
-  float* value;              // [B][6]
-  uint8_t* legal;            // [B] nullable
-  float* h0;                 // [B][64] nullable
-  float* pi0;                // [B][6] nullable
-  float* value0;             // [B] nullable
-  float* h1;                 // [B][6][64] nullable
-  float* pi1;                // [B][6][6] nullable
-  int32_t* err_count;        // nullable
+// mzh_probe_actions (mzh_probe_kernel / mzh_probe_multi_kernel, mzh_search.hip): rows as in MzhRowParams
+struct MzhProbeParams : MzhRowParams {
+  const uint8_t* state;  // [B][n_disks] nullable
+  float* reward;         // [B][6]
+  float* value;          // [B][6]
+  uint8_t* legal;        // [B] nullable
+  float* h0;             // [B][64] nullable
+  float* pi0;            // [B][6] nullable
+  float* value0;         // [B] nullable
+  float* h1;             // [B][6][64] nullable
+  float* pi1;            // [B][6][6] nullable
+  int32_t* err_count;    // nullable: += 1 per skipped row
 };
 size_t mzh_probe_smem_bytes(int R);
 // mp == nullptr: mzh_probe_kernel<R> on ceil(n / R) workgroups; else the tile table of the n rows, then

@@ -25,8 +25,7 @@
 // from the saliency kernel's transposed blob, dyn2 / rwd2 from the engine's MzhPackedG buffer.  Rows never mix
 // in an MFMA, so a row's outputs are the same bits in any position and at either R.
 #include "mzh_backward.h"
-#include "mzh_device.h"
-#include "mzh_internal.h"
+#include "mzh_rows.h"
 
 #define MZH_PG_NETS 5
 
@@ -83,40 +82,24 @@ __device__ __forceinline__ void mzh_pgrad_body(const MzhNet& net, const MzhSalNe
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r16 = lane & 15, g = lane >> 4;
-  const int row0 = tile.template root0<R>();
-  const int nvalid = tile.template nvalid<R>(p.n, row0);
-  if (tid < R) {
-    int e = -1, li = -1, a = 0;
-    if (tid < nvalid) {
-      e = p.env_index ? p.env_index[row0 + tid] : row0 + tid;
-      bool ok = (unsigned)e < (unsigned)p.B;
-      if (ok) {
-        a = p.action[e];
-        ok = (unsigned)a < (unsigned)MZH_A;
-      }
-      if (ok && p.policy_logit) {
-        li = p.policy_logit[e];
-        ok = li >= -1 && li < MZH_A;
-      }
-      if (!ok) {
-        if (p.err_count) atomicAdd(p.err_count, 1);
-        e = -1;
-        li = -1;
-        a = 0;
-      }
+  int li = -1, a = 0;
+  mzh_rows_fill<R>(sm.env, p, p.err_count, tile, [&](int e) {  // an action outside [0, 6) or a policy_logit outside [-1, 6) skips its row
+    a = p.action[e];
+    bool ok = (unsigned)a < (unsigned)MZH_A;
+    if (ok && p.policy_logit) {
+      li = p.policy_logit[e];
+      ok = li >= -1 && li < MZH_A;
     }
-    sm.env[tid] = e;
+    if (!ok) {
+      li = -1;
+      a = 0;
+    }
+    return ok;
+  }, [&]() {
     sm.pick[tid] = li;
     sm.act[tid] = a;
-  }
-  __syncthreads();
-  auto load_obs = [&]() {
-    for (int i = tid; i < R * p.kin; i += MZH_THREADS) {
-      const int r = i / p.kin, k = i - r * p.kin;
-      const int e = sm.env[r];
-      sm.x[r * MZH_LD64 + mzh_kpos(k)] = (e >= 0 && k < p.in_dim) ? p.obs[(size_t)e * p.in_dim + k] : 0.0f;
-    }
-  };
+  });
+  auto load_obs = [&]() { mzh_rows_load_obs<R>(sm.x, sm.env, p); };
   // a hidden tile (k-block order) as net `ni`'s [256] of `out` ([B][5][256])
   auto store256 = [&](float* out, int ni, const float* t) {
     for (int i = tid; i < R * MZH_F; i += MZH_THREADS) {
@@ -133,7 +116,8 @@ __device__ __forceinline__ void mzh_pgrad_body(const MzhNet& net, const MzhSalNe
       if (e >= 0) p.delta2[((size_t)e * MZH_PG_NETS + ni) * MZH_H + k] = k < ncols ? s[r * ld + mzh_kpos(k)] : 0.0f;
     }
   };
-  // a [R][68] latent buffer (k-block order) as [B][64]
+  // a [R][68] latent buffer (k-block order) as [B][64] (mzh_rows_store_latent's loop, kept as this kernel's own:
+  // through the helper its code grows by 18 - 38 instructions)
   auto store64 = [&](float* out, const float* s) {
     for (int i = tid; i < R * MZH_H; i += MZH_THREADS) {
       const int r = i >> 6, k = i & 63;
@@ -174,14 +158,7 @@ __device__ __forceinline__ void mzh_pgrad_body(const MzhNet& net, const MzhSalNe
     sm.h0s[r * MZH_LD64 + k] = sm.x[r * MZH_LD64 + k];
   }
   store64(p.h0, sm.x);
-  if (tid < R * 8) {
-    const int r = tid >> 3, c = tid & 7;
-    const int e = sm.env[r];
-    if (e >= 0) {
-      if (p.pi0 && c < MZH_A) p.pi0[(size_t)e * MZH_A + c] = sm.pi[r * 8 + c];
-      if (p.value0 && c == 6) p.value0[e] = sm.value[r];
-    }
-  }
+  mzh_rows_store_root<R>(ms, sm.env, p.pi0, p.value0);
   store256(p.act, 3, sm.hidP);
   store256(p.act, 4, sm.hidV);
   float* seedP = sm.lrwd;  // [R][MZH_LDSUP]: 16 columns used (the initial MLP leaves lrwd alone)
@@ -209,12 +186,7 @@ __device__ __forceinline__ void mzh_pgrad_body(const MzhNet& net, const MzhSalNe
     objective(row, 3, obj);
   } else if (tid >= 64 && tid < 64 + R) {  // another wave: the value seeds
     const int row = tid - 64;
-    float* seed = sm.seedV + row * MZH_LDSEED;
-    if (net.support == 33) {
-      sal_value_seed33(sm.lval + row * MZH_LDSUP, seed);
-    } else {
-      for (int i = 0; i < 16; ++i) seed[i] = i == 0 ? 1.0f : 0.0f;
-    }
+    sal_head_seed(net.support, sm.lval + row * MZH_LDSUP, sm.seedV + row * MZH_LDSEED);
     objective(row, 4, sm.value[row]);
   } else if (tid >= 128 && tid < 128 + R) {  // a third: the representation's
     const int row = tid - 128;
@@ -263,12 +235,7 @@ __device__ __forceinline__ void mzh_pgrad_body(const MzhNet& net, const MzhSalNe
   float* G1 = sm.hidV;  // [R][MZH_LD64]: the dynamics' seed (the next state's value hidden tile is not needed)
   if (tid < R) {  // the reward seeds
     const int row = tid;
-    float* seed = sm.seedV + row * MZH_LDSEED;
-    if (net.support == 33) {
-      sal_value_seed33(sm.lrwd + row * MZH_LDSUP, seed);
-    } else {
-      for (int i = 0; i < 16; ++i) seed[i] = i == 0 ? 1.0f : 0.0f;
-    }
+    sal_head_seed(net.support, sm.lrwd + row * MZH_LDSUP, sm.seedV + row * MZH_LDSEED);
     objective(row, 2, sm.reward[row]);
   } else if (tid >= 64 && tid < 64 + R) {
     const int row = tid - 64;
@@ -309,18 +276,13 @@ __global__ __launch_bounds__(MZH_THREADS, 1) void mzh_pgrad_kernel(MzhNet net, M
   mzh_pgrad_body<R>(net, nt, nt.base, gt, gt.base, p);
 }
 
-// Rows of several networks (a set, mzh_load_weight_set): workgroup t takes tile t of the table
-// mzh_multi_tiles_kernel made of this call's net_index; one at or above the tile count returns before its
-// first barrier (a refused net_index leaves the count 0: nothing is written)
+// rows of several networks (mzh_rows_multi_tile)
 template <int R>
 __global__ __launch_bounds__(MZH_THREADS, 1) void mzh_pgrad_multi_kernel(MzhNet net, MzhSalNetT nt, MzhPgNetT gt,
                                                                          MzhPgradParams p, MzhMultiParams mp) {
-  if ((int)blockIdx.x >= *mp.ntiles) return;
-  const MzhTableTile t{mp.tiles[blockIdx.x]};
-  mzh_net_select(net, mp, t.t.net, net.support == 33);
-  const float4* T = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(nt.base) + (size_t)t.t.net * nt.stride);
-  const float4* GT = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(gt.base) + (size_t)t.t.net * gt.stride);
-  mzh_pgrad_body<R>(net, nt, T, gt, GT, p, t);
+  if (mzh_rows_no_tile(mp)) return;
+  const MzhTableTile t = mzh_rows_multi_tile(net, mp);
+  mzh_pgrad_body<R>(net, nt, mzh_net_ptr(nt.base, t.t.net, nt.stride), gt, mzh_net_ptr(gt.base, t.t.net, gt.stride), p, t);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -457,28 +419,12 @@ template <int R>
 static size_t pgrad_smem_bytes() { return (sizeof(PgSmem<R>) + 15) & ~(size_t)15; }
 size_t mzh_pgrad_smem_bytes(int R) { return R == 32 ? pgrad_smem_bytes<32>() : pgrad_smem_bytes<16>(); }
 
-template <int R>
-static hipError_t launch_pgrad_t(const MzhNet& net, const MzhSalNetT& nt, const MzhPgNetT& gt, const MzhPgradParams& p,
-                                 const MzhMultiParams* mp, hipStream_t stream) {
-  const size_t smem = pgrad_smem_bytes<R>();
-  const void* fn = mp ? reinterpret_cast<const void*>(&mzh_pgrad_multi_kernel<R>)
-                      : reinterpret_cast<const void*>(&mzh_pgrad_kernel<R>);
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  if (e != hipSuccess) return e;
-  if (!mp) {
-    hipLaunchKernelGGL((mzh_pgrad_kernel<R>), dim3((p.n + R - 1) / R), dim3(MZH_THREADS), smem, stream, net, nt, gt, p);
-    return hipGetLastError();
-  }
-  e = mzh_launch_multi_tiles(*mp, p.n, R, stream);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((mzh_pgrad_multi_kernel<R>), dim3(mzh_multi_max_tiles(p.n, R, mp->M)), dim3(MZH_THREADS), smem, stream,
-                     net, nt, gt, p, *mp);
-  return hipGetLastError();
-}
-
 hipError_t mzh_launch_pgrad(int R, const MzhNet& net, const MzhSalNetT& nt, const MzhPgNetT& gt, const MzhPgradParams& p,
                             int support, const MzhMultiParams* mp, hipStream_t stream) {
-  hipError_t e = R == 32 ? launch_pgrad_t<32>(net, nt, gt, p, mp, stream) : launch_pgrad_t<16>(net, nt, gt, p, mp, stream);
+  hipError_t e = R == 32 ? mzh_rows_launch(&mzh_pgrad_multi_kernel<32>, &mzh_pgrad_kernel<32>, 32, pgrad_smem_bytes<32>(), p.n,
+                                           mp, stream, net, nt, gt, p)
+                         : mzh_rows_launch(&mzh_pgrad_multi_kernel<16>, &mzh_pgrad_kernel<16>, 16, pgrad_smem_bytes<16>(), p.n,
+                                           mp, stream, net, nt, gt, p);
   if (e != hipSuccess || !p.grad) return e;
   const int n_floats = (int)mzh_canon_view(nullptr, p.in_dim, support).total;
   hipLaunchKernelGGL(mzh_pgrad_expand_kernel, dim3((unsigned)p.n * MZH_PGX_CHUNKS), dim3(MZH_PGX_THREADS), 0, stream, p, support,

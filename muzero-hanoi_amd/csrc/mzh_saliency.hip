@@ -22,9 +22,8 @@
 //   rep 0   DX    <- hidV . rep0 | hidP . rep0       (DX = hidR as [2R][68], natural column order)
 // There is no bit contract on the backward's summation order; a row's outputs depend on that row and its
 // network alone (rows never mix in an MFMA), so they are the same bits in any position and at either R.
-#include "mzh_backward.h"  // sal_mma, sal_zero, sal_value_seed33, MZH_LDSEED
-#include "mzh_device.h"
-#include "mzh_internal.h"
+#include "mzh_backward.h"
+#include "mzh_rows.h"
 
 template <int R>
 struct SalSmem : MlpSmem<R> {
@@ -42,55 +41,24 @@ __device__ __forceinline__ void mzh_saliency_body(const MzhNet& net, const MzhSa
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r16 = lane & 15, g = lane >> 4;
-  const int row0 = tile.template root0<R>();
-  const int nvalid = tile.template nvalid<R>(p.n, row0);
-  if (tid < R) {
-    int e = -1, li = -1;
-    if (tid < nvalid) {
-      e = p.env_index ? p.env_index[row0 + tid] : row0 + tid;
-      if ((unsigned)e >= (unsigned)p.B) {
-        if (p.err_count) atomicAdd(p.err_count, 1);
-        e = -1;
-      } else if (p.logit_index) {
-        li = p.logit_index[e];
-        if (li < -1 || li >= MZH_A) {
-          if (p.err_count) atomicAdd(p.err_count, 1);
-          e = -1;
-          li = -1;
-        }
-      }
+  int li = -1;
+  mzh_rows_fill<R>(sm.env, p, p.err_count, tile, [&](int e) {  // a logit_index outside [-1, 6) skips its row
+    if (!p.logit_index) return true;
+    li = p.logit_index[e];
+    if (li < -1 || li >= MZH_A) {
+      li = -1;
+      return false;
     }
-    sm.env[tid] = e;
-    sm.pick[tid] = li;
-  }
-  __syncthreads();
-  auto load_obs = [&]() {
-    for (int i = tid; i < R * p.kin; i += MZH_THREADS) {
-      const int r = i / p.kin, k = i - r * p.kin;
-      const int e = sm.env[r];
-      sm.x[r * MZH_LD64 + mzh_kpos(k)] = (e >= 0 && k < p.in_dim) ? p.obs[(size_t)e * p.in_dim + k] : 0.0f;
-    }
-  };
-  load_obs();
+    return true;
+  }, [&]() { sm.pick[tid] = li; });
+  mzh_rows_load_obs<R>(sm.x, sm.env, p);
   __syncthreads();
   MlpSmem<R>& ms = sm;  // the MLP block the inference kernels run on
   mzh_mlp_initial<R>(ms, net, wave, lane);
 
   // ---- the forward's outputs, and the heads' seeds (lrwd is unused by the initial MLP) ----
-  if (p.h0)
-    for (int i = tid; i < R * MZH_H; i += MZH_THREADS) {
-      const int r = i >> 6, k = i & 63;
-      const int e = sm.env[r];
-      if (e >= 0) p.h0[(size_t)e * MZH_H + mzh_kpos(k)] = sm.x[r * MZH_LD64 + k];
-    }
-  if (tid < R * 8) {
-    const int r = tid >> 3, c = tid & 7;
-    const int e = sm.env[r];
-    if (e >= 0) {
-      if (p.pi0 && c < MZH_A) p.pi0[(size_t)e * MZH_A + c] = sm.pi[r * 8 + c];
-      if (p.value0 && c == 6) p.value0[e] = sm.value[r];
-    }
-  }
+  if (p.h0) mzh_rows_store_latent<R>(p.h0, sm.x, sm.env);
+  mzh_rows_store_root<R>(ms, sm.env, p.pi0, p.value0);
   float* seedP = sm.lrwd;  // [R][MZH_LDSUP]: 16 columns used
   if (tid < R) {
     const int row = tid;
@@ -109,16 +77,14 @@ __device__ __forceinline__ void mzh_saliency_body(const MzhNet& net, const MzhSa
     for (int i = 0; i < 16; ++i) seedP[row * MZH_LDSUP + mzh_kpos(i)] = i == k ? 1.0f : 0.0f;
   } else if (tid >= 64 && tid < 64 + R) {  // another wave: the value seeds
     const int row = tid - 64;
-    float* seed = sm.seedV + row * MZH_LDSEED;
-    if (net.support == 33) {
-      sal_value_seed33(sm.lval + row * MZH_LDSUP, seed);
-    } else {
-      for (int i = 0; i < 16; ++i) seed[i] = i == 0 ? 1.0f : 0.0f;
-    }
+    sal_head_seed(net.support, sm.lval + row * MZH_LDSUP, sm.seedV + row * MZH_LDSEED);
   }
   __syncthreads();
 
-  // ---- head layer 2 transposed, the ReLU masks of hidP / hidV (in place: a lane reads the element it writes) ----
+  // ---- head layer 2 transposed, the ReLU masks of hidP / hidV (in place: a lane reads the element it writes).  This
+  // step, the normalisation's backward and rep0's hidden tile below are this kernel's own text although mzh_backward.h
+  // has each of them for mzh_pgrad.hip: through the shared forms the 65,536-row call measured 0.3 - 0.5% slower
+  // (profiles/rows_refactor_experiments.json) ----
   for (int q = 0; q < 4; ++q) {
     const int t = wave * 4 + q;
     const int pos = t * 16 + 4 * (r16 & 3) + (r16 >> 2);
@@ -161,11 +127,9 @@ __device__ __forceinline__ void mzh_saliency_body(const MzhNet& net, const MzhSa
   }
   __syncthreads();
 
-  // ---- normalize_h_state's backward (networks.py:191-196; D = max - min + 1e-8), one thread per gradient row:
-  // every element g_i / D, the arg-max element - sum g_i (h_i - min) / D^2, the arg-min element
-  // - sum g_i / D + sum g_i (h_i - min) / D^2; arg-min / arg-max: the lowest unit index holding the forward's
-  // min / max.  The observations come back into sm.x beside it (nothing reads the normalised latent any more).
-  load_obs();
+  // ---- normalize_h_state's backward, one thread per gradient row; the observations come back into sm.x beside
+  // it (nothing reads the normalised latent any more) ----
+  mzh_rows_load_obs<R>(sm.x, sm.env, p);
   if (tid < 2 * R) {
     float* gr = G + tid * MZH_LD64;
     const float* h = sm.hraw + (tid < R ? tid : tid - R) * MZH_LD64;
@@ -265,43 +229,24 @@ __global__ __launch_bounds__(MZH_THREADS, 1) void mzh_saliency_kernel(MzhNet net
   mzh_saliency_body<R>(net, nt, nt.base, p);
 }
 
-// Rows of several networks (a set, mzh_load_weight_set): workgroup t takes tile t of the table
-// mzh_multi_tiles_kernel made of this call's net_index; one at or above the tile count returns before its
-// first barrier (a refused net_index leaves the count 0: nothing is written)
+// rows of several networks (mzh_rows_multi_tile)
 template <int R>
 __global__ __launch_bounds__(MZH_THREADS, 1) void mzh_saliency_multi_kernel(MzhNet net, MzhSalNetT nt, MzhSalParams p,
                                                                             MzhMultiParams mp) {
-  if ((int)blockIdx.x >= *mp.ntiles) return;
-  const MzhTableTile t{mp.tiles[blockIdx.x]};
-  mzh_net_select(net, mp, t.t.net, net.support == 33);
-  const float4* T = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(nt.base) + (size_t)t.t.net * nt.stride);
-  mzh_saliency_body<R>(net, nt, T, p, t);
+  if (mzh_rows_no_tile(mp)) return;
+  const MzhTableTile t = mzh_rows_multi_tile(net, mp);
+  mzh_saliency_body<R>(net, nt, mzh_net_ptr(nt.base, t.t.net, nt.stride), p, t);
 }
 
 template <int R>
 static size_t saliency_smem_bytes() { return (sizeof(SalSmem<R>) + 15) & ~(size_t)15; }
 size_t mzh_saliency_smem_bytes(int R) { return R == 32 ? saliency_smem_bytes<32>() : saliency_smem_bytes<16>(); }
 
-template <int R>
-static hipError_t launch_saliency_t(const MzhNet& net, const MzhSalNetT& nt, const MzhSalParams& p, const MzhMultiParams* mp,
-                                    hipStream_t stream) {
-  const size_t smem = saliency_smem_bytes<R>();
-  const void* fn = mp ? reinterpret_cast<const void*>(&mzh_saliency_multi_kernel<R>)
-                      : reinterpret_cast<const void*>(&mzh_saliency_kernel<R>);
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  if (e != hipSuccess) return e;
-  if (!mp) {
-    hipLaunchKernelGGL((mzh_saliency_kernel<R>), dim3((p.n + R - 1) / R), dim3(MZH_THREADS), smem, stream, net, nt, p);
-    return hipGetLastError();
-  }
-  e = mzh_launch_multi_tiles(*mp, p.n, R, stream);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((mzh_saliency_multi_kernel<R>), dim3(mzh_multi_max_tiles(p.n, R, mp->M)), dim3(MZH_THREADS), smem,
-                     stream, net, nt, p, *mp);
-  return hipGetLastError();
-}
-
 hipError_t mzh_launch_saliency(int R, const MzhNet& net, const MzhSalNetT& nt, const MzhSalParams& p,
                                const MzhMultiParams* mp, hipStream_t stream) {
-  return R == 32 ? launch_saliency_t<32>(net, nt, p, mp, stream) : launch_saliency_t<16>(net, nt, p, mp, stream);
+  if (R == 32)
+    return mzh_rows_launch(&mzh_saliency_multi_kernel<32>, &mzh_saliency_kernel<32>, 32, saliency_smem_bytes<32>(), p.n, mp,
+                           stream, net, nt, p);
+  return mzh_rows_launch(&mzh_saliency_multi_kernel<16>, &mzh_saliency_kernel<16>, 16, saliency_smem_bytes<16>(), p.n, mp,
+                         stream, net, nt, p);
 }

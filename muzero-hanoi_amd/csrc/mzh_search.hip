@@ -12,6 +12,7 @@
 #include "mzh_device.h"
 #include "mzh_env_kernels.h"
 #include "mzh_internal.h"
+#include "mzh_rows.h"
 #include "mzh_tree.h"
 
 // One workgroup per CU (all 512 registers per lane): the next simulation's first weight chunks stay
@@ -384,29 +385,13 @@ __device__ __forceinline__ void mzh_probe_body(const MzhNet& net, const MzhProbe
   extern __shared__ __align__(16) unsigned char smem_raw[];
   ProbeSmem<R>& sm = *reinterpret_cast<ProbeSmem<R>*>(smem_raw);
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int row0 = tile.template root0<R>();
-  const int nvalid = tile.template nvalid<R>(p.n, row0);
-  if (tid < R) {
-    int e = -1;
-    if (tid < nvalid) {
-      e = p.env_index ? p.env_index[row0 + tid] : row0 + tid;
-      if ((unsigned)e >= (unsigned)p.B) {
-        if (p.err_count) atomicAdd(p.err_count, 1);
-        e = -1;
-      }
-    }
-    sm.env[tid] = e;
-  }
-  __syncthreads();
-  for (int i = tid; i < R * p.kin; i += MZH_THREADS) {
-    const int r = i / p.kin, k = i - r * p.kin;
-    const int e = sm.env[r];
-    sm.x[r * MZH_LD64 + mzh_kpos(k)] = (e >= 0 && k < p.in_dim) ? p.obs[(size_t)e * p.in_dim + k] : 0.0f;
-  }
+  mzh_rows_fill<R>(sm.env, p, p.err_count, tile);
+  mzh_rows_load_obs<R>(sm.x, sm.env, p);
   __syncthreads();
   MlpSmem<R>& ms = sm;  // the MLP block the inference kernels run on
   mzh_mlp_initial<R>(ms, net, wave, lane);
-  // the root: position k of a row of sm.x holds unit mzh_kpos(k) (an involution)
+  // the root, its latent kept for the six lookaheads in the same pass as its store (mzh_rows_store_latent's
+  // mapping), and legal on the root store's spare thread
   for (int i = tid; i < R * MZH_H; i += MZH_THREADS) {
     const int r = i >> 6, k = i & 63;
     const int e = sm.env[r];
@@ -457,14 +442,11 @@ __global__ __launch_bounds__(MZH_THREADS, 1) void mzh_probe_kernel(MzhNet net, M
   mzh_probe_body<R>(net, p);
 }
 
-// Rows of several networks (a set, mzh_load_weight_set): workgroup t probes tile t of the table
-// mzh_multi_tiles_kernel made of this call's net_index; one at or above the tile count returns before its
-// first barrier (a refused net_index leaves the count 0: nothing is written)
+// rows of several networks (mzh_rows_multi_tile)
 template <int R>
 __global__ __launch_bounds__(MZH_THREADS, 1) void mzh_probe_multi_kernel(MzhNet net, MzhProbeParams p, MzhMultiParams mp) {
-  if ((int)blockIdx.x >= *mp.ntiles) return;
-  const MzhTableTile t{mp.tiles[blockIdx.x]};
-  mzh_net_select(net, mp, t.t.net, net.support == 33);
+  if (mzh_rows_no_tile(mp)) return;
+  const MzhTableTile t = mzh_rows_multi_tile(net, mp);
   mzh_probe_body<R>(net, p, t);
 }
 
@@ -545,8 +527,7 @@ static hipError_t launch_multi_t(int grid, const MzhNet& net, const MzhSearchPar
   const void* fn = reinterpret_cast<const void*>(&mzh_search_multi_kernel<R, OHL, SUP33>);
   hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(mzh_multi_tiles_kernel, dim3(1), dim3(MZH_MULTI_MAX_NETS), 0, stream, mp, p.B, R);
-  e = hipGetLastError();
+  e = mzh_launch_multi_tiles(mp, p.B, R, stream);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL((mzh_search_multi_kernel<R, OHL, SUP33>), dim3(grid), dim3(MZH_THREADS), smem, stream, net, p, mp);
   return hipGetLastError();
@@ -598,25 +579,6 @@ template <int R>
 static size_t probe_smem_bytes() { return (sizeof(ProbeSmem<R>) + 15) & ~(size_t)15; }
 size_t mzh_probe_smem_bytes(int R) { return R == 32 ? probe_smem_bytes<32>() : probe_smem_bytes<16>(); }
 
-template <int R>
-static hipError_t launch_probe_t(const MzhNet& net, const MzhProbeParams& p, const MzhMultiParams* mp, hipStream_t stream) {
-  const size_t smem = probe_smem_bytes<R>();
-  const void* fn = mp ? reinterpret_cast<const void*>(&mzh_probe_multi_kernel<R>)
-                      : reinterpret_cast<const void*>(&mzh_probe_kernel<R>);
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  if (e != hipSuccess) return e;
-  if (!mp) {
-    hipLaunchKernelGGL((mzh_probe_kernel<R>), dim3((p.n + R - 1) / R), dim3(MZH_THREADS), smem, stream, net, p);
-    return hipGetLastError();
-  }
-  hipLaunchKernelGGL(mzh_multi_tiles_kernel, dim3(1), dim3(MZH_MULTI_MAX_NETS), 0, stream, *mp, p.n, R);
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((mzh_probe_multi_kernel<R>), dim3(mzh_multi_max_tiles(p.n, R, mp->M)), dim3(MZH_THREADS), smem, stream,
-                     net, p, *mp);
-  return hipGetLastError();
-}
-
 // the tile table of n rows at R rows per tile (the prologue of every multi-network launch)
 hipError_t mzh_launch_multi_tiles(const MzhMultiParams& mp, int n, int R, hipStream_t stream) {
   hipLaunchKernelGGL(mzh_multi_tiles_kernel, dim3(1), dim3(MZH_MULTI_MAX_NETS), 0, stream, mp, n, R);
@@ -624,5 +586,7 @@ hipError_t mzh_launch_multi_tiles(const MzhMultiParams& mp, int n, int R, hipStr
 }
 
 hipError_t mzh_launch_probe(int R, const MzhNet& net, const MzhProbeParams& p, const MzhMultiParams* mp, hipStream_t stream) {
-  return R == 32 ? launch_probe_t<32>(net, p, mp, stream) : launch_probe_t<16>(net, p, mp, stream);
+  if (R == 32)
+    return mzh_rows_launch(&mzh_probe_multi_kernel<32>, &mzh_probe_kernel<32>, 32, probe_smem_bytes<32>(), p.n, mp, stream, net, p);
+  return mzh_rows_launch(&mzh_probe_multi_kernel<16>, &mzh_probe_kernel<16>, 16, probe_smem_bytes<16>(), p.n, mp, stream, net, p);
 }

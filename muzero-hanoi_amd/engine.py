@@ -202,6 +202,43 @@ class Engine:
                                                  self._stream()), "mzh_recurrent_inference")
         return out
 
+    def _rows_call(self, who, args, inputs, outputs, tile, err, net_index, out):
+        """what probe_actions, saliency and param_grads share.  args: the call's _lib structure.  inputs: (field,
+        tensor or None, dtype, shape) in the order checked, "obs" first; outputs: (key of `out`, field, dtype, shape,
+        allocate when missing).  A shape's "B" is obs's rows, its "n" env_index's (B without it).  Checks every given
+        tensor, allocates, fills args (and with net_index a MultiArgs and out["_status"]) and calls mzh_<who>."""
+        dev = self.device
+        given = {f: t for f, t, _, _ in inputs}
+        dims = {"B": int(given["obs"].shape[0])}
+        dims["n"] = dims["B"] if given.get("env_index") is None else int(given["env_index"].shape[0])
+        inputs = list(inputs) + [("net_index", net_index, torch.int32, ("n",))]
+        checks = [(f, t, dt, shp) for f, t, dt, shp in inputs if t is not None]
+        out = dict(out) if out is not None else {}
+        for k, _, dt, shp, allocate in outputs:
+            if k not in out and allocate:
+                out[k] = torch.empty(tuple(dims.get(d, d) for d in shp), dtype=dt, device=dev)
+            if k in out:
+                checks.append((k, out[k], dt, shp))
+        for name, t, dt, shp in checks:
+            shp = tuple(dims.get(d, d) for d in shp)
+            if t.dtype != dt or tuple(t.shape) != shp or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"{who}: {name} must be a contiguous {dt} {shp} tensor on {dev}")
+        args.B, args.n, args.flags, args.err_count = dims["B"], dims["n"], search_flags(None, tile), ptr(err)
+        for f, t, _, _ in inputs[:-1]:
+            setattr(args, f, ptr(t))
+        for k, f, _, _, _ in outputs:
+            setattr(args, f, ptr(out.get(k)))
+        m = None
+        if net_index is not None:
+            if getattr(self, "set_size", 0) < 1:
+                raise RuntimeError(f"{who}: no weight set loaded (load_weight_set)")
+            out["_status"] = torch.zeros(2, dtype=torch.int32, device=dev)
+            m = _lib.MultiArgs()
+            m.n_networks, m.net_index, m.status = self.set_size, ptr(net_index), ptr(out["_status"])
+        check(getattr(_lib.lib(), "mzh_" + who)(self._h, ctypes.byref(args), None if m is None else ctypes.byref(m),
+                                                self._stream()), "mzh_" + who)
+        return out
+
     def probe_actions(self, obs, *, env_index=None, state=None, net_index=None, out=None, full=False, tile=None,
                       err=None):
         """mzh_probe_actions: for every row the six one-step lookaheads recurrent_inference(represent(obs), a),
@@ -213,48 +250,17 @@ class Engine:
         them any of h0 [B, 64], pi0 [B, 6], value0 [B], h1 [B, 6, 64], pi1 [B, 6, 6]); missing reward / value
         (and legal with state) are allocated, the others only with full=True.  tile = None | 16 | 32.
         Returns the dict; with net_index, "_status" is the device's [2] int32 verdict as in search_multi."""
-        dev = self.device
-        B = int(obs.shape[0])
-        checks = [("obs", obs, torch.float32, (B, 3 * self.n_disks))]
-        n = B
-        if env_index is not None:
-            n = int(env_index.shape[0])
-            checks.append(("env_index", env_index, torch.int32, (n,)))
-        if state is not None:
-            checks.append(("state", state, torch.uint8, (B, self.n_disks)))
-        if net_index is not None:
-            checks.append(("net_index", net_index, torch.int32, (n,)))
-        out = dict(out) if out is not None else {}
-        shapes = dict(reward=(B, ACTIONS), value=(B, ACTIONS), h0=(B, LATENT), pi0=(B, ACTIONS), value0=(B,),
-                      h1=(B, ACTIONS, LATENT), pi1=(B, ACTIONS, ACTIONS))
-        for k, shp in shapes.items():
-            if k not in out and (full or k in ("reward", "value")):
-                out[k] = torch.empty(shp, dtype=torch.float32, device=dev)
-            if k in out:
-                checks.append((k, out[k], torch.float32, shp))
-        if state is not None and "legal" not in out:
-            out["legal"] = torch.empty(B, dtype=torch.uint8, device=dev)
-        if "legal" in out:
-            checks.append(("legal", out["legal"], torch.uint8, (B,)))
-        for name, t, dt, shp in checks:
-            if t.dtype != dt or tuple(t.shape) != shp or not t.is_contiguous() or t.device != dev:
-                raise ValueError(f"probe_actions: {name} must be a contiguous {dt} {shp} tensor on {dev}")
-        a = _lib.ProbeArgs()
-        a.B, a.n, a.flags = B, n, search_flags(None, tile)
-        for k, t in (("env_index", env_index), ("obs", obs), ("state", state), ("err_count", err)):
-            setattr(a, k, ptr(t))
-        for k in ("reward", "value", "legal", "h0", "pi0", "value0", "h1", "pi1"):
-            setattr(a, k, ptr(out.get(k)))
-        m = None
-        if net_index is not None:
-            if getattr(self, "set_size", 0) < 1:
-                raise RuntimeError("probe_actions: no weight set loaded (load_weight_set)")
-            out["_status"] = torch.zeros(2, dtype=torch.int32, device=dev)
-            m = _lib.MultiArgs()
-            m.n_networks, m.net_index, m.status = self.set_size, ptr(net_index), ptr(out["_status"])
-        check(_lib.lib().mzh_probe_actions(self._h, ctypes.byref(a), None if m is None else ctypes.byref(m),
-                                           self._stream()), "mzh_probe_actions")
-        return out
+        f32, N = torch.float32, self.n_disks
+        return self._rows_call(
+            "probe_actions", _lib.ProbeArgs(),
+            [("obs", obs, f32, ("B", 3 * N)), ("env_index", env_index, torch.int32, ("n",)),
+             ("state", state, torch.uint8, ("B", N))],
+            [("reward", "reward", f32, ("B", ACTIONS), True), ("value", "value", f32, ("B", ACTIONS), True),
+             ("h0", "h0", f32, ("B", LATENT), full), ("pi0", "pi0", f32, ("B", ACTIONS), full),
+             ("value0", "value0", f32, ("B",), full), ("h1", "h1", f32, ("B", ACTIONS, LATENT), full),
+             ("pi1", "pi1", f32, ("B", ACTIONS, ACTIONS), full),
+             ("legal", "legal", torch.uint8, ("B",), state is not None)],
+            tile, err, net_index, out)
 
     def saliency(self, obs, *, env_index=None, net_index=None, logit_index=None, out=None, full=False, tile=None,
                  err=None):
@@ -268,50 +274,16 @@ class Engine:
         value0 [B]); missing policy / value are allocated, the others only with full=True.  tile = None | 16 | 32.
         err: [1] int32, += 1 per skipped row.  Returns the dict; with net_index, "_status" is the device's [2]
         int32 verdict as in search_multi."""
-        dev = self.device
-        B = int(obs.shape[0])
-        N = self.n_disks
-        checks = [("obs", obs, torch.float32, (B, 3 * N))]
-        n = B
-        if env_index is not None:
-            n = int(env_index.shape[0])
-            checks.append(("env_index", env_index, torch.int32, (n,)))
-        if logit_index is not None:
-            checks.append(("logit_index", logit_index, torch.int32, (B,)))
-        if net_index is not None:
-            checks.append(("net_index", net_index, torch.int32, (n,)))
-        out = dict(out) if out is not None else {}
-        shapes = dict(policy=(B, 3 * N), value=(B, 3 * N), disc_policy=(B, N), disc_value=(B, N), h0=(B, LATENT),
-                      pi0=(B, ACTIONS), value0=(B,))
-        for k, shp in shapes.items():
-            if k not in out and (full or k in ("policy", "value")):
-                out[k] = torch.empty(shp, dtype=torch.float32, device=dev)
-            if k in out:
-                checks.append((k, out[k], torch.float32, shp))
-        if full and "picked" not in out:
-            out["picked"] = torch.empty(B, dtype=torch.int32, device=dev)
-        if "picked" in out:
-            checks.append(("picked", out["picked"], torch.int32, (B,)))
-        for name, t, dt, shp in checks:
-            if t.dtype != dt or tuple(t.shape) != shp or not t.is_contiguous() or t.device != dev:
-                raise ValueError(f"saliency: {name} must be a contiguous {dt} {shp} tensor on {dev}")
-        a = _lib.SaliencyArgs()
-        a.B, a.n, a.flags = B, n, search_flags(None, tile)
-        for k, t in (("env_index", env_index), ("obs", obs), ("logit_index", logit_index), ("err_count", err)):
-            setattr(a, k, ptr(t))
-        a.sal_policy, a.sal_value = ptr(out["policy"]), ptr(out["value"])
-        for k in ("picked", "disc_policy", "disc_value", "h0", "pi0", "value0"):
-            setattr(a, k, ptr(out.get(k)))
-        m = None
-        if net_index is not None:
-            if getattr(self, "set_size", 0) < 1:
-                raise RuntimeError("saliency: no weight set loaded (load_weight_set)")
-            out["_status"] = torch.zeros(2, dtype=torch.int32, device=dev)
-            m = _lib.MultiArgs()
-            m.n_networks, m.net_index, m.status = self.set_size, ptr(net_index), ptr(out["_status"])
-        check(_lib.lib().mzh_saliency(self._h, ctypes.byref(a), None if m is None else ctypes.byref(m),
-                                      self._stream()), "mzh_saliency")
-        return out
+        f32, N = torch.float32, self.n_disks
+        return self._rows_call(
+            "saliency", _lib.SaliencyArgs(),
+            [("obs", obs, f32, ("B", 3 * N)), ("env_index", env_index, torch.int32, ("n",)),
+             ("logit_index", logit_index, torch.int32, ("B",))],
+            [("policy", "sal_policy", f32, ("B", 3 * N), True), ("value", "sal_value", f32, ("B", 3 * N), True),
+             ("disc_policy", "disc_policy", f32, ("B", N), full), ("disc_value", "disc_value", f32, ("B", N), full),
+             ("h0", "h0", f32, ("B", LATENT), full), ("pi0", "pi0", f32, ("B", ACTIONS), full),
+             ("value0", "value0", f32, ("B",), full), ("picked", "picked", torch.int32, ("B",), full)],
+            tile, err, net_index, out)
 
     def param_grads(self, obs, action, *, env_index=None, net_index=None, policy_logit=None, out=None, full=False,
                     tile=None, dense=False, err=None):
@@ -327,48 +299,18 @@ class Engine:
         full=True, grad with dense=True (row j of the CALL: the dense gradients in load_weights' flat layout).
         tile = None | 16 | 32.  err: [1] int32, += 1 per skipped row.  Returns the dict; with net_index, "_status"
         is the device's [2] int32 verdict as in search_multi."""
-        dev = self.device
-        B = int(obs.shape[0])
-        N = self.n_disks
-        checks = [("obs", obs, torch.float32, (B, 3 * N)), ("action", action, torch.int32, (B,))]
-        n = B
-        if env_index is not None:
-            n = int(env_index.shape[0])
-            checks.append(("env_index", env_index, torch.int32, (n,)))
-        if policy_logit is not None:
-            checks.append(("policy_logit", policy_logit, torch.int32, (B,)))
-        if net_index is not None:
-            checks.append(("net_index", net_index, torch.int32, (n,)))
-        out = dict(out) if out is not None else {}
+        f32, N = torch.float32, self.n_disks
+        n_floats = sum(int(np.prod(s)) for s in weight_shapes(N, self.support))
+        shapes = dict(delta1=("B", 5, HIDDEN), delta2=("B", 5, LATENT), act=("B", 5, HIDDEN), h0=("B", LATENT),
+                      z1=("B", LATENT), h1=("B", LATENT), pi0=("B", ACTIONS), value0=("B",), reward=("B",),
+                      objective=("B", 5), grad=("n", n_floats))
         required = ("delta1", "delta2", "act", "h0", "z1")
-        shapes = dict(delta1=(B, 5, HIDDEN), delta2=(B, 5, LATENT), act=(B, 5, HIDDEN), h0=(B, LATENT), z1=(B, LATENT),
-                      h1=(B, LATENT), pi0=(B, ACTIONS), value0=(B,), reward=(B,), objective=(B, 5),
-                      grad=(n, sum(int(np.prod(s)) for s in weight_shapes(N, self.support))))
-        for k, shp in shapes.items():
-            if k not in out and (k in required or (dense if k == "grad" else full)):
-                out[k] = torch.empty(shp, dtype=torch.float32, device=dev)
-            if k in out:
-                checks.append((k, out[k], torch.float32, shp))
-        for name, t, dt, shp in checks:
-            if t.dtype != dt or tuple(t.shape) != shp or not t.is_contiguous() or t.device != dev:
-                raise ValueError(f"param_grads: {name} must be a contiguous {dt} {shp} tensor on {dev}")
-        a = _lib.PgradArgs()
-        a.B, a.n, a.flags = B, n, search_flags(None, tile)
-        for k, t in (("env_index", env_index), ("obs", obs), ("action", action), ("policy_logit", policy_logit),
-                     ("err_count", err)):
-            setattr(a, k, ptr(t))
-        for k in shapes:
-            setattr(a, k, ptr(out.get(k)))
-        m = None
-        if net_index is not None:
-            if getattr(self, "set_size", 0) < 1:
-                raise RuntimeError("param_grads: no weight set loaded (load_weight_set)")
-            out["_status"] = torch.zeros(2, dtype=torch.int32, device=dev)
-            m = _lib.MultiArgs()
-            m.n_networks, m.net_index, m.status = self.set_size, ptr(net_index), ptr(out["_status"])
-        check(_lib.lib().mzh_param_grads(self._h, ctypes.byref(a), None if m is None else ctypes.byref(m),
-                                         self._stream()), "mzh_param_grads")
-        return out
+        return self._rows_call(
+            "param_grads", _lib.PgradArgs(),
+            [("obs", obs, f32, ("B", 3 * N)), ("action", action, torch.int32, ("B",)),
+             ("env_index", env_index, torch.int32, ("n",)), ("policy_logit", policy_logit, torch.int32, ("B",))],
+            [(k, k, f32, shp, k in required or (dense if k == "grad" else full)) for k, shp in shapes.items()],
+            tile, err, net_index, out)
 
     # ---------------------------------------------------------------- expansion memo (wave kernel)
     def set_memo_depth(self, depth):

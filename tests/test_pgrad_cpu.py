@@ -1,5 +1,5 @@
 """Parameter gradients of the five sub-networks (gradient_analysis.py get_results), the checks that need no GPU:
-the boundary of mzh_param_grads (export, struct layout, argument errors before any device or engine is needed),
+the boundary of mzh_param_grads (export, struct layout; its argument errors: tests/rows_refusals.py),
 the gather map of the extra transposed buffer against a direct transposed pack (tests/pgrad_map_check.cpp under
 the host sanitizers, as its own program), the conditioning of every case, the reference's recorded gradients
 (tests/golden/pgrad_n3.npz, tests/golden/gen_pgrad_golden.py) against this repository's float64 torch path, and
@@ -16,12 +16,12 @@ import pytest
 import torch
 
 import pgrad_ref as pr
+import rows_refusals as rr
 from conftest import ROOT, golden
 
 HEADER = os.path.join(ROOT, "include", "mzh.h")
 FIELDS = ["B", "n", "flags", "env_index", "obs", "action", "policy_logit", "delta1", "delta2", "act", "h0", "z1", "h1",
           "pi0", "value0", "reward", "objective", "grad", "err_count"]
-REQUIRED = ("obs", "action", "delta1", "delta2", "act", "h0", "z1")
 
 
 @pytest.fixture(scope="module")
@@ -60,59 +60,19 @@ def test_pgrad_args_layout_matches_header(lib, tmp_path):
     assert fields == FIELDS
 
 
-def _valid_args(lib):
-    """arguments that pass every argument check (the pointers are never dereferenced by the checks)"""
-    a = lib.PgradArgs()
-    a.B, a.n, a.flags = 8, 4, 0
-    for f in FIELDS[3:]:
-        setattr(a, f, 0x1000)
-    return a
-
-
-def _valid_multi(lib):
-    m = lib.MultiArgs()
-    m.n_networks, m.net_index, m.status = 3, 0x1000, 0x1000
-    return m
-
-
-@pytest.mark.parametrize("field,value,msg", [(f, None, "required buffer is NULL") for f in REQUIRED] + [
-    ("n", 0, "bad n=0"), ("n", -2, "bad n=-2"), ("B", 0, "B=0"), ("B", -1, "B=-1"),
-    ("flags", 1, "flags=0x1"), ("flags", 2, "flags=0x2"), ("flags", 64, "flags=0x40"), ("flags", 128 | 16, "flags=0x90")])
+# the argument errors: the cases and checks shared by the three row calls (tests/rows_refusals.py)
+@pytest.mark.parametrize("field,value,msg", rr.argument_errors("mzh_param_grads"))
 def test_argument_errors_without_device_or_engine(lib, field, value, msg):
-    """refused before any launch, any device use and any look at the engine"""
-    L = lib.lib()
-    a = _valid_args(lib)
-    setattr(a, field, value)
-    for multi in (None, ctypes.byref(_valid_multi(lib))):
-        assert L.mzh_param_grads(None, ctypes.byref(a), multi, None) == lib.MZH_ERR_ARG == -1
-        assert "param_grads" in lib.last_error() and msg in lib.last_error()
+    rr.check_argument_error(lib, "mzh_param_grads", field, value, msg)
 
 
 def test_rows_beyond_the_batch_null_args_optional_outputs_and_the_tile_flags(lib):
-    L = lib.lib()
-    assert L.mzh_param_grads(None, None, None, None) == -1 and "args is NULL" in lib.last_error()
-    a = _valid_args(lib)
-    a.env_index, a.n, a.B = None, 9, 8  # without env_index row j is env j: n <= B
-    assert L.mzh_param_grads(None, ctypes.byref(a), None, None) == -1 and "bad n=9" in lib.last_error()
-    a.n = 8  # ... and n == B passes the argument checks: the next refusal is the missing engine
-    assert L.mzh_param_grads(None, ctypes.byref(a), None, None) == -1 and "engine NULL" in lib.last_error()
-    a = _valid_args(lib)
-    for f in FIELDS[3:]:
-        if f not in REQUIRED:
-            setattr(a, f, None)  # every optional pointer may be NULL
-    for flags in (0, lib.MZH_FLAG_COOP_TILE16, lib.MZH_FLAG_COOP_TILE32):
-        a.flags = flags
-        assert L.mzh_param_grads(None, ctypes.byref(a), None, None) == -1 and "engine NULL" in lib.last_error()
+    rr.check_rows_beyond_the_batch_null_args_optional_outputs_and_the_tile_flags(lib, "mzh_param_grads")
 
 
-@pytest.mark.parametrize("field,value,msg", [("net_index", None, "net_index is NULL"), ("n_networks", 0, "n_networks=0"),
-                                             ("n_networks", -1, "n_networks=-1"), ("n_networks", 257, "n_networks=257")])
+@pytest.mark.parametrize("field,value,msg", rr.MULTI_ERRORS)
 def test_multi_argument_errors_without_device_or_engine(lib, field, value, msg):
-    L = lib.lib()
-    m = _valid_multi(lib)
-    setattr(m, field, value)
-    assert L.mzh_param_grads(None, ctypes.byref(_valid_args(lib)), ctypes.byref(m), None) == -1
-    assert msg in lib.last_error()
+    rr.check_multi_argument_error(lib, "mzh_param_grads", field, value, msg)
 
 
 # ------------------------------------------------------------------------------------ the extra buffer's gather map

@@ -1,5 +1,5 @@
 """Input saliency (gradient_analysis.py compute_saliency), the checks that need no GPU: the boundary of
-mzh_saliency (export, struct layout, argument errors before any device or engine is needed), the transposed
+mzh_saliency (export, struct layout; its argument errors: tests/rows_refusals.py), the transposed
 weight blob element by element (tests/saliency_pack_check.cpp under the host sanitizers, as its own program),
 the reference's recorded vectors (tests/golden/saliency_n3.npz, tests/golden/gen_saliency_golden.py) against
 this repository's float64 torch path, the conditioning of every case's inputs, and that the bound the GPU tests
@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+import rows_refusals as rr
 import saliency_ref as sr
 from conftest import ROOT, golden
 
@@ -59,60 +60,19 @@ def test_saliency_args_layout_matches_header(lib, tmp_path):
     assert fields == FIELDS
 
 
-def _valid_args(lib):
-    """arguments that pass every argument check (the pointers are never dereferenced by the checks)"""
-    a = lib.SaliencyArgs()
-    a.B, a.n, a.flags = 8, 4, 0
-    for f in FIELDS[3:]:
-        setattr(a, f, 0x1000)
-    return a
-
-
-def _valid_multi(lib):
-    m = lib.MultiArgs()
-    m.n_networks, m.net_index, m.status = 3, 0x1000, 0x1000
-    return m
-
-
-@pytest.mark.parametrize("field,value,msg", [
-    ("obs", None, "required buffer is NULL"), ("sal_policy", None, "required buffer is NULL"),
-    ("sal_value", None, "required buffer is NULL"),
-    ("n", 0, "bad n=0"), ("n", -2, "bad n=-2"), ("B", 0, "B=0"), ("B", -1, "B=-1"),
-    ("flags", 1, "flags=0x1"), ("flags", 2, "flags=0x2"), ("flags", 64, "flags=0x40"), ("flags", 128 | 16, "flags=0x90")])
+# the argument errors: the cases and checks shared by the three row calls (tests/rows_refusals.py)
+@pytest.mark.parametrize("field,value,msg", rr.argument_errors("mzh_saliency"))
 def test_argument_errors_without_device_or_engine(lib, field, value, msg):
-    """refused before any launch, any device use and any look at the engine"""
-    L = lib.lib()
-    a = _valid_args(lib)
-    setattr(a, field, value)
-    for multi in (None, ctypes.byref(_valid_multi(lib))):
-        assert L.mzh_saliency(None, ctypes.byref(a), multi, None) == lib.MZH_ERR_ARG == -1
-        assert msg in lib.last_error()
+    rr.check_argument_error(lib, "mzh_saliency", field, value, msg)
 
 
 def test_rows_beyond_the_batch_null_args_optional_outputs_and_the_tile_flags(lib):
-    L = lib.lib()
-    assert L.mzh_saliency(None, None, None, None) == -1 and "args is NULL" in lib.last_error()
-    a = _valid_args(lib)
-    a.env_index, a.n, a.B = None, 9, 8  # without env_index row j is env j: n <= B
-    assert L.mzh_saliency(None, ctypes.byref(a), None, None) == -1 and "bad n=9" in lib.last_error()
-    a.n = 8  # ... and n == B passes the argument checks: the next refusal is the missing engine
-    assert L.mzh_saliency(None, ctypes.byref(a), None, None) == -1 and "engine NULL" in lib.last_error()
-    a = _valid_args(lib)
-    for f in ("logit_index", "picked", "disc_policy", "disc_value", "h0", "pi0", "value0", "err_count"):
-        setattr(a, f, None)  # every optional pointer may be NULL
-    for flags in (0, lib.MZH_FLAG_COOP_TILE16, lib.MZH_FLAG_COOP_TILE32):
-        a.flags = flags
-        assert L.mzh_saliency(None, ctypes.byref(a), None, None) == -1 and "engine NULL" in lib.last_error()
+    rr.check_rows_beyond_the_batch_null_args_optional_outputs_and_the_tile_flags(lib, "mzh_saliency")
 
 
-@pytest.mark.parametrize("field,value,msg", [("net_index", None, "net_index is NULL"), ("n_networks", 0, "n_networks=0"),
-                                             ("n_networks", -1, "n_networks=-1"), ("n_networks", 257, "n_networks=257")])
+@pytest.mark.parametrize("field,value,msg", rr.MULTI_ERRORS)
 def test_multi_argument_errors_without_device_or_engine(lib, field, value, msg):
-    L = lib.lib()
-    m = _valid_multi(lib)
-    setattr(m, field, value)
-    assert L.mzh_saliency(None, ctypes.byref(_valid_args(lib)), ctypes.byref(m), None) == -1
-    assert msg in lib.last_error()
+    rr.check_multi_argument_error(lib, "mzh_saliency", field, value, msg)
 
 
 # ------------------------------------------------------------------------------------ the transposed blob
