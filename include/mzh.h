@@ -777,7 +777,8 @@ int mzh_episode_ingest(const mzh_ingest_args* args, mzh_stream stream);
  * n_sims < 0, max_steps < 1, T < max_steps, T * B rows beyond int32, goal_peg outside 0..2, a flag other than
  * MZH_FLAG_NP1_UCB, engine NULL; MZH_ERR_TEMPERATURE as mzh_search; MZH_ERR_CAPACITY: B > max_roots, n_sims >
  * max_sims, or n_sims beyond the latency kernel's LDS (the MZH_FLAG_KERNEL_ONE rule); MZH_ERR_STATE: weights
- * not loaded.  The checks that need no engine come first.  Weight sets and replay have no episode form.
+ * not loaded.  The checks that need no engine come first.  Replay has no episode form; a weight set plays through
+ * mzh_play_episodes_multi below.
  * ------------------------------------------------------------------------------------------- */
 typedef struct mzh_episode_args {
   int32_t B;             /* envs */
@@ -809,6 +810,26 @@ typedef struct mzh_episode_args {
 } mzh_episode_args;
 
 int mzh_play_episodes(mzh_engine* eng, const mzh_episode_args* args, mzh_stream stream);
+
+/* Episodes of several networks in one launch: env b plays its whole episode under network net_index[b] of the
+ * set loaded by mzh_load_weight_set (or refreshed by mzh_load_weight_set_device), with the result
+ * mzh_play_episodes gives on an engine holding that network alone, bit for bit, from the same start state, the same
+ * rows of the [T][B] tables (column b) and the same minmax_in[b].  `args` is mzh_play_episodes', unchanged; `multi`
+ * is mzh_search_multi's with its contract: net_index [B] on the device, non-decreasing, each entry in
+ * [0, n_networks); a network without envs is fine.  Two launches: the one-workgroup prologue of the other multi
+ * calls checks net_index on the device, then the set form of the episode kernel plays env blockIdx.x,
+ * blockIdx.x + gridDim.x, ... on min(B, 256) workgroups, each holding the hidden layers' rows (registers) and the
+ * output layers (LDS) of its env's network and loading another network's only where its next env has one (B > 256).
+ * The engine's single network is neither needed nor touched.
+ * Refused before any launch: everything mzh_play_episodes refuses before it uses the engine, in its order; then
+ * multi NULL, net_index NULL, n_networks outside [1, 256] (MZH_ERR_ARG), all of these without an engine; then engine
+ * NULL and the capacity errors of mzh_play_episodes; no set loaded (MZH_ERR_STATE); n_networks above the M of the
+ * loaded set (MZH_ERR_ARG).
+ * Refused on the device: a net_index that decreases or has an entry outside [0, n_networks) -- no env plays, no
+ * output of args is written (err_count included), and status[0] = 1.  Otherwise status[0] = 0 and status[1] is the
+ * number of networks that have envs. */
+int mzh_play_episodes_multi(mzh_engine* eng, const mzh_episode_args* args, const mzh_multi_args* multi,
+                            mzh_stream stream);
 
 #ifdef __cplusplus
 }

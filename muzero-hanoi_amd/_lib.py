@@ -218,6 +218,7 @@ SIGNATURES = {
     "mzh_replay_set_priorities": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, ctypes.c_int, _vp, _vp]),
     "mzh_episode_ingest": (ctypes.c_int, [ctypes.POINTER(IngestArgs), _vp]),
     "mzh_play_episodes": (ctypes.c_int, [_vp, ctypes.POINTER(EpisodeArgs), _vp]),
+    "mzh_play_episodes_multi": (ctypes.c_int, [_vp, ctypes.POINTER(EpisodeArgs), ctypes.POINTER(MultiArgs), _vp]),
 }
 
 _lib = None

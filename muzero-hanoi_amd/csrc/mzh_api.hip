@@ -72,6 +72,7 @@ struct mzh_engine {
   int set_m = 0;               // 0: no set loaded
   size_t set_stride = 0;
   MzhNet setnet{};             // network 0 of the set: the template mzh_search_multi_kernel offsets
+  MzhOneNet setonet{};         // network 0's latency-kernel views: the set form of the episode kernel offsets them
   const float* set_scal = nullptr;
   MzhTile* mtiles = nullptr;   // tile table workspace of mzh_search_multi, allocated with the first set
   int32_t* mntiles = nullptr;
@@ -327,6 +328,19 @@ static MzhSalNetT make_tnet(const MzhPackedT& t, const void* base, size_t stride
   return n;
 }
 
+// the latency kernel's views of the blob at `base` (MzhPacked::one: offsets inside the main blob)
+static MzhOneNet make_onet(const MzhPacked& pk, const float* base) {
+  MzhOneNet o;
+  o.l1 = reinterpret_cast<const float4*>(base + pk.one.l1);
+  o.b1 = reinterpret_cast<const float4*>(base + pk.one.b1);
+  o.rep0 = base + pk.one.rep0;
+  o.rep0b = base + pk.one.rep0b;
+  o.rep2 = reinterpret_cast<const float4*>(base + pk.one.rep2);
+  o.rep2b = base + pk.one.rep2b;
+  o.l2 = reinterpret_cast<const float4*>(base + pk.one.l2);
+  return o;
+}
+
 // the three kernels' views (MzhNet, MzhWNet, MzhOneNet) and the saliency view of the single network whose
 // blobs lie in wbuf / tbuf with the offsets of pk / pt
 static int bind_single(mzh_engine* eng, const MzhPacked& pk, const MzhPackedT& pt) {
@@ -356,14 +370,7 @@ static int bind_single(mzh_engine* eng, const MzhPacked& pk, const MzhPackedT& p
   w.oh = base + pk.wonehot;
   w.support = sup;
   w.in_dim = in;
-  MzhOneNet& o = eng->onet;
-  o.l1 = reinterpret_cast<const float4*>(base + pk.one.l1);
-  o.b1 = reinterpret_cast<const float4*>(base + pk.one.b1);
-  o.rep0 = base + pk.one.rep0;
-  o.rep0b = base + pk.one.rep0b;
-  o.rep2 = reinterpret_cast<const float4*>(base + pk.one.rep2);
-  o.rep2b = base + pk.one.rep2b;
-  o.l2 = reinterpret_cast<const float4*>(base + pk.one.l2);
+  eng->onet = make_onet(pk, base);
   eng->loaded = true;
   return MZH_OK;
 }
@@ -410,6 +417,7 @@ static int bind_set(mzh_engine* eng, const MzhPacked& layout, const MzhPackedT& 
   const float* base = static_cast<const float*>(eng->setbuf);
   const int nst = make_net(layout, base, eng->support, eng->in_dim, &eng->setnet);
   if (nst) return nst;
+  eng->setonet = make_onet(layout, base);
   eng->set_stride = stride * sizeof(float);
   eng->set_scal = base + (size_t)M * stride;
   eng->set_m = M;
@@ -1668,8 +1676,10 @@ extern "C" int mzh_episode_ingest(const mzh_ingest_args* a, mzh_stream stream) {
   return e == hipSuccess ? MZH_OK : hip_fail(e, "episode ingest launch");
 }
 
-// Whole episodes in one launch on the latency kernel (mzh.h).  The checks that need no engine come first.
-extern "C" int mzh_play_episodes(mzh_engine* eng, const mzh_episode_args* a, mzh_stream stream) {
+// Whole episodes in one launch on the latency kernel (mzh.h): mzh_play_episodes (m == NULL, the engine's network)
+// and mzh_play_episodes_multi (the loaded set).  The checks that need no engine come first.
+static int play_episodes_common(mzh_engine* eng, const mzh_episode_args* a, const mzh_multi_args* m, bool multi,
+                                mzh_stream stream) {
   if (!a) return fail(MZH_ERR_ARG, "play_episodes: args is NULL");
   if (a->B < 1 || a->n_sims < 0) return fail(MZH_ERR_ARG, "play_episodes: B=%d n_sims=%d", a->B, a->n_sims);
   if (a->goal_peg < 0 || a->goal_peg > 2) return fail(MZH_ERR_ARG, "play_episodes: goal_peg=%d outside 0..2", a->goal_peg);
@@ -1686,13 +1696,26 @@ extern "C" int mzh_play_episodes(mzh_engine* eng, const mzh_episode_args* a, mzh
       !a->solved || !a->final_state || !a->minmax_out)
     return fail(MZH_ERR_ARG, "play_episodes: required buffer is NULL");
   if (!a->deterministic && !a->action_u) return fail(MZH_ERR_ARG, "play_episodes: stochastic action selection needs action_u");
+  if (multi) {
+    if (!m) return fail(MZH_ERR_ARG, "play_episodes_multi: multi is NULL");
+    if (!m->net_index) return fail(MZH_ERR_ARG, "play_episodes_multi: net_index is NULL");
+    if (m->n_networks < 1 || m->n_networks > MZH_MULTI_MAX_NETS)
+      return fail(MZH_ERR_ARG, "play_episodes_multi: n_networks=%d outside [1, %d]", m->n_networks, MZH_MULTI_MAX_NETS);
+  }
   if (!eng) return fail(MZH_ERR_ARG, "play_episodes: engine is NULL");
   if (a->B > eng->max_roots) return fail(MZH_ERR_CAPACITY, "play_episodes: B=%d > max_roots=%d", a->B, eng->max_roots);
   if (a->n_sims > eng->max_sims) return fail(MZH_ERR_CAPACITY, "play_episodes: n_sims=%d > max_sims=%d", a->n_sims, eng->max_sims);
   MzhSearchPlan pl;  // the latency kernel's plan: its grid, the latents in LDS where they fit, or its capacity error
   const int st = make_plan(a->B, a->n_sims, MZH_FLAG_KERNEL_ONE, false, eng->support, true, &pl);
   if (st) return st;
-  if (!eng->loaded) return fail(MZH_ERR_STATE, "weights not loaded");
+  if (multi) {
+    if (eng->set_m == 0) return fail(MZH_ERR_STATE, "no weight set loaded (mzh_load_weight_set)");
+    if (m->n_networks > eng->set_m)
+      return fail(MZH_ERR_ARG, "play_episodes_multi: n_networks=%d outside [1, %d], the loaded set", m->n_networks,
+                  eng->set_m);
+  } else if (!eng->loaded) {
+    return fail(MZH_ERR_STATE, "weights not loaded");
+  }
   DeviceGuard g(eng->device);
   if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
   MzhSearchParams p{};
@@ -1706,6 +1729,25 @@ extern "C" int mzh_play_episodes(mzh_engine* eng, const mzh_episode_args* a, mzh
   ep.T = a->T; ep.n_disks = eng->n_disks; ep.goal_peg = a->goal_peg; ep.max_steps = a->max_steps;
   ep.start = a->state; ep.obs = a->obs; ep.reward = a->reward; ep.steps = a->steps; ep.illegal = a->illegal;
   ep.solved = a->solved; ep.final_state = a->final_state; ep.minmax_out = a->minmax_out; ep.err_count = a->err_count;
-  hipError_t e = mzh_launch_episodes(pl, eng->net, eng->onet, p, ep, (hipStream_t)stream);
-  return e == hipSuccess ? MZH_OK : hip_fail(e, "play_episodes launch");
+  if (!multi) {
+    hipError_t e = mzh_launch_episodes(pl, eng->net, eng->onet, p, ep, (hipStream_t)stream);
+    return e == hipSuccess ? MZH_OK : hip_fail(e, "play_episodes launch");
+  }
+  // the device check of net_index: the tile prologue of the other multi calls with the whole batch as the tile size
+  // (one tile per network that has envs, at most min(M, B): inside the table), whose count the episode kernel reads
+  const MzhMultiParams mp = multi_params(eng, m);
+  hipError_t e = mzh_launch_multi_tiles(mp, a->B, a->B, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "play_episodes_multi net_index check launch");
+  const MzhEpisodeSet es{m->net_index, eng->mntiles, eng->set_stride};
+  e = mzh_launch_episodes_set(pl, eng->setnet, eng->setonet, p, ep, es, (hipStream_t)stream);
+  return e == hipSuccess ? MZH_OK : hip_fail(e, "play_episodes_multi launch");
+}
+
+extern "C" int mzh_play_episodes(mzh_engine* eng, const mzh_episode_args* a, mzh_stream stream) {
+  return play_episodes_common(eng, a, nullptr, false, stream);
+}
+
+extern "C" int mzh_play_episodes_multi(mzh_engine* eng, const mzh_episode_args* a, const mzh_multi_args* m,
+                                       mzh_stream stream) {
+  return play_episodes_common(eng, a, m, true, stream);
 }

@@ -412,6 +412,15 @@ struct MzhEpisodeParams {
 };
 hipError_t mzh_launch_episodes(const MzhSearchPlan& pl, const MzhNet& net, const MzhOneNet& on, const MzhSearchParams& p,
                                const MzhEpisodeParams& ep, hipStream_t stream);
+// the set side of mzh_play_episodes_multi (a fifth kernel argument of the episode form): env b plays under network
+// net_index[b] of the loaded set, whose blobs -- each in the latency kernel's layout too -- lie `stride` bytes apart
+struct MzhEpisodeSet {
+  const int32_t* net_index;  // [B] caller's, checked by mzh_multi_tiles_kernel before the episode launch
+  const int32_t* ntiles;     // [1] that check's verdict (MzhMultiParams::ntiles): 0 = refused, no env plays
+  size_t stride;             // bytes between two networks' blobs
+};
+hipError_t mzh_launch_episodes_set(const MzhSearchPlan& pl, const MzhNet& net, const MzhOneNet& on, const MzhSearchParams& p,
+                                   const MzhEpisodeParams& ep, const MzhEpisodeSet& es, hipStream_t stream);
 size_t mzh_one_smem_bytes(int S, bool latl);
 hipError_t mzh_launch_one(const MzhSearchPlan& pl, const MzhNet& net, const MzhOneNet& on, const MzhSearchParams& p,
                           hipStream_t stream);

@@ -511,8 +511,45 @@ __device__ __forceinline__ int one_fresh(int v) {
   return v;
 }
 
-// the episode form's fourth kernel argument
+// the episode form's fourth kernel argument, and the set form's fifth
 __device__ __forceinline__ const MzhEpisodeParams& one_ep(const MzhEpisodeParams& e) { return e; }
+__device__ __forceinline__ const MzhEpisodeParams& one_ep(const MzhEpisodeParams& e, const MzhEpisodeSet&) { return e; }
+__device__ __forceinline__ const MzhEpisodeSet& one_set(const MzhEpisodeParams&, const MzhEpisodeSet& s) { return s; }
+
+// the views of the blob `off` bytes after o's (a set's networks lie at a constant stride: MzhEpisodeSet)
+__device__ __forceinline__ MzhOneNet one_net_at(const MzhOneNet& o, size_t off) {
+  auto mv = [off](auto* q) { return reinterpret_cast<decltype(q)>(reinterpret_cast<const char*>(q) + off); };
+  return MzhOneNet{mv(o.l1), mv(o.b1), mv(o.rep0), mv(o.rep0b), mv(o.rep2), mv(o.rep2b), mv(o.l2)};
+}
+
+// a network's stationary part: the hidden layers' weight rows of unit t % 256 into the thread's registers (every
+// weight array lies in the one packed blob) and the output layers' image into LDS
+__device__ __forceinline__ void one_load_net(const MzhOneNet& on, int t, bool A, float (&w1)[64], float (&w2)[64],
+                                             float (&woh)[6], float& b1a, float& b1b, float4* l2) {
+  const __amdgpu_buffer_rsrc_t wres = mzh_rsrc(on.l1);
+  const int wbase = 0;
+  {
+    const int n = t & 255, k0 = A ? 0 : 32;
+#pragma unroll
+    for (int k4 = 0; k4 < 16; ++k4) {
+      const floatx4 a = mzh_ld4(wres, 16 * n, wbase + ((k0 + k4) * 256) * 16);
+      const floatx4 b = mzh_ld4(wres, 16 * n, wbase + ((k0 + 16 + k4) * 256) * 16);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        w1[4 * k4 + i] = a[i];
+        w2[4 * k4 + i] = b[i];
+      }
+    }
+    const floatx4 o0 = mzh_ld4(wres, 16 * n, 64 * 256 * 16), o1 = mzh_ld4(wres, 16 * n, 65 * 256 * 16);
+    woh[0] = o0[0]; woh[1] = o0[1]; woh[2] = o0[2]; woh[3] = o0[3]; woh[4] = o1[0]; woh[5] = o1[1];
+    const float4 bb = on.b1[n];
+    b1a = A ? bb.x : bb.z;
+    b1b = A ? bb.y : bb.w;
+  }
+  const __amdgpu_buffer_rsrc_t l2res = mzh_rsrc(on.l2);
+  for (int i = t; i < MZH_ONE_L2F4; i += kThreads)
+    *reinterpret_cast<floatx4*>(&l2[i]) = mzh_ld4(l2res, 16 * i, 0);
+}
 
 // LATL: the latents in LDS (when the launcher finds room; otherwise in the engine's HBM workspace).
 // EPA: empty, the search form mzh_search_one_kernel<SUP33, MMIN, LATL>(net, on, p): root r of p, one search.
@@ -523,9 +560,13 @@ __device__ __forceinline__ const MzhEpisodeParams& one_ep(const MzhEpisodeParams
 // step_counter / the tallies in sm.pad, the MinMaxStats in sm.rsv; "done" is sm.pad[0], written by that one lane
 // before the move's last barrier and read by every thread after it.  Always launched with MMIN: from its second
 // move on an agent's MinMaxStats are carried bounds, as a caller's minmax_in are.
+// EPA = MzhEpisodeParams, MzhEpisodeSet: the set form of the episode form (mzh_play_episodes_multi; a fifth kernel
+// argument): env r plays under network net_index[r] of a loaded set, `on` being network 0's views.  A workgroup holds
+// the rows and the LDS image of its env's network and loads another network's only where its next env has one; every
+// other line is the episode form's, so an env plays bit for bit as on an engine holding its network alone.
 template <bool SUP33, bool MMIN, bool LATL, class... EPA>
 __global__ __launch_bounds__(512, 2) void mzh_search_one_kernel(MzhNet net, MzhOneNet on, MzhSearchParams p, EPA... epa) {
-  constexpr bool EP = sizeof...(EPA) != 0;
+  constexpr bool EP = sizeof...(EPA) != 0, SET = sizeof...(EPA) == 2;
   extern __shared__ __align__(128) unsigned char smem_raw[];
   MzhOneSmem& sm = *reinterpret_cast<MzhOneSmem*>(smem_raw);
   float4* l2 = reinterpret_cast<float4*>(smem_raw + kSmBytes);
@@ -542,6 +583,13 @@ __global__ __launch_bounds__(512, 2) void mzh_search_one_kernel(MzhNet net, MzhO
 
   const int t = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(t >> 6);  // wave-uniform (scalar branches)
   const bool A = t < 256;  // waves 0-3: dynamic_net.0 / rwd_net.0 rows; waves 4-7: policy_net.0 / value_net.0
+  // the set form: nothing plays on a net_index the device check refused (uniform over the grid, before any barrier);
+  // else the views of the network of this workgroup's first env (blockIdx.x < B: the grid is min(B, 256))
+  if constexpr (SET) {
+    const MzhEpisodeSet& es = one_set(epa...);
+    if (*es.ntiles == 0) return;
+    on = one_net_at(on, (size_t)es.net_index[blockIdx.x] * es.stride);
+  }
   const __amdgpu_buffer_rsrc_t wres = mzh_rsrc(on.l1);  // every weight array lies in the one packed blob
   const int wbase = 0;
   // the hidden layers' weight rows of unit t % 256, in registers for the whole launch
@@ -565,7 +613,7 @@ __global__ __launch_bounds__(512, 2) void mzh_search_one_kernel(MzhNet net, MzhO
     b1a = A ? bb.x : bb.z;
     b1b = A ? bb.y : bb.w;
   }
-  const __amdgpu_buffer_rsrc_t l2res = mzh_rsrc(on.l2), r2res = mzh_rsrc(on.rep2);
+  __amdgpu_buffer_rsrc_t l2res = mzh_rsrc(on.l2), r2res = mzh_rsrc(on.rep2);
   for (int i = t; i < MZH_ONE_L2F4; i += kThreads)
     *reinterpret_cast<floatx4*>(&l2[i]) = mzh_ld4(l2res, 16 * i, 0);
   for (int i = t; i < (int)(sizeof(MzhOneSmem) / 4); i += kThreads) reinterpret_cast<float*>(&sm)[i] = 0.0f;
@@ -578,6 +626,21 @@ __global__ __launch_bounds__(512, 2) void mzh_search_one_kernel(MzhNet net, MzhO
   __syncthreads();
 
   for (int r = blockIdx.x; r < p.B; r += gridDim.x) {
+    if constexpr (SET) {
+      // env r of another network than the workgroup's last env (both entries re-read here, nothing kept across the
+      // move loop): that network's views, rows and LDS image.  The last env's closing barrier is behind every
+      // thread, so no wave still reads the old image; the barrier after the start state below covers the new one.
+      const MzhEpisodeSet& es = one_set(epa...);
+      if (r != (int)blockIdx.x) {
+        const int m = es.net_index[r], was = es.net_index[r - (int)gridDim.x];
+        if (m != was) {
+          on = one_net_at(on, (size_t)(m - was) * es.stride);
+          one_load_net(on, t, A, w1, w2, woh, b1a, b1b, l2);
+          l2res = mzh_rsrc(on.l2);
+          r2res = mzh_rsrc(on.rep2);
+        }
+      }
+    }
     if constexpr (EP) {  // env r: oneHot_encoding(c_state) (utils.py:9-25) of its start; a peg outside 0..2 skips it
       const MzhEpisodeParams& ep = one_ep(epa...);
       if (wave == 0) {
@@ -942,6 +1005,29 @@ hipError_t mzh_launch_episodes(const MzhSearchPlan& pl, const MzhNet& net, const
                   : launch_episode_t<true, false>(net, on, p, ep, pl.grid, stream);
   return pl.ohl ? launch_episode_t<false, true>(net, on, p, ep, pl.grid, stream)
                 : launch_episode_t<false, false>(net, on, p, ep, pl.grid, stream);
+}
+
+template <bool SUP33, bool LATL>
+static hipError_t launch_episode_set_t(const MzhNet& net, const MzhOneNet& on, const MzhSearchParams& p,
+                                       const MzhEpisodeParams& ep, const MzhEpisodeSet& es, int grid, hipStream_t stream) {
+  const size_t smem = mzh_one_smem_bytes(p.S, LATL);
+  const void* fn = reinterpret_cast<const void*>(&mzh_search_one_kernel<SUP33, true, LATL, MzhEpisodeParams, MzhEpisodeSet>);
+  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((mzh_search_one_kernel<SUP33, true, LATL, MzhEpisodeParams, MzhEpisodeSet>), dim3(grid),
+                     dim3(kThreads), smem, stream, net, on, p, ep, es);
+  return hipGetLastError();
+}
+
+// the set form of the episode launch (mzh_play_episodes_multi): `on` is network 0 of the set, es.ntiles the verdict
+// of mzh_multi_tiles_kernel on es.net_index, launched before this on the same stream
+hipError_t mzh_launch_episodes_set(const MzhSearchPlan& pl, const MzhNet& net, const MzhOneNet& on, const MzhSearchParams& p,
+                                   const MzhEpisodeParams& ep, const MzhEpisodeSet& es, hipStream_t stream) {
+  if (pl.sup33)
+    return pl.ohl ? launch_episode_set_t<true, true>(net, on, p, ep, es, pl.grid, stream)
+                  : launch_episode_set_t<true, false>(net, on, p, ep, es, pl.grid, stream);
+  return pl.ohl ? launch_episode_set_t<false, true>(net, on, p, ep, es, pl.grid, stream)
+                : launch_episode_set_t<false, false>(net, on, p, ep, es, pl.grid, stream);
 }
 
 #ifdef MZH_STAMPS

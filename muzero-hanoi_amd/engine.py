@@ -445,7 +445,7 @@ class Engine:
 
     def play_episodes(self, n_sims, state, max_steps, *, tie_idx, noise=None, action_u=None, minmax_in=None,
                       goal_peg=2, temperature=1.0, deterministic=False, discount=0.8, eps=0.25, np1_ucb=False,
-                      record_obs=False, visits=False, out=None, err=None):
+                      record_obs=False, visits=False, out=None, err=None, net_index=None):
         """Whole episodes in one launch (mzh_play_episodes): env b starts from state[b] ([B, n_disks] uint8) and
         plays until it is done; move t of env b searches with row [t, b] of tie_idx [T, B] int32, noise [T, B, 6]
         float64 (None: no root noise) and action_u [T, B] float64 (None when deterministic), its MinMaxStats
@@ -456,8 +456,14 @@ class Engine:
         visits [T, B, 6] -- whose rows t >= steps[b] the kernel leaves as they are (allocated here: action -1,
         everything else 0; or the caller's tensors of the same names in `out`), and per env steps, illegal
         (int32), solved (uint8), final_state [B, n_disks] and minmax [B, 2].  err [1] int32 counts the envs
-        refused on the device (a start state with a peg outside 0..2; such an env plays nothing)."""
+        refused on the device (a start state with a peg outside 0..2; such an env plays nothing).
+        net_index [B] (non-decreasing, each in [0, set size)): env b plays under network net_index[b] of the loaded
+        weight set instead of the engine's network (mzh_play_episodes_multi), with the result a lone engine of
+        that network gives; the dict then has "_status", the device's [2] int32 verdict: [0] = 1 where it refused
+        net_index (nothing played, nothing written), [1] the networks that had envs."""
         d = self.device
+        if net_index is not None and getattr(self, "set_size", 0) < 1:
+            raise RuntimeError("play_episodes: no weight set loaded (load_weight_set)")
         if tie_idx.dim() != 2:
             raise ValueError(f"play_episodes: tie_idx must be [T, B], got {tuple(tie_idx.shape)}")
         T, B = (int(x) for x in tie_idx.shape)
@@ -503,7 +509,18 @@ class Engine:
                      ("obs", "obs"), ("steps", "steps"), ("illegal", "illegal"), ("solved", "solved"),
                      ("final_state", "final_state"), ("minmax_out", "minmax"), ("err_count", "err")):
             setattr(a, k, ptr(res.get(f)))
-        check(_lib.lib().mzh_play_episodes(self._h, ctypes.byref(a), self._stream()), "mzh_play_episodes")
+        if net_index is None:
+            check(_lib.lib().mzh_play_episodes(self._h, ctypes.byref(a), self._stream()), "mzh_play_episodes")
+        else:
+            ni = net_index.to(d, torch.int32).contiguous()
+            if tuple(ni.shape) != (B,):
+                raise ValueError(f"play_episodes: net_index must have one entry per env ({B}), got {tuple(ni.shape)}")
+            res["_status"] = torch.zeros(2, dtype=torch.int32, device=d)
+            keep.append(ni)
+            m = _lib.MultiArgs()
+            m.n_networks, m.net_index, m.status = self.set_size, ptr(ni), ptr(res["_status"])
+            check(_lib.lib().mzh_play_episodes_multi(self._h, ctypes.byref(a), ctypes.byref(m), self._stream()),
+                  "mzh_play_episodes_multi")
         res["_keep"] = keep + [pt]
         return res
 

@@ -34,9 +34,9 @@ from torch.autograd.graph import increment_version
 
 from .buffer import Buffer
 from .mcts import MCTS
-from .networks import MuZeroNet
+from .networks import MuZeroNet, NetworkSet
 from .rng import predraw
-from .selfplay import BatchedSelfPlay, episode_records, ingest_records, play_game
+from .selfplay import BatchedSelfPlay, episode_records, episodes_result, ingest_records, play_game
 from .utils import adjust_temperature, organise_transitions
 
 
@@ -113,8 +113,7 @@ class Muzero:
     # ------------------------------------------------------------------ Muzero.py:81-151
     def training_loop(self, n_loops, min_replay_size, print_acc=50):
         logging.info("Training started \n")
-        accuracy, tot_accuracy = [], []
-        value_loss, rwd_loss, pi_loss = [], [], []
+        log = self._new_log()
         for n in range(1, n_loops):
             ep_steps = []
             if self.ingest == "device":  # played, filtered and written to the buffer on the device
@@ -126,31 +125,42 @@ class Muzero:
             else:
                 episodes = (self._play_game(episode=n * self.n_ep_x_loop, deterministic=False)
                             for _ in range(self.n_ep_x_loop))
-            for steps, states, rwds, actions, pi_probs, returns, priorities in episodes:
-                ep_steps.append(steps)
-                if returns[-1, 0] > 0:  # only successful episodes enter the buffer
-                    self.buffer.add(states, rwds, actions, pi_probs, returns, priorities)
-            accuracy.append(sum(ep_steps) / self.n_ep_x_loop)
-            if len(self.buffer) > min_replay_size:
-                for _ in range(self.n_update_x_loop):
-                    if self.priority_replay:
-                        states, rwds, actions, pi_probs, returns, indx, w = self.buffer.priority_sample(self.batch_s)
-                    else:
-                        states, rwds, actions, pi_probs, returns = self.buffer.uniform_sample(self.batch_s)
-                        indx, w = None, None
-                    new_prio, v_loss, r_loss, p_loss = self._update(states, rwds, actions, pi_probs, returns, w)
-                    self.buffer.update_priorities(indx, new_prio)
-                value_loss.append(v_loss)
-                rwd_loss.append(r_loss)
-                pi_loss.append(p_loss)
-            if n * self.n_ep_x_loop % print_acc == 0:
-                mean_acc = sum(accuracy) / print_acc
-                logging.info("Loop %s | steps %.3f | V %.3f | rwd %.3f | Pi %.3f", n, mean_acc,
-                             sum(value_loss) / print_acc, sum(rwd_loss) / print_acc, sum(pi_loss) / print_acc)
-                tot_accuracy.append(mean_acc)
-                accuracy = []
-                value_loss, rwd_loss, pi_loss = [], [], []
-        return tot_accuracy
+            self._finish_loop(log, n, ep_steps, episodes, min_replay_size, print_acc)
+        return log["tot_accuracy"]
+
+    @staticmethod
+    def _new_log():
+        """what a training_loop call accumulates between its loops"""
+        return dict(accuracy=[], tot_accuracy=[], value_loss=[], rwd_loss=[], pi_loss=[])
+
+    def _finish_loop(self, log, n, ep_steps, episodes, min_replay_size, print_acc):
+        """loop n after its self-play (Muzero.py:95-151): the successful episodes into the buffer (ep_steps: the
+        step counts of those already ingested), the loop's updates once the buffer is large enough, the log"""
+        for steps, states, rwds, actions, pi_probs, returns, priorities in episodes:
+            ep_steps.append(steps)
+            if returns[-1, 0] > 0:  # only successful episodes enter the buffer
+                self.buffer.add(states, rwds, actions, pi_probs, returns, priorities)
+        log["accuracy"].append(sum(ep_steps) / self.n_ep_x_loop)
+        if len(self.buffer) > min_replay_size:
+            for _ in range(self.n_update_x_loop):
+                if self.priority_replay:
+                    states, rwds, actions, pi_probs, returns, indx, w = self.buffer.priority_sample(self.batch_s)
+                else:
+                    states, rwds, actions, pi_probs, returns = self.buffer.uniform_sample(self.batch_s)
+                    indx, w = None, None
+                new_prio, v_loss, r_loss, p_loss = self._update(states, rwds, actions, pi_probs, returns, w)
+                self.buffer.update_priorities(indx, new_prio)
+            log["value_loss"].append(v_loss)
+            log["rwd_loss"].append(r_loss)
+            log["pi_loss"].append(p_loss)
+        if n * self.n_ep_x_loop % print_acc == 0:
+            mean_acc = sum(log["accuracy"]) / print_acc
+            logging.info("Loop %s | steps %.3f | V %.3f | rwd %.3f | Pi %.3f", n, mean_acc,
+                         sum(log["value_loss"]) / print_acc, sum(log["rwd_loss"]) / print_acc,
+                         sum(log["pi_loss"]) / print_acc)
+            log["tot_accuracy"].append(mean_acc)
+            log["accuracy"] = []
+            log["value_loss"], log["rwd_loss"], log["pi_loss"] = [], [], []
 
     # ------------------------------------------------------------------ Muzero.py:153-207
     def _play_game(self, episode, deterministic=False):
@@ -165,10 +175,7 @@ class Muzero:
         (for n_games = 1 exactly the draws of _play_game).  Returns _play_game's tuple per episode; with
         ingest="device" the episodes go into the buffer here and only their step counts come back."""
         env, mm = self.env, self.mcts.min_max_stats
-        sp = BatchedSelfPlay(self.networks, env.discs, env.max_steps, int(self.mcts.n_simulations),
-                             discount=self.discount, dirichlet_alpha=self.mcts.root_dirichlet_alpha,
-                             root_exploration_eps=self.mcts.root_exploration_eps, goal_peg=env.goal[0],
-                             np1_ucb=self.mcts.np1_ucb)
+        sp = self._selfplay(self.networks)
         kw = dict(temperature=adjust_temperature(episode), deterministic=deterministic,
                   minmax=[[mm.maximum, mm.minimum]] * n_games)
         if self.selfplay != "device":
@@ -176,10 +183,28 @@ class Muzero:
         elif n_games == 1:  # one launch; the global stream is left where the lockstep play leaves it
             res = sp.play_episodes([env.init_state_idx], legacy_rng=True, **kw)
         else:  # the whole draw table from the global stream, move-major: row t * n_games + b for move t of env b
-            T = int(env.max_steps)
-            flat = predraw(T * n_games, deterministic=deterministic, alpha=sp.alpha, eps=sp.eps)
-            draws = tuple(None if x is None else x.reshape((T, n_games) + x.shape[1:]) for x in flat)
-            res = sp.play_episodes([env.init_state_idx] * n_games, draws=draws, **kw)
+            res = sp.play_episodes([env.init_state_idx] * n_games, draws=self._draw_table(sp, n_games, deterministic),
+                                   **kw)
+        return self._games_played(res)
+
+    def _selfplay(self, network):
+        """the BatchedSelfPlay of this agent's env and search settings over `network`"""
+        env = self.env
+        return BatchedSelfPlay(network, env.discs, env.max_steps, int(self.mcts.n_simulations),
+                               discount=self.discount, dirichlet_alpha=self.mcts.root_dirichlet_alpha,
+                               root_exploration_eps=self.mcts.root_exploration_eps, goal_peg=env.goal[0],
+                               np1_ucb=self.mcts.np1_ucb)
+
+    def _draw_table(self, sp, n_games, deterministic=False):
+        """play_episodes' table for n_games envs from the global NumPy stream, move-major"""
+        T = int(self.env.max_steps)
+        flat = predraw(T * n_games, deterministic=deterministic, alpha=sp.alpha, eps=sp.eps)
+        return tuple(None if x is None else x.reshape((T, n_games) + x.shape[1:]) for x in flat)
+
+    def _games_played(self, res):
+        """what follows a play of this agent's episodes (res: play(record_obs=True)'s dict): the MCTS instance keeps
+        the union of their MinMaxStats; _play_games' return value"""
+        mm = self.mcts.min_max_stats
         fin = res["minmax"].cpu().numpy()
         mm.maximum, mm.minimum = float(fin[:, 0].max()), float(fin[:, 1].min())
         if self.ingest == "device":
@@ -211,6 +236,76 @@ class Muzero:
         """Muzero.py:276-323"""
         return organise_transitions(episode_state, episode_rwd, episode_action, episode_piProb, episode_returns,
                                     self.unroll_n_steps, self.n_action)
+
+
+class MuzeroPopulation:
+    """Several seeds of one Muzero(selfplay="device") configuration trained abreast: every loop the agents' episodes
+    play in ONE launch over the NetworkSet of their networks (BatchedSelfPlay.play_episodes with net_index: agent
+    m's n_ep_x_loop envs on workgroups of their own), then each agent runs the lone loop's own ingest and updates.
+
+    seeds: one agent per seed, built after torch.manual_seed(seed), with its own NumPy legacy stream in the state
+    np.random.seed(seed) produces.  muzero_kwargs: Muzero's, without selfplay (always "device").  weights: how the
+    set's engine picks up the agents' changed parameters every loop (networks.engine_for_set).
+    Agent m ends exactly as torch.manual_seed(s); mz = Muzero(..., selfplay="device"); np.random.seed(s);
+    mz.training_loop(...) ends: parameters, optimiser state, buffer, MinMaxStats, tot_accuracy and stream
+    (self.streams[m], a np.random.get_state() tuple).  The caller's global NumPy stream is left as it was found."""
+
+    def __init__(self, seeds, *, weights="device", **muzero_kwargs):
+        seeds = [int(s) for s in seeds]
+        if not seeds:
+            raise ValueError("MuzeroPopulation: no seeds")
+        if muzero_kwargs.setdefault("selfplay", "device") != "device":
+            raise ValueError("MuzeroPopulation trains Muzero(selfplay='device') agents: selfplay must be 'device', "
+                             f"not {muzero_kwargs['selfplay']!r}")
+        self.seeds, self.weights = seeds, weights
+        self.agents = []
+        for seed in seeds:
+            torch.manual_seed(seed)
+            self.agents.append(Muzero(**muzero_kwargs))
+        self.streams = [np.random.RandomState(seed).get_state() for seed in seeds]
+        self.networks = NetworkSet([a.networks for a in self.agents])
+
+    def training_loop(self, n_loops, min_replay_size, print_acc=50):
+        """Muzero.training_loop of every agent, loop by loop abreast.  Returns the list of the agents' tot_accuracy."""
+        logging.info("Training started \n")
+        agents, M = self.agents, len(self.agents)
+        first, E = agents[0], agents[0].n_ep_x_loop
+        T, sp = int(first.env.max_steps), first._selfplay(self.networks)
+        start = np.full(M * E, first.env.init_state_idx, np.int64)
+        net_index = np.repeat(np.arange(M), E)
+        logs = [a._new_log() for a in agents]
+        caller = np.random.get_state()
+        try:
+            for n in range(1, n_loops):
+                # every agent's table from its own stream, as a lone _play_games draws it; agent m's envs are
+                # columns m * E .. of the launch's table
+                tables, drawn_from = [], list(self.streams)
+                for m, a in enumerate(agents):
+                    np.random.set_state(self.streams[m])
+                    tables.append(a._draw_table(sp, E))
+                    self.streams[m] = np.random.get_state()
+                draws = tuple(None if col[0] is None else torch.from_numpy(np.concatenate(col, axis=1))
+                              for col in zip(*tables))
+                minmax = np.repeat([[a.mcts.min_max_stats.maximum, a.mcts.min_max_stats.minimum] for a in agents], E,
+                                   axis=0)
+                out = sp._launch_episodes(start, draws, minmax, adjust_temperature(n * E), False, net_index, self.weights)
+                *steps, n_err = (int(x) for x in torch.cat([out["steps"], out["err"]]).cpu())  # the one host read
+                if n_err:
+                    raise RuntimeError(f"mzh_play_episodes_multi refused {n_err} start state(s)")
+                for m, a in enumerate(agents):
+                    cols = slice(m * E, (m + 1) * E)
+                    if E == 1:  # the one-env schedule: the stream as the moves played leave it
+                        np.random.set_state(drawn_from[m])
+                        predraw(steps[m], deterministic=False, alpha=sp.alpha, eps=sp.eps)
+                    else:
+                        np.random.set_state(self.streams[m])
+                    played = a._games_played(episodes_result(out, start[cols], max(steps[cols]), cols))
+                    ep_steps, episodes = ([int(s) for s in played], ()) if a.ingest == "device" else ([], played)
+                    a._finish_loop(logs[m], n, ep_steps, episodes, min_replay_size, print_acc)
+                    self.streams[m] = np.random.get_state()
+        finally:
+            np.random.set_state(caller)
+        return [log["tot_accuracy"] for log in logs]
 
 
 def unrolled_losses(net, states, rwds, actions, pi_probs, returns, unroll_n_steps, device):

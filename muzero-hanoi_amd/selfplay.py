@@ -230,9 +230,10 @@ class _Lockstep:
 class BatchedSelfPlay:
     """B independent agents in lockstep on one GPU, one MCTS instance (MinMaxStats) each.
 
-    network: one network for every agent, or a networks.NetworkSet -- then play / play_plans take net_index
-    [B] (non-decreasing: the agents of one network are consecutive) and agent b searches under
-    network[net_index[b]], all of them in one mzh_search_multi launch per move."""
+    network: one network for every agent, or a networks.NetworkSet -- then play / play_plans / play_episodes take
+    net_index [B] (non-decreasing: the agents of one network are consecutive) and agent b searches under
+    network[net_index[b]], all of them in one mzh_search_multi launch per move (play_episodes: in its one
+    mzh_play_episodes_multi launch)."""
 
     def __init__(self, network, n_disks, max_steps, n_simulations, *, discount=0.8, dirichlet_alpha=0.25,
                  root_exploration_eps=0.25, goal_peg=2, np1_ucb=False):
@@ -276,10 +277,12 @@ class BatchedSelfPlay:
         return dict(res, steps=env.steps_total, illegal=env.illegal_total, start_idx=run.start, minmax=run.mm)
 
     def play_episodes(self, start_idx, temperature=1.0, deterministic=False, seed=0, legacy_rng=False, minmax=None,
-                      draws=None):
+                      draws=None, net_index=None, weights="auto"):
         """`play(record_obs=True)` as ONE launch (Engine.play_episodes, mzh_play_episodes): a workgroup of the
         latency kernel takes an env and plays it to its end -- search, action draw, env step and record -- without
-        returning to the host.  One network (no NetworkSet, no RecordedNetwork).  Returns the dict
+        returning to the host.  A live network or, with net_index [B] (the class docstring), a NetworkSet whose
+        envs all play in that one launch (mzh_play_episodes_multi), each as under its network alone; no
+        RecordedNetwork.  Returns the dict
         play(record_obs=True) returns: the same keys, dtypes, shapes and fill values (action -1 and everything
         else 0 at rows past an episode's end, reward as float64 through HanoiBatch.reward_value, active derived
         from steps), the record trimmed to max(steps) rows -- the call's one host read.
@@ -295,12 +298,21 @@ class BatchedSelfPlay:
         legacy_rng = True (B = 1 only, without draws): the table is rng.predraw(T) from NumPy's global stream;
         after the launch the stream is put back and advanced by rng.predraw(steps), so it is left exactly
         where play(legacy_rng=True) leaves it.
+        weights: how a NetworkSet's engine picks up changed parameters (networks.engine_for_set).
         RuntimeError if the kernel refused a start state (a peg outside 0..2: not reachable from start_idx)."""
         start = np.asarray(start_idx, np.int64).reshape(-1)
         B, T = int(start.shape[0]), int(self.max_steps)
         kw = dict(deterministic=deterministic, alpha=self.alpha, eps=self.eps)
-        if isinstance(self.network, (NetworkSet, RecordedNetwork)):
-            raise ValueError("play_episodes: one live network only (no NetworkSet, no RecordedNetwork)")
+        if isinstance(self.network, RecordedNetwork):
+            raise ValueError("play_episodes: live networks only (no RecordedNetwork)")
+        multi = isinstance(self.network, NetworkSet)
+        if multi != (net_index is not None):
+            raise ValueError("play_episodes: net_index [B] is required with a NetworkSet and only accepted with one")
+        if multi:
+            ni = np.asarray(net_index, np.int64).reshape(-1)
+            if ni.shape[0] != B or (B and (ni.min() < 0 or ni.max() >= len(self.network) or np.any(np.diff(ni) < 0))):
+                raise ValueError(f"play_episodes: net_index must be {B} non-decreasing indices into the set of "
+                                 f"{len(self.network)}")
         if legacy_rng and (B != 1 or draws is not None):
             raise ValueError("play_episodes: legacy_rng=True is the one-env schedule: it needs B = 1 and draws=None, "
                              f"got B = {B}")
@@ -309,7 +321,8 @@ class BatchedSelfPlay:
         if draws is not None:
             draws = _episode_draws(draws, T, B, _rng.uses_noise(**kw), not deterministic)
         if B == 0:  # nothing to play and (a checked [T, 0] table) nothing to draw: play's empty records
-            return self.play(start, temperature, deterministic, seed, legacy_rng, minmax, record_obs=True)
+            return self.play(start, temperature, deterministic, seed, legacy_rng, minmax, record_obs=True,
+                             net_index=net_index)
         state0 = None
         if draws is None:  # one flat draw of T * B rows, row t * B + b for move t of env b
             if legacy_rng:
@@ -318,16 +331,7 @@ class BatchedSelfPlay:
             draws = tuple(None if x is None else torch.from_numpy(x).reshape((T, B) + x.shape[1:]) for x in flat)
         t_max = 0
         try:
-            eng = engine_for(self.network, self.S, B)
-            dev = eng.device
-            noise, tie, u = (None if x is None else x.to(dev) for x in draws)
-            pw = 3 ** np.arange(self.N - 1, -1, -1, dtype=np.int64)
-            state = torch.from_numpy(((start[:, None] // pw) % 3).astype(np.uint8)).to(dev)
-            mm = None if minmax is None else torch.as_tensor(np.asarray(minmax, np.float64)).reshape(B, 2).to(dev)
-            out = eng.play_episodes(self.S, state, T, tie_idx=tie, noise=noise, action_u=u, minmax_in=mm,
-                                    goal_peg=self.goal_peg, temperature=float(temperature),
-                                    deterministic=bool(deterministic), discount=self.discount, eps=self.eps,
-                                    np1_ucb=self.np1_ucb, record_obs=True)
+            out = self._launch_episodes(start, draws, minmax, temperature, deterministic, ni if multi else None, weights)
             steps = out["steps"]
             t_max, n_err = (int(x) for x in torch.stack([steps.max(), out["err"][0]]).cpu())  # the one host read
         finally:
@@ -336,10 +340,24 @@ class BatchedSelfPlay:
                 _rng.predraw(t_max, **kw)
         if n_err:
             raise RuntimeError(f"mzh_play_episodes refused {n_err} start state(s)")
-        active = torch.arange(t_max, device=dev)[:, None] < steps[None, :]
-        return dict(action=out["action"][:t_max], reward=HanoiBatch.reward_value(out["reward"][:t_max]),
-                    pi=out["pi"][:t_max], root_q=out["root_q"][:t_max], active=active, obs=out["obs"][:t_max],
-                    steps=steps, illegal=out["illegal"], start_idx=torch.from_numpy(start).to(dev), minmax=out["minmax"])
+        return episodes_result(out, start, t_max)
+
+    def _launch_episodes(self, start, draws, minmax, temperature, deterministic, net_index, weights="auto"):
+        """play_episodes' launch, without its host read: Engine.play_episodes' dict for the starts `start` (int64
+        array [B]) on the checked table `draws`; net_index: an int64 array [B] with a NetworkSet, else None"""
+        B, T = int(start.shape[0]), int(self.max_steps)
+        multi = net_index is not None
+        eng = engine_for_set(self.network, self.S, B, weights=weights) if multi else engine_for(self.network, self.S, B)
+        dev = eng.device
+        noise, tie, u = (None if x is None else x.to(dev) for x in draws)
+        pw = 3 ** np.arange(self.N - 1, -1, -1, dtype=np.int64)
+        state = torch.from_numpy(((start[:, None] // pw) % 3).astype(np.uint8)).to(dev)
+        mm = None if minmax is None else torch.as_tensor(np.asarray(minmax, np.float64)).reshape(B, 2).to(dev)
+        return eng.play_episodes(self.S, state, T, tie_idx=tie, noise=noise, action_u=u, minmax_in=mm,
+                                 goal_peg=self.goal_peg, temperature=float(temperature),
+                                 deterministic=bool(deterministic), discount=self.discount, eps=self.eps,
+                                 np1_ucb=self.np1_ucb, record_obs=True,
+                                 net_index=torch.from_numpy(net_index.astype(np.int32)) if multi else None)
 
     def play_plans(self, start_idx, max_plan_len, temperature=1.0, deterministic=False, seed=0, legacy_rng=False,
                    minmax=None, net_index=None):
@@ -460,6 +478,18 @@ class BatchedSelfPlay:
             run.advance("mzh_env_step_observe", mzh_probe_actions=err)
             t += 1
         return dict(reward=rec_r[:t], value=rec_v[:t], legal=rec_l[:t], action=rec_a[:t], steps=env.steps_total)
+
+
+def episodes_result(out, start, t_max, cols=slice(None)):
+    """play(record_obs=True)'s dict from Engine.play_episodes' `out` for the envs `cols` (a slice of the batch; start:
+    their start indices, an int64 array), the record trimmed to t_max >= max(steps[cols]) rows"""
+    dev = out["steps"].device
+    steps = out["steps"][cols]
+    active = torch.arange(t_max, device=dev)[:, None] < steps[None, :]
+    return dict(action=out["action"][:t_max, cols], reward=HanoiBatch.reward_value(out["reward"][:t_max, cols]),
+                pi=out["pi"][:t_max, cols], root_q=out["root_q"][:t_max, cols], active=active,
+                obs=out["obs"][:t_max, cols], steps=steps, illegal=out["illegal"][cols],
+                start_idx=torch.from_numpy(np.asarray(start, np.int64)).to(dev), minmax=out["minmax"][cols])
 
 
 def _episode_draws(draws, T, B, noisy, stochastic):
@@ -688,7 +718,7 @@ def _batch_starts(n_disks, episodes, start, start_idx, seed, goal_peg):
 
 def evaluate_networks(networks, n_disks, n_sims_range, *, episodes=1, start=None, start_idx=None, max_steps=200,
                       temperature=1.0, deterministic=False, seed=0, goal_peg=2, np1_ucb=False, max_plan_len=None,
-                      dirichlet_alpha=0.25, max_roots=65536):
+                      dirichlet_alpha=0.25, max_roots=65536, launch="lockstep"):
     """evaluate's batched schedule for several networks at once -- the variants of an ablation sweep
     (checkpoint.ablation_variants; the reference runs acting_ablations.py once per variant): per budget one
     batch of len(networks) * episodes envs, network m's episodes consecutive and every network given the same
@@ -696,10 +726,17 @@ def evaluate_networks(networks, n_disks, n_sims_range, *, episodes=1, start=None
     launch per move.  A batch above max_roots envs is played as several.  Every episode is its own agent with
     a fresh MinMaxStats and its own synthetic draws (the draws of env b of the batch: not those evaluate
     would give network m's episode alone).
+    launch: "lockstep" (that move loop) or "episodes": each batch to its end in one launch
+    (BatchedSelfPlay.play_episodes over the set, its draw schedule: env b takes row [t, b] of one table drawn from
+    the batch's seed); search-per-step episodes only, so not with max_plan_len.
     networks: a networks.NetworkSet or a sequence of networks.  Returns a list with, per network, the dict
     evaluate returns (minmax None), scored by the same code."""
     nset = _network_set("evaluate_networks", networks)
     _check_plan("evaluate_networks", max_plan_len, n_sims_range)
+    if launch not in ("lockstep", "episodes"):
+        raise ValueError(f"evaluate_networks: launch must be 'lockstep' or 'episodes', not {launch!r}")
+    if launch == "episodes" and max_plan_len is not None:
+        raise ValueError("evaluate_networks: launch='episodes' plays a search per step: it has no max_plan_len form")
     if int(max_roots) < 1:
         raise ValueError(f"evaluate_networks: max_roots must be >= 1, got {max_roots}")
     M = len(nset)
@@ -708,6 +745,8 @@ def evaluate_networks(networks, n_disks, n_sims_range, *, episodes=1, start=None
         sp = BatchedSelfPlay(nset, n_disks, max_steps, int(n), goal_peg=goal_peg, np1_ucb=np1_ucb,
                              dirichlet_alpha=dirichlet_alpha)
         play = sp.play if max_plan_len is None else (lambda s, **kw: sp.play_plans(s, int(max_plan_len), **kw))
+        if launch == "episodes":
+            play = sp.play_episodes
         starts = _batch_starts(n_disks, episodes, start, start_idx, seed, goal_peg)
         E = len(starts)
         all_starts, net_index = np.tile(starts, M), np.repeat(np.arange(M), E)
