@@ -705,6 +705,52 @@ int mzh_replay_set_priorities(float* prio, int64_t size, const int64_t* indx, co
                               int32_t* status, mzh_stream stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * One update round of a set of M networks: for every active network m, what mzh_replay_sample (draw[m]) +
+ * mzh_train_update (train[m]) + mzh_replay_set_priorities (prio, size of the ring, indx, train[m].new_prio) do
+ * one after the other, as FOUR launches for the whole set -- the draws (grid M), the row kernel (grid rows x M),
+ * the gradient / Adam kernel (grid tiles x M), the write-backs (grid M).  Every network ends bit for bit as its
+ * three lone calls end: the kernels are the lone calls' own bodies with their arguments read from a table.
+ *
+ * mzh_train_set_create copies the shapes and uploads the table of the 2 M argument blocks once; EVERY pointer in
+ * them is fixed for the handle's life: parameters, moments, wt, scratch, row_loss, new_prio, the ring arrays,
+ * prio, cdf, indx and the draw's out_* buffers, which must be the very buffers train[m] names as obs / rwds /
+ * actions / pi / returns (a network's draw feeds its own update).  beta1, beta2 and eps are taken per network at
+ * creation; the per-call fields train[m].step_size / bc2_sqrt and draw[m].u / status are ignored, and draw[m].n
+ * is here the ring's SIZE (the length of prio and cdf, Buffer.size): the write-back's index bound and the upper
+ * bound of every round's n.
+ * MZH_ERR_ARG, before the device is touched: a NULL train, draw or out; M outside
+ * [1, MZH_TRAIN_SET_MAX]; networks that differ in B, U, in_dim, support or rows; draw[m].m != B,
+ * draw[m].d_state != in_dim, draw[m].U != U, draw[m].A != 6; an out_* pointer that is not the matching train
+ * input; a NULL new_prio; whatever mzh_train_update refuses of train[m] and mzh_replay_sample of draw[m] (u and
+ * status apart).  The message names the field and the network.
+ *
+ * mzh_train_set_update makes one round.  All three arrays are read (status: written) by the KERNELS WHEN THEY RUN,
+ * not at call time, so they must be device-readable and stay unchanged until the stream has passed the call:
+ *   step [M]      : per network {active, n = len(buffer), step_size, bc2_sqrt of this Adam step}.  The host reads
+ *                   active and n at call time as well (to launch nothing for a round without an active network,
+ *                   and to refuse an active n outside [1, ring size] with MZH_ERR_ARG), so this pointer must be
+ *                   valid on both sides: mapped page-locked memory, whose host and device addresses coincide.
+ *   u [M][B]      : the draws' uniforms (np.random.random_sample(B) per network), device-readable
+ *   status [M][4] : device-written (out), row m only if network m is active: [0] the draw's status, [1] its
+ *                   exact-scan flag, [2] the write-back's status (mzh_replay_sample / _set_priorities), [3] 0
+ * A network with step[m].active == 0 is skipped by all four kernels: nothing of it is read or written, its
+ * status row included.  MZH_ERR_ARG for a NULL step, u, status or set.  With no active network the call launches
+ * nothing and returns MZH_OK; otherwise exactly four launches on the stream, no synchronisation.
+ * mzh_train_transpose stays per network (needed only after parameters were written from outside).
+ * ------------------------------------------------------------------------------------------- */
+#define MZH_TRAIN_SET_MAX 256
+typedef struct mzh_train_set_step {
+  int32_t active, n;
+  float step_size, bc2_sqrt;
+} mzh_train_set_step;
+typedef struct mzh_train_set mzh_train_set;
+
+int mzh_train_set_create(const mzh_train_args* train, const mzh_replay_args* draw, int M, mzh_train_set** out);
+int mzh_train_set_destroy(mzh_train_set* set);
+int mzh_train_set_update(mzh_train_set* set, const mzh_train_set_step* step, const double* u, int32_t* status,
+                         mzh_stream stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Episode ingest: the record of one batched lockstep self-play run (BatchedSelfPlay.play with
  * record_obs, T recorded steps of B envs) into the replay ring, for TD_return=True.  Replaces, per
  * episode, compute_n_step_returns (utils.py:28-69), the priorities |return - root Q| in float32

@@ -104,6 +104,14 @@ class ReplayArgs(ctypes.Structure):
                 ("out_actions", _vp), ("out_pi", _vp), ("out_returns", _vp), ("status", _vp)]
 
 
+class TrainSetStep(ctypes.Structure):
+    """mirror of struct mzh_train_set_step (include/mzh.h)"""
+    _fields_ = [("active", _i32), ("n", _i32), ("step_size", ctypes.c_float), ("bc2_sqrt", ctypes.c_float)]
+
+
+TRAIN_SET_MAX = 256  # MZH_TRAIN_SET_MAX
+
+
 class IngestArgs(ctypes.Structure):
     """mirror of struct mzh_ingest_args (include/mzh.h)"""
     _fields_ = [("B", _i32), ("T", _i32), ("d_state", _i32), ("U", _i32), ("A", _i32), ("n_step", _i32),
@@ -216,6 +224,10 @@ SIGNATURES = {
     "mzh_train_update": (ctypes.c_int, [ctypes.POINTER(TrainArgs), _vp]),
     "mzh_replay_sample": (ctypes.c_int, [ctypes.POINTER(ReplayArgs), _vp]),
     "mzh_replay_set_priorities": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, ctypes.c_int, _vp, _vp]),
+    "mzh_train_set_create": (ctypes.c_int, [ctypes.POINTER(TrainArgs), ctypes.POINTER(ReplayArgs), ctypes.c_int,
+                                            ctypes.POINTER(_vp)]),
+    "mzh_train_set_destroy": (ctypes.c_int, [_vp]),
+    "mzh_train_set_update": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "mzh_episode_ingest": (ctypes.c_int, [ctypes.POINTER(IngestArgs), _vp]),
     "mzh_play_episodes": (ctypes.c_int, [_vp, ctypes.POINTER(EpisodeArgs), _vp]),
     "mzh_play_episodes_multi": (ctypes.c_int, [_vp, ctypes.POINTER(EpisodeArgs), ctypes.POINTER(MultiArgs), _vp]),

@@ -22,6 +22,8 @@
 // the whole workgroup, every load independent.  One 1,024-thread workgroup: at the
 // reference's buffer (50,000 transitions) the draw is a few latency-bound passes over 200 KB; one launch
 // replaces the host's NumPy passes and the index and weight uploads.
+// The draw and the write-back each have a set form (grid M, workgroup m = network m of a table in device memory;
+// mzh_train_set_update) that runs the same body as the one-network kernel.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -217,9 +219,23 @@ __device__ __forceinline__ double rdiv(double a, double b, double y) {
   return __builtin_fma(__builtin_fma(-q, b, a), y, q);
 }
 
-__global__ __launch_bounds__(RT) void replay_sample_kernel(mzh_replay_args a) {
+// Where a launch's arguments come from (mzh_train.hip has the same pair for the update's kernels): the one-draw
+// kernel takes its mzh_replay_args as the kernel argument; the set kernel takes row blockIdx.x of a table in
+// device memory, read through the constant address space (written once by the host: every field a scalar load
+// wherever it is used), with n, the uniforms and the status row from the call.  One body serves both.
+template <class T>
+using MzrTableRow = const __attribute__((address_space(4))) T;
+template <class T>
+__device__ __forceinline__ MzrTableRow<T>& mzr_table_row(const T* table, int m) {
+  return ((MzrTableRow<T>*)table)[m];
+}
+
+// the draw of one workgroup: a = the ring, workspace and outputs; n = len(buffer); u [a.m] the uniforms;
+// status [2] (STAMPS: a diagnostic build's phase stamps behind them, the one-draw kernel only)
+template <bool STAMPS, class Args>
+__device__ __forceinline__ void replay_sample_body(Args& a, const int n, const double* u, int32_t* status) {
   __shared__ ReplayLds L;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = a.n, m = a.m;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, m = a.m;
   const float* p = a.prio;
 #ifdef MZH_STAMPS
   unsigned long long stamp[8] = {};
@@ -373,8 +389,8 @@ __global__ __launch_bounds__(RT) void replay_sample_kernel(mzh_replay_args a) {
     }
   }
   if (tid == 0) {
-    a.status[0] = valid ? 0 : 1;
-    a.status[1] = valid && exact ? 1 : 0;
+    status[0] = valid ? 0 : 1;
+    status[1] = valid && exact ? 1 : 0;
   }
   __syncthreads();
 
@@ -390,7 +406,7 @@ __global__ __launch_bounds__(RT) void replay_sample_kernel(mzh_replay_args a) {
     __syncthreads();
     MZR_STAMP(5)
     for (int k = tid; k < m; k += RT) {
-      const double uk = a.u[k];
+      const double uk = u[k];
       int lo = 0, hi = nc - 1;  // the first sample above uk (the last one is 1.0 > uk)
       while (lo < hi) {
         const int mid = (lo + hi) >> 1;
@@ -457,13 +473,26 @@ __global__ __launch_bounds__(RT) void replay_sample_kernel(mzh_replay_args a) {
 #ifdef MZH_STAMPS
   __syncthreads();
   MZR_STAMP(7)
-  if (tid == 0)
-    for (int k = 0; k < 8; ++k) a.status[2 + k] = (int32_t)(stamp[k] - stamp[0]);
+  if (STAMPS && tid == 0)
+    for (int k = 0; k < 8; ++k) status[2 + k] = (int32_t)(stamp[k] - stamp[0]);
 #endif
 }
 
-__global__ __launch_bounds__(RT) void replay_set_priorities_kernel(float* prio, long long size, const int64_t* idx,
-                                                                   const float* val, int m, int32_t* status) {
+__global__ __launch_bounds__(RT) void replay_sample_kernel(mzh_replay_args a) {
+  replay_sample_body<true>(a, a.n, a.u, a.status);
+}
+
+__global__ __launch_bounds__(RT) void replay_sample_set_kernel(MztSetParams v) {
+  const int m = blockIdx.x;
+  if (!v.step[m].active) return;
+  auto& a = mzr_table_row(v.draw, m);
+  int32_t* status = v.status + 4 * m;
+  if (threadIdx.x == 0) status[3] = 0;
+  replay_sample_body<false>(a, v.step[m].n, v.u + (size_t)m * a.m, status);
+}
+
+__device__ __forceinline__ void replay_set_priorities_body(float* prio, long long size, const int64_t* idx,
+                                                           const float* val, int m, int32_t* status) {
   __shared__ long long sidx[MZR_MAX_BATCH];
   const int tid = threadIdx.x;
   int fin = 1, pos = 0, inr = 1;
@@ -497,6 +526,18 @@ __global__ __launch_bounds__(RT) void replay_set_priorities_kernel(float* prio, 
   }
 }
 
+__global__ __launch_bounds__(RT) void replay_set_priorities_kernel(float* prio, long long size, const int64_t* idx,
+                                                                   const float* val, int m, int32_t* status) {
+  replay_set_priorities_body(prio, size, idx, val, m, status);
+}
+
+__global__ __launch_bounds__(RT) void replay_set_priorities_set_kernel(MztSetParams v) {
+  const int m = blockIdx.x;
+  if (!v.step[m].active) return;
+  auto& a = mzr_table_row(v.prio, m);
+  replay_set_priorities_body(a.prio, a.size, a.idx, a.val, a.m, v.status + 4 * m + 2);
+}
+
 }  // namespace
 
 hipError_t mzr_launch_sample(const mzh_replay_args& a, hipStream_t stream) {
@@ -507,5 +548,15 @@ hipError_t mzr_launch_sample(const mzh_replay_args& a, hipStream_t stream) {
 hipError_t mzr_launch_set_priorities(float* prio, long long size, const int64_t* idx, const float* val, int m,
                                      int32_t* status, hipStream_t stream) {
   hipLaunchKernelGGL(replay_set_priorities_kernel, dim3(1), dim3(RT), 0, stream, prio, size, idx, val, m, status);
+  return hipGetLastError();
+}
+
+hipError_t mzr_launch_sample_set(int M, const MztSetParams& v, hipStream_t stream) {
+  hipLaunchKernelGGL(replay_sample_set_kernel, dim3(M), dim3(RT), 0, stream, v);
+  return hipGetLastError();
+}
+
+hipError_t mzr_launch_set_priorities_set(int M, const MztSetParams& v, hipStream_t stream) {
+  hipLaunchKernelGGL(replay_set_priorities_set_kernel, dim3(M), dim3(RT), 0, stream, v);
   return hipGetLastError();
 }

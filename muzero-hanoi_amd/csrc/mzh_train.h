@@ -61,7 +61,35 @@ struct MztGradParams {
   float step_size, bc2_sqrt, beta1, beta2, eps;
 };
 
+// ---- the set forms (mzh_train_set_update): the grid's y index (x for the one-workgroup kernels) is the network,
+// whose arguments are row m of a table in device memory, written once when the set is created and never by a
+// kernel; what changes from call to call is the per-call record step[m] (mzh_train_set_step of mzh.h: active, n,
+// step_size, bc2_sqrt), read by the kernels when they run.  A workgroup of an inactive network returns before its
+// first barrier and touches nothing of that network.
+struct MzrPrioArgs {  // replay_set_priorities_kernel's arguments of one network
+  float* prio;
+  long long size;
+  const int64_t* idx;
+  const float* val;
+  int m;
+};
+
+struct MztSetParams {
+  const mzh_replay_args* draw;  // [M]  n, u and status unused: they come from step, u + m * batch, status + 4 m
+  const MztRowParams* rows;     // [M]
+  const MztGradParams* grad;    // [M]  step_size and bc2_sqrt unused: they come from step
+  const MzrPrioArgs* prio;      // [M]
+  const mzh_train_set_step* step;  // [M]
+  const double* u;              // [M][batch]
+  int32_t* status;              // [M][4]: draw status, exact-scan flag, set-priorities status, zero
+};
+
 size_t mzt_rows_smem_bytes(int rows, int U);
+hipError_t mzt_rows_set_prepare(int rows, int support, int U);  // the set form's dynamic LDS limit, once per set
+hipError_t mzt_launch_rows_set(int rows, int support, int B, int U, int M, const MztSetParams& v, hipStream_t stream);
+hipError_t mzt_launch_grad_adam_set(int n_tiles, int M, const MztSetParams& v, hipStream_t stream);
+hipError_t mzr_launch_sample_set(int M, const MztSetParams& v, hipStream_t stream);
+hipError_t mzr_launch_set_priorities_set(int M, const MztSetParams& v, hipStream_t stream);
 hipError_t mzt_launch_rows(int rows, int support, const MztRowParams& p, hipStream_t stream);
 hipError_t mzt_launch_grad_adam(const MztGradParams& P, int n_tiles, hipStream_t stream);
 hipError_t mzt_launch_transpose(const float* W, float* WT, int out, int in, int ldwt, hipStream_t stream);

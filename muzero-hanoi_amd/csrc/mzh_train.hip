@@ -17,6 +17,10 @@
 //       moment, second moment, sqrt / bias-correction / eps, addcdiv) in place on the torch
 //       parameter and state tensors, and the transposed weight copy refreshed.
 //
+// Both kernels have a set form (mzt_rows_set_kernel, mzt_grad_adam_set_kernel; mzh_train_set_update): the grid's y
+// index is the network, whose parameter block is a row of a table in device memory, and a network that is
+// inactive in the call is skipped.  The single and the set forms run one body each.
+//
 // The arithmetic is fp32 like torch's; sums run in other orders than hipBLASLt / torch-CPU, so
 // results agree with the reference to fp32 rounding (tests/test_training.py), not bit for bit.
 #include <hip/hip_runtime.h>
@@ -182,8 +186,20 @@ struct RowLds {
   __device__ __host__ static size_t bytes(int U) { return sizeof(float) * (size_t)(fixed() + U * per_step()); }
 };
 
-template <int R, int SUP>
-__global__ __launch_bounds__(RNT, 1) void mzt_rows_kernel(MztRowParams p) {
+// Where a launch's arguments come from.  The one-network kernels take their parameter block as the kernel
+// argument; the set kernels take row blockIdx.y of a table in device memory, read through the constant address
+// space: the table is written once by the host, so every field is a scalar load wherever it is used, as a kernel
+// argument's is.  Both hand the block to the one body below, which is templated on the block's type only because
+// the address space is part of it.
+template <class T>
+using MztTableRow = const __attribute__((address_space(4))) T;
+template <class T>
+__device__ __forceinline__ MztTableRow<T>& mzt_table_row(const T* table, int m) {
+  return ((MztTableRow<T>*)table)[m];
+}
+
+template <int R, int SUP, class RowParams>
+__device__ __forceinline__ void mzt_rows_body(RowParams& p) {
   extern __shared__ float lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int U = p.U, B = p.B;
@@ -224,8 +240,8 @@ __global__ __launch_bounds__(RNT, 1) void mzt_rows_kernel(MztRowParams p) {
   auto s_lr = [&](int t) { return st + t * PS + 4 * R * F + R * H + R * 56; };     // [R][48]
   auto s_vr = [&](int t) { return st + t * PS + 4 * R * F + R * H + R * 104; };    // [2][R] v_t, r_t
 
-  const MztNet& n = p.n;
-  const MztScratch& s = p.s;
+  auto& n = p.n;
+  auto& s = p.s;
   auto rowb = [&](int r) { return min(b0 + r, B - 1); };
   auto valid = [&](int r) { return b0 + r < B; };
 
@@ -547,11 +563,29 @@ __global__ __launch_bounds__(RNT, 1) void mzt_rows_kernel(MztRowParams p) {
   }
 }
 
+template <int R, int SUP>
+__global__ __launch_bounds__(RNT, 1) void mzt_rows_kernel(MztRowParams p) {
+  mzt_rows_body<R, SUP>(p);
+}
+
+template <int R, int SUP>
+__global__ __launch_bounds__(RNT, 1) void mzt_rows_set_kernel(MztSetParams v) {
+  const int m = blockIdx.y;
+  if (!v.step[m].active) return;
+  mzt_rows_body<R, SUP>(mzt_table_row(v.rows, m));
+}
+
 // ------------------------------------------------------------------------------------------
 // weight gradients + Adam: one workgroup per 16x16 tile of one Linear layer
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ void adam(float* pp, float* mm, float* vv, size_t i, float g, const MztGradParams& P) {
+// this step's Adam scalars: a lone update's come with its parameter block, a set's step_size and bc2_sqrt from
+// the network's per-call record (the networks of a set sit at different Adam steps)
+struct MztAdam {
+  float step_size, bc2_sqrt, beta1, beta2, eps;
+};
+
+__device__ __forceinline__ void adam(float* pp, float* mm, float* vv, size_t i, float g, const MztAdam& P) {
   float m = mm[i], v = vv[i];
   m = m + (1.0f - P.beta1) * (g - m);           // exp_avg.lerp_(grad, 1 - beta1)
   v = v * P.beta2 + (1.0f - P.beta2) * (g * g);  // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
@@ -562,14 +596,15 @@ __device__ __forceinline__ void adam(float* pp, float* mm, float* vv, size_t i, 
 }
 
 constexpr int NW2 = 16;  // waves per weight tile: they split the B*U rows
-__global__ __launch_bounds__(64 * NW2) void mzt_grad_adam_kernel(MztGradParams P) {
+template <class GradParams>
+__device__ __forceinline__ void mzt_grad_adam_body(GradParams& P, const MztAdam& ad) {
   constexpr int NP = 4 * NW2;  // bias row classes (16 columns x NP)
   __shared__ float red[NW2][16][17];
   __shared__ float bred[NP][17];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int li = 0;
   while (li < 9 && (int)blockIdx.x >= P.L[li + 1].tile0) ++li;
-  const MztGradLayer& L = P.L[li];
+  auto& L = P.L[li];
   const int tile = blockIdx.x - L.tile0;
   const int ob = tile / L.nkb, kb = tile - ob * L.nkb;
   const int o0 = ob * 16, k0 = kb * 16;
@@ -628,15 +663,26 @@ __global__ __launch_bounds__(64 * NW2) void mzt_grad_adam_kernel(MztGradParams P
 #pragma unroll
       for (int w = 0; w < NW2; ++w) g += red[w][i][j];
       const size_t idx = (size_t)o * L.in + k;
-      adam(L.W, L.mW, L.vW, idx, g, P);
+      adam(L.W, L.mW, L.vW, idx, g, ad);
       L.WT[(size_t)k * L.ldwt + o] = L.W[idx];
     }
   }
   if (kb == 0 && tid < 16 && o0 + tid < L.out) {
     float g = 0.f;
     for (int part = 0; part < NP; ++part) g += bred[part][tid];
-    adam(L.b, L.mb, L.vb, o0 + tid, g, P);
+    adam(L.b, L.mb, L.vb, o0 + tid, g, ad);
   }
+}
+
+__global__ __launch_bounds__(64 * NW2) void mzt_grad_adam_kernel(MztGradParams P) {
+  mzt_grad_adam_body(P, MztAdam{P.step_size, P.bc2_sqrt, P.beta1, P.beta2, P.eps});
+}
+
+__global__ __launch_bounds__(64 * NW2) void mzt_grad_adam_set_kernel(MztSetParams v) {
+  const int m = blockIdx.y;
+  if (!v.step[m].active) return;
+  auto& P = mzt_table_row(v.grad, m);
+  mzt_grad_adam_body(P, MztAdam{v.step[m].step_size, v.step[m].bc2_sqrt, P.beta1, P.beta2, P.eps});
 }
 
 __global__ void mzt_transpose_kernel(const float* W, float* WT, int out, int in, int ldwt) {
@@ -657,6 +703,18 @@ hipError_t launch_rows(const MztRowParams& p, hipStream_t stream) {
   return hipGetLastError();
 }
 
+template <int R, int SUP>
+hipError_t prepare_rows_set(int U) {
+  return hipFuncSetAttribute((const void*)mzt_rows_set_kernel<R, SUP>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                             (int)RowLds<R>::bytes(U));
+}
+
+template <int R, int SUP>
+hipError_t launch_rows_set(int B, int U, int M, const MztSetParams& v, hipStream_t stream) {
+  hipLaunchKernelGGL((mzt_rows_set_kernel<R, SUP>), dim3((B + R - 1) / R, M), dim3(RNT), RowLds<R>::bytes(U), stream, v);
+  return hipGetLastError();
+}
+
 }  // namespace
 
 size_t mzt_rows_smem_bytes(int rows, int U) { return rows == 1 ? RowLds<1>::bytes(U) : RowLds<2>::bytes(U); }
@@ -664,6 +722,22 @@ size_t mzt_rows_smem_bytes(int rows, int U) { return rows == 1 ? RowLds<1>::byte
 hipError_t mzt_launch_rows(int rows, int support, const MztRowParams& p, hipStream_t stream) {
   if (support == 33) return rows == 1 ? launch_rows<1, 33>(p, stream) : launch_rows<2, 33>(p, stream);
   return rows == 1 ? launch_rows<1, 1>(p, stream) : launch_rows<2, 1>(p, stream);
+}
+
+hipError_t mzt_rows_set_prepare(int rows, int support, int U) {
+  if (support == 33) return rows == 1 ? prepare_rows_set<1, 33>(U) : prepare_rows_set<2, 33>(U);
+  return rows == 1 ? prepare_rows_set<1, 1>(U) : prepare_rows_set<2, 1>(U);
+}
+
+hipError_t mzt_launch_rows_set(int rows, int support, int B, int U, int M, const MztSetParams& v, hipStream_t stream) {
+  if (support == 33)
+    return rows == 1 ? launch_rows_set<1, 33>(B, U, M, v, stream) : launch_rows_set<2, 33>(B, U, M, v, stream);
+  return rows == 1 ? launch_rows_set<1, 1>(B, U, M, v, stream) : launch_rows_set<2, 1>(B, U, M, v, stream);
+}
+
+hipError_t mzt_launch_grad_adam_set(int n_tiles, int M, const MztSetParams& v, hipStream_t stream) {
+  hipLaunchKernelGGL(mzt_grad_adam_set_kernel, dim3(n_tiles, M), dim3(64 * NW2), 0, stream, v);
+  return hipGetLastError();
 }
 
 hipError_t mzt_launch_grad_adam(const MztGradParams& P, int n_tiles, hipStream_t stream) {

@@ -125,7 +125,9 @@ class Muzero:
             else:
                 episodes = (self._play_game(episode=n * self.n_ep_x_loop, deterministic=False)
                             for _ in range(self.n_ep_x_loop))
-            self._finish_loop(log, n, ep_steps, episodes, min_replay_size, print_acc)
+            self._ingest_loop(log, ep_steps, episodes)
+            self._update_loop(log, min_replay_size)
+            self._log_loop(log, n, print_acc)
         return log["tot_accuracy"]
 
     @staticmethod
@@ -134,13 +136,22 @@ class Muzero:
         return dict(accuracy=[], tot_accuracy=[], value_loss=[], rwd_loss=[], pi_loss=[])
 
     def _finish_loop(self, log, n, ep_steps, episodes, min_replay_size, print_acc):
-        """loop n after its self-play (Muzero.py:95-151): the successful episodes into the buffer (ep_steps: the
-        step counts of those already ingested), the loop's updates once the buffer is large enough, the log"""
+        """loop n after its self-play (Muzero.py:95-151), its three parts in order"""
+        self._ingest_loop(log, ep_steps, episodes)
+        self._update_loop(log, min_replay_size)
+        self._log_loop(log, n, print_acc)
+
+    def _ingest_loop(self, log, ep_steps, episodes):
+        """the successful episodes into the buffer (ep_steps: the step counts of those already ingested) and the
+        loop's accuracy"""
         for steps, states, rwds, actions, pi_probs, returns, priorities in episodes:
             ep_steps.append(steps)
             if returns[-1, 0] > 0:  # only successful episodes enter the buffer
                 self.buffer.add(states, rwds, actions, pi_probs, returns, priorities)
         log["accuracy"].append(sum(ep_steps) / self.n_ep_x_loop)
+
+    def _update_loop(self, log, min_replay_size):
+        """the loop's updates once the buffer is large enough, and their losses"""
         if len(self.buffer) > min_replay_size:
             for _ in range(self.n_update_x_loop):
                 if self.priority_replay:
@@ -153,6 +164,9 @@ class Muzero:
             log["value_loss"].append(v_loss)
             log["rwd_loss"].append(r_loss)
             log["pi_loss"].append(p_loss)
+
+    def _log_loop(self, log, n, print_acc):
+        """every print_acc episodes: the mean accuracy and losses since the last line"""
         if n * self.n_ep_x_loop % print_acc == 0:
             mean_acc = sum(log["accuracy"]) / print_acc
             logging.info("Loop %s | steps %.3f | V %.3f | rwd %.3f | Pi %.3f", n, mean_acc,
@@ -245,25 +259,38 @@ class MuzeroPopulation:
 
     seeds: one agent per seed, built after torch.manual_seed(seed), with its own NumPy legacy stream in the state
     np.random.seed(seed) produces.  muzero_kwargs: Muzero's, without selfplay (always "device").  weights: how the
-    set's engine picks up the agents' changed parameters every loop (networks.engine_for_set).
+    set's engine picks up the agents' changed parameters every loop (networks.engine_for_set).  update: "each" (the
+    default) or "set", the agents' update rounds as one launch sequence (SetUpdate); self.active_history then lists,
+    per loop, the agents that updated in it.
     Agent m ends exactly as torch.manual_seed(s); mz = Muzero(..., selfplay="device"); np.random.seed(s);
     mz.training_loop(...) ends: parameters, optimiser state, buffer, MinMaxStats, tot_accuracy and stream
     (self.streams[m], a np.random.get_state() tuple).  The caller's global NumPy stream is left as it was found."""
 
-    def __init__(self, seeds, *, weights="device", **muzero_kwargs):
+    def __init__(self, seeds, *, weights="device", update="each", **muzero_kwargs):
+        # update: "each" = every agent runs the lone loop's own draws, updates and write-backs one after the other;
+        # "set" = the agents' update rounds as one launch sequence for all of them (SetUpdate: four launches and one
+        # host read per loop instead of four launches and a synchronisation per agent and round), every agent still
+        # ending bit for bit as its lone run ends.  Validated before any agent is built.
+        if update not in ("each", "set"):
+            raise ValueError(f"MuzeroPopulation: update must be 'each' or 'set', not {update!r}")
+        if update == "set" and muzero_kwargs.get("update_impl", "torch") != "fused":
+            raise ValueError("MuzeroPopulation(update='set') runs the fused update of every agent in one launch "
+                             "sequence: it needs update_impl='fused' with device sampling (priority_replay on a GPU)")
         seeds = [int(s) for s in seeds]
         if not seeds:
             raise ValueError("MuzeroPopulation: no seeds")
         if muzero_kwargs.setdefault("selfplay", "device") != "device":
             raise ValueError("MuzeroPopulation trains Muzero(selfplay='device') agents: selfplay must be 'device', "
                              f"not {muzero_kwargs['selfplay']!r}")
-        self.seeds, self.weights = seeds, weights
+        self.seeds, self.weights, self.update = seeds, weights, update
         self.agents = []
         for seed in seeds:
             torch.manual_seed(seed)
             self.agents.append(Muzero(**muzero_kwargs))
         self.streams = [np.random.RandomState(seed).get_state() for seed in seeds]
         self.networks = NetworkSet([a.networks for a in self.agents])
+        self.active_history = []  # update="set": per loop, the indices of the agents that updated in it
+        self._set_update = SetUpdate(self.agents) if update == "set" else None
 
     def training_loop(self, n_loops, min_replay_size, print_acc=50):
         """Muzero.training_loop of every agent, loop by loop abreast.  Returns the list of the agents' tot_accuracy."""
@@ -292,6 +319,9 @@ class MuzeroPopulation:
                 *steps, n_err = (int(x) for x in torch.cat([out["steps"], out["err"]]).cpu())  # the one host read
                 if n_err:
                     raise RuntimeError(f"mzh_play_episodes_multi refused {n_err} start state(s)")
+                su = self._set_update
+                if su is not None:
+                    su.begin_loop()
                 for m, a in enumerate(agents):
                     cols = slice(m * E, (m + 1) * E)
                     if E == 1:  # the one-env schedule: the stream as the moves played leave it
@@ -301,8 +331,16 @@ class MuzeroPopulation:
                         np.random.set_state(self.streams[m])
                     played = a._games_played(episodes_result(out, start[cols], max(steps[cols]), cols))
                     ep_steps, episodes = ([int(s) for s in played], ()) if a.ingest == "device" else ([], played)
-                    a._finish_loop(logs[m], n, ep_steps, episodes, min_replay_size, print_acc)
+                    if su is None:
+                        a._finish_loop(logs[m], n, ep_steps, episodes, min_replay_size, print_acc)
+                    else:  # phase A: the ingest, then this loop's uniforms off the agent's stream, where a lone
+                        a._ingest_loop(logs[m], ep_steps, episodes)  # loop's updates would have drawn them
+                        su.stage(m, min_replay_size)
                     self.streams[m] = np.random.get_state()
+                if su is not None:  # phase B: every round of every agent, one synchronisation, then the logs
+                    self.active_history.append(su.run(logs))
+                    for m, a in enumerate(agents):
+                        a._log_loop(logs[m], n, print_acc)
         finally:
             np.random.set_state(caller)
         return [log["tot_accuracy"] for log in logs]
@@ -558,3 +596,170 @@ class FusedUpdate:
         means = self.row_loss.mean(0)
         newp = None if w is None else (newp_t if on_dev else newp_t.cpu().numpy())
         return newp, means[0], means[1], means[2]
+
+
+class SetUpdate:
+    """The update rounds of several agents (update_impl="fused", device sampling) as one launch sequence
+    (mzh_train_set_update, csrc/mzh_replay.hip + csrc/mzh_train.hip): per round the draws, the row kernel, the
+    gradient / Adam kernel and the priority write-backs of ALL active agents are four launches, the network on the
+    grid's y (or x) index, and a loop ends with one synchronisation and one read of the status words.  Every agent
+    ends bit for bit as its own priority_sample + FusedUpdate + update_priorities end: the kernels run the lone
+    calls' bodies, and the uniforms come off the agent's NumPy stream in the lone loop's order (nothing else draws
+    between a loop's updates).
+
+    The handle fixes every pointer: each agent's sampled batch, indices and new priorities are allocated once here
+    (a lone update allocates them per call), row_loss is one [M][B][3] tensor (the logged losses are one batched
+    mean over it), the importance weights are the buffer's ones.  The per-round records, uniforms and status words
+    sit in mapped page-locked memory, one slot per round of a loop, rewritten only after the loop's
+    synchronisation.  Agents whose buffer is still too small are inactive in a loop: the kernels skip them."""
+
+    STEP = np.dtype([("active", np.int32), ("n", np.int32), ("step_size", np.float32), ("bc2_sqrt", np.float32)])
+
+    def __init__(self, agents):
+        from . import _lib
+
+        for a in agents:
+            if not isinstance(a._graphed, FusedUpdate) or not getattr(a.buffer, "device_sampling", False):
+                raise ValueError("MuzeroPopulation(update='set') needs update_impl='fused' with device sampling on "
+                                 "every agent (priority_replay on a GPU, device_sampling not switched off)")
+        if len(agents) > _lib.TRAIN_SET_MAX:
+            raise ValueError(f"MuzeroPopulation(update='set'): {len(agents)} agents, at most {_lib.TRAIN_SET_MAX}")
+        self._lib, self.agents = _lib, agents
+        self.M, self.R, self.B = len(agents), int(agents[0].n_update_x_loop), int(agents[0].batch_s)
+        self.dev = agents[0].buffer.dev
+        M, R, B = self.M, self.R, self.B
+        self.step = torch.zeros((R, M, 4), dtype=torch.int32, pin_memory=True)
+        self.step_np = self.step.numpy().view(self.STEP).reshape(R, M)
+        self.u = torch.zeros((R, M, B), dtype=torch.float64, pin_memory=True)
+        self.u_np = self.u.numpy()
+        self.status = torch.zeros((R, M, 4), dtype=torch.int32, pin_memory=True)
+        self.status_np = self.status.numpy()
+        self.step_dev, self.u_dev, self.status_dev = (_lib.host_device_pointer(t.data_ptr())
+                                                      for t in (self.step, self.u, self.status))
+        if self.step_dev != self.step.data_ptr():  # the host reads the records through the same pointer (mzh.h)
+            raise RuntimeError("SetUpdate: page-locked memory has different host and device addresses")
+        self.handle, self._key = None, None
+        self.active, self.final_step = [], {}
+
+    def __del__(self):
+        try:
+            self._destroy()
+        except Exception:  # interpreter shutdown: the library may be gone before the handle
+            pass
+
+    def _destroy(self):
+        if getattr(self, "handle", None) is not None:
+            self._lib.lib().mzh_train_set_destroy(self.handle)
+            self.handle = None
+
+    def _ready(self, a):
+        """the agent's FusedUpdate set up for this batch size (its argument block, scratch, Adam state views)"""
+        fu = a._graphed
+        if fu._a is None or fu.B != self.B or fu._state_key != fu._state_identity():
+            fu._setup(self.B, self.dev)
+        return fu
+
+    def _identity(self):
+        return tuple((id(a._graphed._a), a._graphed._state_key, a.buffer._dev_replay.m) for a in self.agents)
+
+    def _build(self):
+        L, M, B, dev = self._lib, self.M, self.B, self.dev
+        self._destroy()
+        train, draw = (L.TrainArgs * M)(), (L.ReplayArgs * M)()
+        self.row_loss = torch.zeros((M, B, 3), dtype=torch.float32, device=dev)
+        self.keep = []  # the tensors the handle's pointers name
+        for m, a in enumerate(self.agents):
+            fu, buf = self._ready(a), a.buffer
+            dr = buf._dev_replay
+            if dr.m != B:
+                dr.check_pending(block=True)
+                dr._alloc_u(B)
+            U, A = buf.unroll_n_steps, buf.n_action
+            outs = (torch.zeros((B, buf.d_state), dtype=torch.float32, device=dev),
+                    torch.zeros((B, U), dtype=torch.float32, device=dev),
+                    torch.zeros((B, U), dtype=torch.int64, device=dev),
+                    torch.zeros((B, U, A), dtype=torch.float32, device=dev),
+                    torch.zeros((B, U), dtype=torch.float32, device=dev))
+            indx = torch.zeros(B, dtype=torch.int64, device=dev)
+            newp = torch.zeros(B, dtype=torch.float32, device=dev)
+            self.keep.append((outs, indx, newp, dr.ones))
+            g = a.networks.optimiser.param_groups[0]
+            train[m] = fu._a  # a copy: parameters, moments, transposed copies, scratch
+            t = train[m]
+            t.obs, t.rwds, t.actions, t.pi, t.returns = (x.data_ptr() for x in outs)
+            t.weights, t.row_loss, t.new_prio = dr.ones.data_ptr(), self.row_loss[m].data_ptr(), newp.data_ptr()
+            (t.beta1, t.beta2), t.eps = g["betas"], g["eps"]
+            t.step_size = t.bc2_sqrt = 0.0  # per round
+            draw[m] = dr.args  # a copy: the ring arrays, prio, cdf
+            d = draw[m]
+            d.n, d.u, d.status = buf.size, None, None  # the ring's size; n, u and status come per round
+            d.indx = indx.data_ptr()
+            d.out_states, d.out_rwds, d.out_actions, d.out_pi, d.out_returns = (x.data_ptr() for x in outs)
+        h = ctypes.c_void_p()
+        L.check(L.lib().mzh_train_set_create(train, draw, M, ctypes.byref(h)), "mzh_train_set_create")
+        self.handle, self._key = h, self._identity()
+        self._train, self._draw = train, draw  # what the handle was made from (tools/bench_population_update.py)
+
+    def begin_loop(self):
+        self.active, self.final_step = [], {}
+        self.step_np["active"][...] = 0
+
+    def stage(self, m, min_replay_size):
+        """agent m after its ingest, the global NumPy stream being its own: if its buffer is large enough, this
+        loop's uniforms and Adam scalars (fp64, as FusedUpdate computes them) into the rounds' slots"""
+        a = self.agents[m]
+        n = len(a.buffer)
+        if not n > min_replay_size:
+            return
+        fu = self._ready(a)
+        g = a.networks.optimiser.param_groups[0]
+        beta1, beta2 = g["betas"]
+        step0 = float(fu._step_views[0])
+        for r in range(self.R):
+            self.u_np[r, m] = np.random.random_sample(self.B)  # the reference's stream: choice's random_sample(m)
+            step = step0 + 1.0 + r
+            self.step_np[r, m] = (1, n, g["lr"] / (1 - beta1 ** step), math.sqrt(1 - beta2 ** step))
+        a.buffer._dev_replay.check_pending(block=True)
+        self.active.append(m)
+        self.final_step[m] = step0 + self.R
+
+    def run(self, logs):
+        """the loop's rounds of the staged agents; the losses of the last round into their logs.  Returns the active
+        agents' indices.  The lone path's exceptions (ValueError for a draw NumPy's choice would refuse,
+        AssertionError / IndexError for the write-back) are raised after all rounds have run and the agents' Adam
+        counters and parameter versions are consistent with what the kernels wrote."""
+        if not self.active:
+            return []
+        L, M, B = self._lib, self.M, self.B
+        if self.handle is None or self._key != self._identity():
+            self._build()
+        stream = L.stream_handle(self.dev)
+        for m in self.active:
+            fu = self.agents[m]._graphed
+            if fu._seen != fu._versions():  # parameters written outside the fused update: re-transpose
+                L.check(L.lib().mzh_train_transpose(fu._a, stream), "mzh_train_transpose")
+        for r in range(self.R):
+            L.check(L.lib().mzh_train_set_update(self.handle, self.step_dev + r * M * 16, self.u_dev + r * M * B * 8,
+                                                 self.status_dev + r * M * 16, stream), "mzh_train_set_update")
+        means = self.row_loss.mean(1)  # [M][3], the last round's
+        L.synchronize(self.dev)  # the loop's one synchronisation; the status words are read below
+        for m in self.active:
+            fu = self.agents[m]._graphed
+            for v in fu._step_views:  # torch.optim.Adam's step counters (float32)
+                v[...] = self.final_step[m]
+            increment_version(fu.params)  # the kernels wrote the parameters in place: let version trackers know
+            fu._seen = fu._versions()
+            logs[m]["value_loss"].append(means[m, 0])
+            logs[m]["rwd_loss"].append(means[m, 1])
+            logs[m]["pi_loss"].append(means[m, 2])
+        for r in range(self.R):
+            for m in self.active:
+                draw, _, wb, _ = (int(x) for x in self.status_np[r, m])
+                if draw != 0:
+                    raise ValueError("probabilities contain NaN or are not non-negative "
+                                     f"(np.random.choice's check of the priorities, buffer.py:89-112; agent {m})")
+                if wb == 1:
+                    raise AssertionError("Priorities must be finite and positive.")
+                if wb == 2:
+                    raise IndexError(f"update_priorities: an index is outside [0, {self.agents[m].buffer.size})")
+        return list(self.active)
