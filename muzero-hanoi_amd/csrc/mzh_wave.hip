@@ -465,8 +465,9 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
   const size_t E = (size_t)p.E;
 
   // root lanes: lanes rho and rho + 32 (rho < ROOTS) both own root wr0 + rho in the tree phases:
-  // selection splits the 6 children between them (3 UCBs per lane), every other tree step runs
-  // mirrored on both (same values, same addresses)
+  // selection splits the 6 children between them (3 UCBs per lane), every other tree step's loads and
+  // arithmetic run mirrored on both (same values, same addresses); of the expansion's and backup's stores each
+  // is issued by one lane of the pair (phase_head)
   const int rho = lane & 31;
   const int half = lane >> 5;
   const int rroot = wr0 + rho;
@@ -858,18 +859,21 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
         const uint4 r0 = rec[0], r1 = rec[1];  // priors 0-3 | priors 4, 5, reward, value
         rr = __uint_as_float(r1.z);
         vv = __uint_as_float(r1.w);
-        // the whole 128-B line as eight 16-B stores (see phase_head's fused form)
+        // the whole 128-B line as eight 16-B stores (see phase_blocks), four per lane of the pair: half 0
+        // writes chunks 0-3 and half 1 chunks 4-7, so the wave still writes the line whole
         uint4* nb = reinterpret_cast<uint4*>(&TB(enew));
         const uint32_t nx = 0xFFFF0000u;
         const uint4 z = make_uint4(0u, 0u, 0u, 0u);
-        nb[0] = make_uint4(nx, nx, nx, nx);
-        nb[1] = make_uint4(nx, nx, 0u, 0u);
+        const uint4 c7 = REPLAY ? z : make_uint4(0u, 0u, (unsigned)(hrow + 1), 0u);  // pad[0]: the node's row + 1
+        // half 0: nx0-3 | nx4,5 R0,1 | R2-5 | P0-3; half 1: P4,5 W0 | W1,2 | W3,4 | W5 pad.  Word by word: a
+        // select between two constant vectors becomes a table in scratch
+        const bool h1 = half != 0;
+        const uint32_t nx0 = h1 ? 0u : nx;
+        nb += 4 * half;
+        nb[0] = make_uint4(h1 ? r1.x : nx, h1 ? r1.y : nx, nx0, nx0);
+        nb[1] = make_uint4(nx0, nx0, 0u, 0u);
         nb[2] = z;
-        nb[3] = r0;
-        nb[4] = make_uint4(r1.x, r1.y, 0u, 0u);
-        nb[5] = z;
-        nb[6] = z;
-        nb[7] = REPLAY ? z : make_uint4(0u, 0u, (unsigned)(hrow + 1), 0u);  // pad[0]: the node's row + 1
+        nb[3] = make_uint4(h1 ? 0u : r0.x, h1 ? 0u : r0.y, h1 ? c7.z : r0.z, h1 ? 0u : r0.w);
       } else {
         vv = vcol;
         rr = rcol;
@@ -884,13 +888,21 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
           leaf += 1 << 18;
         }
       }
-      if (leafE == 0) {
-        ws.rX[leafA][rho] = enew;
-        ws.rR[leafA][rho] = rr;
-      } else {
-        TB(leafE).nx[leafA].X = (int16_t)enew;
-        TB(leafE).R[leafA] = rr;
+      // this phase's stores: the pair's lanes hold the same values for the same addresses, so one of them stores
+      // (st); the loads and the arithmetic stay mirrored, both lanes need the values.  The next selection reads
+      // them on both lanes behind the simulation loop's closing fence.  (Selection's own path-cache stores stay
+      // mirrored: one lane storing them measured no gain)
+      const bool st = !half;
+      if (st) {
+        if (leafE == 0) {
+          ws.rX[leafA][rho] = enew;
+          ws.rR[leafA][rho] = rr;
+        } else {
+          TB(leafE).nx[leafA].X = (int16_t)enew;
+          TB(leafE).R[leafA] = rr;
+        }
       }
+      MZH_STAMP(12);  // record + new block: closes when the stores are issued
       double v = (double)vv;
       double lmax = -__builtin_inf(), lmin = __builtin_inf();
       // path entry j: slot (parent expanded index * 8 + child) and the child's statistics at
@@ -932,8 +944,10 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
         double Wn;
         int Nn;
         node(jn, Wn, Nn);
-        TB(e).W[a] = Wn;
-        TB(e).nx[a].N = (uint16_t)Nn;
+        if (st) {
+          TB(e).W[a] = Wn;
+          TB(e).nx[a].N = (uint16_t)Nn;
+        }
       };
       for (; j >= 1; --j) {
         int slot_n, Nj_n;
@@ -952,8 +966,10 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
         double Wn;
         int Nn;
         node(0, Wn, Nn);
-        ws.rW[a][rho] = Wn;
-        ws.rN[a][rho] = Nn;
+        if (st) {
+          ws.rW[a][rho] = Wn;
+          ws.rN[a][rho] = Nn;
+        }
       }
       rootW = rootW + v;
       rootN = rootN + 1;
@@ -1005,6 +1021,7 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
       mode = nm == 0 ? 0 : (NT == 2 && nm <= 16) ? 1 : 2;
       cnt = __builtin_amdgcn_readfirstlane(cnt + (mode == 0 ? 1u : mode == 1 ? 0x10000u : 0u));
     }
+    MZH_STAMP(3);  // memo lookup + mode ballot
     float vcol = 0.0f, rcol = 0.0f;
     if (mode == 2) {
       if (!REPLAY) {

@@ -2,9 +2,12 @@
 (libmzh_diag.so: python -m muzero_hanoi_amd.build --diag).  s_memtime ticks per simulation of the four
 waves of workgroup 0, averaged over the launches: where one simulation of the bench workload's search goes.
 A stamp closes the phase it names: the ticks since the previous stamp.  The latent gather's stamp closes
-when its loads are issued, so the wait for them falls into the dynamics chain.
+when its loads are issued, so the wait for them falls into the dynamics chain.  In a simulation that runs no MLP
+the stamps between the lookup's and the new block's are empty, so it splits into select / lookup / record + new
+block / backup; "record + new block" closes when the block's stores are issued.  --warm: launches before the
+stamped ones (the grown memo fills over the first few; a warm table is what bench.py times).
 
-    MZH_DIAG_LIB=muzero-hanoi_amd/libmzh_diag.so python tools/wave_stamps.py [--config 2] [--launches 5]
+    MZH_DIAG_LIB=muzero-hanoi_amd/libmzh_diag.so python tools/wave_stamps.py [--config 2] [--launches 5] [--warm 1]
 """
 import argparse
 import ctypes
@@ -19,9 +22,9 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 # stamp index -> phase, in the order a simulation runs them (mzh_wave.hip)
-PHASES = [(4, "loop top"), (0, "select"), (10, "gather issue"), (5, "dyn chain + bias"), (6, "rwd chain + bias"),
+PHASES = [(4, "loop top"), (0, "select"), (3, "memo lookup + mode ballot"), (10, "gather issue"), (5, "dyn chain + bias"), (6, "rwd chain + bias"),
           (11, "rwd head"), (7, "normalise + latent store"), (8, "pol chain + softmax"), (9, "val chain + bias"),
-          (1, "val head"), (2, "new block + backup")]
+          (1, "val head"), (12, "record + new block"), (2, "backup")]
 MLP = (10, 5, 6, 11, 7, 8, 9, 1)
 
 
@@ -30,6 +33,7 @@ def main():
     ap.add_argument("--config", type=int, default=2, help="bench.py's BASELINE config (2: the default workload)")
     ap.add_argument("--kernel", choices=["auto", "wave", "wave16"], default="auto")
     ap.add_argument("--launches", type=int, default=5)
+    ap.add_argument("--warm", type=int, default=1, help="launches before the stamped ones")
     ap.add_argument("--seed", type=int, default=0)
     a = ap.parse_args()
     import bench
@@ -54,7 +58,8 @@ def main():
         return eng.search(S, obs=obs, tie_idx=tie, noise=noise, action_u=u, temperature=1.0, deterministic=False,
                           discount=0.8, eps=0.25, out=out, kernel=kern)
 
-    o = run()
+    for _ in range(max(1, a.warm)):
+        o = run()
     torch.cuda.synchronize()
     assert "mzh_wave_kernel" in o["_plan"]["kernel"], f"{o['_plan']['kernel']}: not a wave kernel"
     assert L.mzh_diag_wave_stamps(buf.ctypes.data_as(ctypes.c_void_p)) == 0  # clears the warm-up launch's
@@ -70,7 +75,7 @@ def main():
     mean = per[:4].mean(0)
     total = float(sum(mean[k] for k, _ in PHASES))
     res = {"config": a.config, "disks": n, "roots": B, "sims": S, "kernel": o["_plan"]["kernel"],
-           "launches": a.launches, "build_id": _lib.build_id(),
+           "launches": a.launches, "warm_launches": max(1, a.warm), "build_id": _lib.build_id(),
            "kernel_ms_diag_build": float(np.median([s_.elapsed_time(e_) for s_, e_ in ev])),
            "sel_steps_per_sim": float(out["sel_steps"].double().sum()) / (B * S),
            "what": "s_memtime ticks per simulation, workgroup 0, lane 0 of each wave; a phase = the ticks since "
