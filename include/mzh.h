@@ -458,6 +458,30 @@ typedef struct mzh_multi_args {
 } mzh_multi_args;
 int mzh_search_multi(mzh_engine* eng, const mzh_search_args* args, const mzh_multi_args* multi, mzh_stream stream);
 
+/* mzh_search_multi with a simulation budget per root: root b runs budget->n_sims[b] simulations under network
+ * net_index[b], with the result mzh_search_multi gives that root in a launch of n_sims[b] simulations on the same
+ * inputs (bit for bit: the acting scripts' loop over n_mcts_simulations_range as one batch).  args.n_sims is the
+ * launch's maximum: it sets the capacity check, the LDS, the length of pow_table (n_sims + 1) and the row stride
+ * of args.latent (n_sims + 1; a root's row holds its latent_len entries, then -1).  Every budget lies in
+ * [0, args.n_sims].
+ * A run is a maximal stretch of consecutive roots with equal (net_index, n_sims).  net_index stays non-decreasing;
+ * inside a network the budgets may come in any order, and equal budgets need not be adjacent -- they only make
+ * more runs.  The prologue cuts at every run's end, so a tile holds up to 16 or 32 roots of one run, and lists the
+ * tiles by decreasing budget (tiles of one budget in no fixed order; no result depends on a tile's place).  The
+ * caller states max_runs >= the number of runs: the grid is ceil(B / tile) + min(max_runs, B) - 1 workgroups, and
+ * args.lockstep_levels (indexed by tile) needs that many entries.
+ * Flags, and every refusal of mzh_search_multi, are that call's.  Also refused before anything is launched, and
+ * before an engine or a device is needed: a NULL args, multi, budget or n_sims, max_runs < 1 (MZH_ERR_ARG); with
+ * the engine: a max_runs whose grid exceeds the engine's tile workspace (MZH_ERR_CAPACITY).
+ * Refused on the device as a bad net_index is -- no root is searched, no output of args is written, status[0] = 1:
+ * a budget outside [0, args.n_sims], more runs than max_runs, more tiles than the tile workspace holds. */
+typedef struct mzh_budget_args {
+  const int32_t* n_sims; /* [B] device: simulations of root b, each in [0, args.n_sims] */
+  int32_t max_runs;      /* >= the runs of (net_index, n_sims): sizes the grid */
+} mzh_budget_args;
+int mzh_search_multi_budget(mzh_engine* eng, const mzh_search_args* args, const mzh_multi_args* multi,
+                            const mzh_budget_args* budget, mzh_stream stream);
+
 /* Action probe (acting_experiments/legal_illegal_preds.py evaluate_network, lines 26-80): what the model
  * predicts for each of the six moves from a state -- h = represent(obs) (networks.py:71-94), then
  * recurrent_inference(h, one_hot(a)) for a = 0..5 (networks.py:96-138) -- which the script files under legal or

@@ -78,6 +78,11 @@ class MultiArgs(ctypes.Structure):
     _fields_ = [("n_networks", _i32), ("net_index", _vp), ("status", _vp)]
 
 
+class BudgetArgs(ctypes.Structure):
+    """mirror of struct mzh_budget_args (include/mzh.h)"""
+    _fields_ = [("n_sims", _vp), ("max_runs", _i32)]
+
+
 # SearchArgs output pointer -> the name its array has in a search's result (Engine.search, MCTS.run_mcts)
 SEARCH_OUTPUTS = (("visits", "visits"), ("root_q", "root_q"), ("minmax_out", "minmax"), ("extra_ties", "extra_ties"),
                   ("action", "action"), ("pi", "pi"), ("latent", "latent"), ("latent_len", "latent_len"),
@@ -204,6 +209,8 @@ SIGNATURES = {
     "mzh_search": (ctypes.c_int, [_vp, ctypes.POINTER(SearchArgs), _vp]),
     "mzh_search_replay": (ctypes.c_int, [_vp, ctypes.POINTER(SearchArgs), _vp]),
     "mzh_search_multi": (ctypes.c_int, [_vp, ctypes.POINTER(SearchArgs), ctypes.POINTER(MultiArgs), _vp]),
+    "mzh_search_multi_budget": (ctypes.c_int, [_vp, ctypes.POINTER(SearchArgs), ctypes.POINTER(MultiArgs),
+                                               ctypes.POINTER(BudgetArgs), _vp]),
     "mzh_probe_actions": (ctypes.c_int, [_vp, ctypes.POINTER(ProbeArgs), ctypes.POINTER(MultiArgs), _vp]),
     "mzh_saliency": (ctypes.c_int, [_vp, ctypes.POINTER(SaliencyArgs), ctypes.POINTER(MultiArgs), _vp]),
     "mzh_param_grads": (ctypes.c_int, [_vp, ctypes.POINTER(PgradArgs), ctypes.POINTER(MultiArgs), _vp]),

@@ -1308,7 +1308,9 @@ extern "C" int mzh_search_replay(mzh_engine* eng, const mzh_search_args* args, m
 
 // Search over the loaded network set: root b under network net_index[b].  Cooperative kernel only (16- or
 // 32-root tiles of one network each); every refusal below returns before anything is launched.
-extern "C" int mzh_search_multi(mzh_engine* eng, const mzh_search_args* a, const mzh_multi_args* m, mzh_stream stream) {
+// b: the roots' own budgets (mzh_search_multi_budget), nullptr where every root runs a->n_sims
+static int search_multi_common(mzh_engine* eng, const mzh_search_args* a, const mzh_multi_args* m, const mzh_budget_args* b,
+                               mzh_stream stream) {
   if (!eng || !a || !m) return fail(MZH_ERR_ARG, "engine or args NULL");
   if (eng->set_m == 0) return fail(MZH_ERR_STATE, "no weight set loaded (mzh_load_weight_set)");
   if (m->n_networks < 1 || m->n_networks > eng->set_m)
@@ -1329,6 +1331,14 @@ extern "C" int mzh_search_multi(mzh_engine* eng, const mzh_search_args* a, const
   pl.ohl = mzh_search_smem_bytes(pl.R, S, true) <= kMaxLds;
   pl.sup33 = eng->support == 33;
   pl.mmin = 1;
+  // the tile workspace holds the tiles of max_roots roots of MZH_MULTI_MAX_NETS networks at 16 roots each
+  const int cap = mzh_multi_max_tiles(eng->max_roots, 16, MZH_MULTI_MAX_NETS);
+  // the grid: the most tiles the batch can make, its runs (at most max_runs) in place of the networks with budgets
+  const int runs = b ? b->max_runs : m->n_networks;
+  const int grid = mzh_multi_max_tiles(a->B, pl.R, runs);
+  if (grid > cap)
+    return fail(MZH_ERR_CAPACITY, "max_runs=%d: up to %d tiles of %d roots exceed the tile workspace (%d)", runs, grid,
+                pl.R, cap);
   if (a->plan_out) {
     const char* tf[2] = {"false", "true"};
     mzh_search_plan* o = a->plan_out;
@@ -1337,14 +1347,38 @@ extern "C" int mzh_search_multi(mzh_engine* eng, const mzh_search_args* a, const
     o->threads_per_workgroup = MZH_THREADS;
     o->roots_per_workgroup = pl.R;
     o->smem_bytes = (int64_t)mzh_search_smem_bytes(pl.R, S, pl.ohl);
-    o->workgroups = mzh_multi_max_tiles(a->B, pl.R, m->n_networks);
+    o->workgroups = grid;
     snprintf(o->kernel, sizeof(o->kernel), "mzh_search_multi_kernel<%d, %s, %s>", pl.R, tf[pl.ohl], tf[pl.sup33]);
   }
   DeviceGuard g(eng->device);
   if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
   const MzhSearchParams p = search_params(eng, a);
-  hipError_t e = mzh_launch_search_multi(pl, eng->setnet, p, multi_params(eng, m), (hipStream_t)stream);
+  hipError_t e;
+  if (b) {
+    MzhBudgetParams bp{};
+    bp.n_sims = b->n_sims;
+    bp.S = S;
+    bp.max_runs = b->max_runs < a->B ? b->max_runs : a->B;
+    bp.cap = cap;
+    e = mzh_launch_search_multi_budget(pl, eng->setnet, p, multi_params(eng, m), bp, (hipStream_t)stream);
+  } else {
+    e = mzh_launch_search_multi(pl, eng->setnet, p, multi_params(eng, m), (hipStream_t)stream);
+  }
   return e == hipSuccess ? MZH_OK : hip_fail(e, "multi search launch");
+}
+
+extern "C" int mzh_search_multi(mzh_engine* eng, const mzh_search_args* a, const mzh_multi_args* m, mzh_stream stream) {
+  return search_multi_common(eng, a, m, nullptr, stream);
+}
+
+// The same search with root b running budget->n_sims[b] simulations (at most a->n_sims, which sizes the launch).
+// What the budget block alone decides is refused first: those refusals need neither an engine nor a device.
+extern "C" int mzh_search_multi_budget(mzh_engine* eng, const mzh_search_args* a, const mzh_multi_args* m,
+                                       const mzh_budget_args* b, mzh_stream stream) {
+  if (!a || !m || !b) return fail(MZH_ERR_ARG, "search_multi_budget: args, multi or budget NULL");
+  if (!b->n_sims) return fail(MZH_ERR_ARG, "search_multi_budget: n_sims is NULL");
+  if (b->max_runs < 1) return fail(MZH_ERR_ARG, "search_multi_budget: max_runs=%d < 1", b->max_runs);
+  return search_multi_common(eng, a, m, b, stream);
 }
 
 // ---- the calls over rows of a sub-batch: mzh_probe_actions, mzh_saliency, mzh_param_grads ----

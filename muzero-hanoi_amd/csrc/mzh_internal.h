@@ -251,7 +251,7 @@ struct MzhSearchPlan {
 // consecutive roots of one network, the unit one workgroup of mzh_search_multi_kernel searches.
 #define MZH_MULTI_MAX_NETS 256
 struct MzhTile {
-  int32_t root0, n, net, pad;
+  int32_t root0, n, net, sims;  // sims: the tile's simulation budget (read by mzh_search_multi_kernel only)
 };
 struct MzhMultiParams {
   const int32_t* net_index;  // [B] caller's, read only by mzh_multi_tiles_kernel
@@ -267,16 +267,30 @@ struct MzhMultiParams {
 static inline int mzh_multi_max_tiles(int B, int R, int M) { return (B + R - 1) / R + (M < B ? M : B) - 1; }
 hipError_t mzh_launch_search_multi(const MzhSearchPlan& pl, const MzhNet& net, const MzhSearchParams& p,
                                    const MzhMultiParams& mp, hipStream_t stream);
-// mzh_multi_tiles_kernel (mzh_search.hip) on mp.net_index [n]: the prologue of every multi-network launch
-hipError_t mzh_launch_multi_tiles(const MzhMultiParams& mp, int n, int R, hipStream_t stream);
+// The simulation budgets of a multi-network search (mzh_search_multi_budget): root b runs n_sims[b] simulations.  A
+// run is a maximal stretch of consecutive roots with equal (net_index, n_sims); a tile never spans a run.  With
+// n_sims == nullptr every root has the launch's budget S and the tiles are those of the networks' segments.
+struct MzhBudgetParams {
+  const int32_t* n_sims;  // [B] caller's (nullable), read only by mzh_multi_tiles_kernel
+  int S;                  // the launch's n_sims: every budget lies in [0, S]
+  int max_runs;           // the caller's bound on the runs (the search grid is sized by it)
+  int cap;                // entries of MzhMultiParams::tiles
+};
+hipError_t mzh_launch_search_multi_budget(const MzhSearchPlan& pl, const MzhNet& net, const MzhSearchParams& p,
+                                          const MzhMultiParams& mp, const MzhBudgetParams& bp, hipStream_t stream);
+// mzh_multi_tiles_kernel (mzh_search.hip) on mp.net_index [n]: the prologue of every multi-network launch (sims: the
+// budget written into every tile, the launch's n_sims for a search, 0 for the row kernels, which never read it)
+hipError_t mzh_launch_multi_tiles(const MzhMultiParams& mp, int n, int R, hipStream_t stream, int sims = 0);
 
 // Where a cooperative workgroup's rows [root0, root0 + nvalid), nvalid <= R, come from: MzhGridTile (workgroup
-// b owns the R rows from b * R: the single-network kernels) or a tile table entry (the multi-network kernels)
+// b owns the R rows from b * R: the single-network kernels) or a tile table entry (the multi-network kernels).
+// kOwnSims: the workgroup's roots run sims() simulations, the table entry's budget, not the launch's n_sims.
 struct MzhGridTile {
   template <int R>
   __device__ __forceinline__ int root0() const { return blockIdx.x * R; }
   template <int R>
   __device__ __forceinline__ int nvalid(int B, int root0) const { return min(R, B - root0); }
+  static constexpr bool kOwnSims = false;
 };
 struct MzhTableTile {
   MzhTile t;
@@ -284,6 +298,8 @@ struct MzhTableTile {
   __device__ __forceinline__ int root0() const { return t.root0; }
   template <int R>
   __device__ __forceinline__ int nvalid(int, int) const { return t.n; }
+  static constexpr bool kOwnSims = true;
+  __device__ __forceinline__ int sims() const { return t.sims; }
 };
 
 // the set's network `net` from the template MzhNet of network 0: every blob of a set has the same layout, at

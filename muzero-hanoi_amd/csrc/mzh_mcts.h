@@ -128,11 +128,13 @@ __device__ __forceinline__ int mzh_play_policy(const MzhSearchParams& p, const i
 // The results of one root (mcts.py:111-126, generate_play_policy mcts.py:154-176), written by one lane:
 // visits, root Q, MinMaxStats bounds, the tie and step counters, the last simulation's action path
 // (path_at(j) = path entry j of that selection, its low 3 bits the child), pi and the action.
-template <class PathAt>
+// OWN (mzh_search_multi_budget): the root ran `own` simulations, its own budget, which is at most p.S; the rows of
+// p.latent keep the launch's stride p.S + 1 either way.
+template <bool OWN = false, class PathAt>
 __device__ __forceinline__ void mzh_write_results(const MzhSearchParams& p, const int root, const int (&vis)[MZH_A],
                                                   const double rootW, const int rootN, const double mmax,
                                                   const double mmin, const int extra, const int steps, const int depth,
-                                                  PathAt path_at) {
+                                                  PathAt path_at, const int own = 0) {
   for (int a = 0; a < MZH_A; ++a) p.visits[(size_t)root * MZH_A + a] = vis[a];
   if (p.root_q) p.root_q[root] = rootN == 0 ? 0.0 : rootW / (double)rootN;
   if (p.minmax_out) {
@@ -142,11 +144,11 @@ __device__ __forceinline__ void mzh_write_results(const MzhSearchParams& p, cons
   if (p.extra_ties) p.extra_ties[root] = extra;
   if (p.sel_steps) p.sel_steps[root] = steps;
   const int PL = p.S + 1;
-  if (p.latent && p.S > 0) {
+  if (p.latent && (OWN ? own : p.S) > 0) {
     for (int j = 0; j < depth; ++j) p.latent[(size_t)root * PL + j] = path_at(j) & 7;
     for (int j = depth; j < PL; ++j) p.latent[(size_t)root * PL + j] = -1;
   }
-  if (p.latent_len) p.latent_len[root] = p.S > 0 ? depth : 0;
+  if (p.latent_len) p.latent_len[root] = (OWN ? own : p.S) > 0 ? depth : 0;
   if (p.pi || p.action) {
     const int act = mzh_play_policy(p, root, vis);
     if (p.action) p.action[root] = act;

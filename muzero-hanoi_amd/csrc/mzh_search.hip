@@ -63,8 +63,13 @@ __device__ __forceinline__ void mzh_search_body(const MzhNet& net, const MzhSear
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int root0 = tile.template root0<R>();
   const int nvalid = tile.template nvalid<R>(p.B, root0);
-  const int S = p.S;
-  const int PL = S + 1;  // path row length
+  // the simulations of this workgroup's roots: p.S, or the tile's own budget (<= p.S, workgroup-uniform, so every
+  // barrier below stays uniform); the LDS layout and the path rows are those of p.S, the launch's maximum
+  int sims;
+  if constexpr (TILE::kOwnSims) sims = tile.sims(); else sims = p.S;
+  const int S = sims;
+  const int SMAX = TILE::kOwnSims ? p.S : S;  // the launch's n_sims
+  const int PL = SMAX + 1;  // path row length
   const double disc = p.discount;
   const bool noised = p.noise != nullptr;
   // this lane's root (tree phases) and child slot
@@ -75,8 +80,8 @@ __device__ __forceinline__ void mzh_search_body(const MzhNet& net, const MzhSear
   if (OHL)
     for (int i = tid; i < MZH_A * MZH_F; i += MZH_THREADS) ohl[i] = net.dyn0_onehot[i];
   if (SUP33 && !REPLAY) mzh_w32_fill<R>(sm, net, tid);
-  for (int i = tid; i < S + 3; i += MZH_THREADS) {
-    table[i] = i < S + 2 ? p.table[i] : 0.0;
+  for (int i = tid; i < SMAX + 3; i += MZH_THREADS) {
+    table[i] = i < SMAX + 2 ? p.table[i] : 0.0;
     inv[i] = 1.0 / (double)i;  // IEEE division: correctly rounded
   }
   if (tid < R) {
@@ -220,7 +225,12 @@ __device__ __forceinline__ void mzh_search_body(const MzhNet& net, const MzhSear
   __syncthreads();
   if (tid < R * 8) {
     const int r = tid >> 3, c = tid & 7;
-    if (r < nvalid && c == 0) tree.results(r);
+    if (r < nvalid && c == 0) {
+      if constexpr (TILE::kOwnSims)
+        tree.results(r, S);
+      else
+        tree.results(r);
+    }
   }
 }
 
@@ -259,13 +269,160 @@ __device__ __forceinline__ int mzh_wave_scan_i32(int v) {
   return v;
 }
 
+// The budget form of the prologue (bp.n_sims given: mzh_search_multi_budget).  Root b runs n_sims[b] simulations; a
+// run is a maximal stretch of consecutive roots with equal (net_index, n_sims), and a tile is up to R consecutive
+// roots of one run.  Thread t owns the roots [t C, (t + 1) C), C = ceil(B / T), and walks them three times: it checks
+// them and finds its first and last run boundary; it counts its tiles per class; it writes them, a class's tiles
+// from the class's first slot on.  The class of a tile is S - budget, so the table lists the deepest budgets first
+// (workgroup t of the search takes tile t and dispatch is in order: the launch lasts as long as its deepest tile,
+// which must not start last); tiles of one budget take their slots by an LDS atomic, in no fixed order -- no result
+// depends on a tile's place in the table.  -DMZH_BUDGET_ROOT_ORDER (A/B builds only): the class is the thread, which
+// leaves the tiles in root order.
+// Refused as a bad net_index is (tile count 0, status[0] = 1, nothing written to the table): an entry of net_index
+// outside [0, M) or below its predecessor, a budget outside [0, S] (0 is the smallest n_sims mzh_search_multi
+// accepts), more runs than bp.max_runs, more tiles than the table holds.  A budget indexes LDS only after every
+// root's checks have passed.
+// cls: dynamic LDS, max(S + 1, T) ints.
+__device__ __forceinline__ void mzh_budget_tiles(const MzhMultiParams& mp, const MzhBudgetParams& bp, const int B,
+                                                 const int R, int* cls) {
+  constexpr int T = MZH_MULTI_MAX_NETS;
+  __shared__ int firstb[T];  // the thread's first run boundary (B: none)
+  __shared__ int lastb[T];   // its last one (-1: none)
+  __shared__ int wtot[T / 64];
+  __shared__ int nrun, total;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int M = mp.M, S = bp.S;
+#ifdef MZH_BUDGET_ROOT_ORDER
+  const int NC = T;
+#else
+  const int NC = S + 1;
+#endif
+  const int C = (B + T - 1) / T;
+  const int i0 = min(B, tid * C), i1 = min(B, i0 + C);
+  for (int k = tid; k < NC; k += T) cls[k] = 0;
+  if (tid == 0) nrun = 0;
+  __syncthreads();
+  auto refuse = [&]() {
+    if (tid == 0) {
+      *mp.ntiles = 0;
+      if (mp.status) {
+        mp.status[0] = 1;
+        mp.status[1] = 0;
+      }
+    }
+  };
+  // root i starts a run where it differs from root i - 1 in either value (root 0 always does)
+  const bool inner = i0 > 0 && i0 < i1;
+  const int pv0 = inner ? mp.net_index[i0 - 1] : -1, ps0 = inner ? bp.n_sims[i0 - 1] : -1;
+  int bad = 0, fb = B, lb = -1, nb = 0;
+  {
+    int pv = pv0, ps = ps0;
+    for (int i = i0; i < i1; ++i) {
+      const int v = mp.net_index[i], s = bp.n_sims[i];
+      if ((unsigned)v >= (unsigned)M || v < pv || (unsigned)s > (unsigned)S) bad = 1;
+      if (i == 0 || v != pv || s != ps) {
+        fb = min(fb, i);
+        lb = i;
+        nb++;
+      }
+      pv = v;
+      ps = s;
+    }
+  }
+  firstb[tid] = fb;
+  lastb[tid] = lb;
+  if (nb) atomicAdd(&nrun, nb);
+  bad = __syncthreads_or(bad);
+  if (bad || nrun > bp.max_runs) {  // workgroup-uniform
+    refuse();
+    return;
+  }
+  // the run my first root lies in started at `before`; the run my last root lies in ends at `after`
+  int before = 0, after = B;
+  for (int t = 0; t < tid; ++t) before = max(before, lastb[t]);
+  for (int t = tid + 1; t < T; ++t) after = min(after, firstb[t]);
+  // walk(f): f(i, v, s) for every root i of mine that starts a tile (a run's roots at multiples of R from its start)
+  auto walk = [&](auto f) {
+    int pv = pv0, ps = ps0, r0 = before;
+    for (int i = i0; i < i1; ++i) {
+      const int v = mp.net_index[i], s = bp.n_sims[i];
+      if (i == 0 || v != pv || s != ps) r0 = i;
+      if (((i - r0) & (R - 1)) == 0) f(i, v, s);
+      pv = v;
+      ps = s;
+    }
+  };
+  int nt = 0;
+  walk([&](int, int, int s) {
+    nt++;
+#ifndef MZH_BUDGET_ROOT_ORDER
+    atomicAdd(&cls[S - s], 1);
+#endif
+  });
+#ifdef MZH_BUDGET_ROOT_ORDER
+  cls[tid] = nt;
+#endif
+  __syncthreads();
+  // cls[k]: tiles of class k -> the class's first slot (thread t scans the classes [t CH, (t + 1) CH))
+  const int CH = (NC + T - 1) / T;
+  const int k0 = min(NC, tid * CH), k1 = min(NC, k0 + CH);
+  int part = 0;
+  for (int k = k0; k < k1; ++k) part += cls[k];
+  const int inc = mzh_wave_scan_i32(part);
+  if (lane == 63) wtot[wave] = inc;
+  __syncthreads();
+  int pre = 0;
+  for (int w = 0; w < wave; ++w) pre += wtot[w];
+  int slot = pre + inc - part;  // exclusive
+  for (int k = k0; k < k1; ++k) {
+    const int c = cls[k];
+    cls[k] = slot;
+    slot += c;
+  }
+  if (tid == T - 1) total = pre + inc;
+  __syncthreads();
+  // (runs <= max_runs bounds the tiles by the launcher's grid; the table's size is checked on its own)
+  if (total > bp.cap) {
+    refuse();
+    return;
+  }
+  int ts = -1, tpos = 0, tnet = 0, tsims = 0;  // the open tile: its first root and slot
+  walk([&](int i, int v, int s) {
+    if (ts >= 0) mp.tiles[tpos] = MzhTile{ts, i - ts, tnet, tsims};
+#ifdef MZH_BUDGET_ROOT_ORDER
+    tpos = cls[tid]++;
+#else
+    tpos = atomicAdd(&cls[S - s], 1);
+#endif
+    ts = i;
+    tnet = v;
+    tsims = s;
+  });
+  // my last tile ends with its R-th root, its run or the batch (a later thread's first boundary, or B)
+  if (ts >= 0) mp.tiles[tpos] = MzhTile{ts, min(ts + R, after) - ts, tnet, tsims};
+  if (tid == 0) {
+    *mp.ntiles = total;
+    if (mp.status) {
+      mp.status[0] = 0;
+      mp.status[1] = total;
+    }
+  }
+}
+
 // One workgroup: check net_index [B] (each entry in [0, M), non-decreasing), find every network's segment,
 // give network m ceil(count_m / R) tiles in network order and write them with their count.  A refused
 // net_index leaves tile count 0 (the search kernel's workgroups all return) and status[0] = 1.  An entry
 // indexes LDS only after it passed the range and order checks, and nothing else ever uses it: the search
-// kernel takes the network from the table.
-__global__ __launch_bounds__(MZH_MULTI_MAX_NETS) void mzh_multi_tiles_kernel(MzhMultiParams mp, int B, int R) {
+// kernel takes the network from the table.  Every tile carries the budget bp.S.  With bp.n_sims the roots have
+// budgets of their own and the tiles are cut by mzh_budget_tiles.
+__global__ __launch_bounds__(MZH_MULTI_MAX_NETS) void mzh_multi_tiles_kernel(MzhMultiParams mp, int B, int R,
+                                                                             MzhBudgetParams bp) {
   constexpr int T = MZH_MULTI_MAX_NETS;
+  if (bp.n_sims) {
+    extern __shared__ int mzh_tiles_cls[];
+    mzh_budget_tiles(mp, bp, B, R, mzh_tiles_cls);
+    return;
+  }
   __shared__ int start[T + 1];  // start[m]: first root of network m (B where it has none left); start[M] = B
   __shared__ int toff[T + 1];   // toff[m]: first tile of network m; toff[M] = tiles
   __shared__ int wtot[T / 64];
@@ -306,7 +463,7 @@ __global__ __launch_bounds__(MZH_MULTI_MAX_NETS) void mzh_multi_tiles_kernel(Mzh
   // at most ceil(B / R) + min(M, B) - 1 tiles (the launcher's grid and the table's capacity)
   for (int m = 0; m < M; ++m) {
     const int s0 = start[m], cnt = start[m + 1] - s0, t0 = toff[m];
-    for (int k = tid; k * R < cnt; k += T) mp.tiles[t0 + k] = MzhTile{s0 + k * R, min(R, cnt - k * R), m, 0};
+    for (int k = tid; k * R < cnt; k += T) mp.tiles[t0 + k] = MzhTile{s0 + k * R, min(R, cnt - k * R), m, bp.S};
   }
   if (tid == 0) {
     *mp.ntiles = toff[T];
@@ -319,7 +476,8 @@ __global__ __launch_bounds__(MZH_MULTI_MAX_NETS) void mzh_multi_tiles_kernel(Mzh
 
 // MMIN = true always: it only adds the subnormal max - min check, and is bit-identical with fresh bounds.
 // A workgroup at or above the tile count (the grid is the upper bound ceil(B / R) + min(M, B) - 1) returns
-// before its first barrier.  blockIdx.x is the tile index (p.lockstep_levels is indexed by tile).
+// before its first barrier.  blockIdx.x is the tile index (p.lockstep_levels is indexed by tile).  The tile's roots
+// run the tile's budget: p.S (mzh_search_multi) or the run's own (mzh_search_multi_budget), always from the table.
 template <int R, bool OHL, bool SUP33>
 __global__ __launch_bounds__(MZH_THREADS, 1) void mzh_search_multi_kernel(MzhNet net, MzhSearchParams p, MzhMultiParams mp) {
   if ((int)blockIdx.x >= *mp.ntiles) return;
@@ -520,14 +678,22 @@ hipError_t mzh_launch_search(const MzhSearchPlan& pl, const MzhNet& net, const M
   return launch_search_t<16, false, false>(pl, net, p, stream);
 }
 
+// the tile table of n rows with budgets of their own (bp.n_sims given)
+static hipError_t launch_budget_tiles(const MzhMultiParams& mp, const MzhBudgetParams& bp, int n, int R, hipStream_t stream) {
+  const size_t smem = sizeof(int) * (size_t)(bp.S + 1 > MZH_MULTI_MAX_NETS ? bp.S + 1 : MZH_MULTI_MAX_NETS);
+  hipLaunchKernelGGL(mzh_multi_tiles_kernel, dim3(1), dim3(MZH_MULTI_MAX_NETS), smem, stream, mp, n, R, bp);
+  return hipGetLastError();
+}
+
+// bp == nullptr: every root runs p.S simulations
 template <int R, bool OHL, bool SUP33>
 static hipError_t launch_multi_t(int grid, const MzhNet& net, const MzhSearchParams& p, const MzhMultiParams& mp,
-                                 hipStream_t stream) {
+                                 const MzhBudgetParams* bp, hipStream_t stream) {
   const size_t smem = search_smem_bytes<R>(p.S, OHL);
   const void* fn = reinterpret_cast<const void*>(&mzh_search_multi_kernel<R, OHL, SUP33>);
   hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   if (e != hipSuccess) return e;
-  e = mzh_launch_multi_tiles(mp, p.B, R, stream);
+  e = bp ? launch_budget_tiles(mp, *bp, p.B, R, stream) : mzh_launch_multi_tiles(mp, p.B, R, stream, p.S);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL((mzh_search_multi_kernel<R, OHL, SUP33>), dim3(grid), dim3(MZH_THREADS), smem, stream, net, p, mp);
   return hipGetLastError();
@@ -535,15 +701,24 @@ static hipError_t launch_multi_t(int grid, const MzhNet& net, const MzhSearchPar
 
 // the tile table of the batch, then mzh_search_multi_kernel<pl.R, pl.ohl, pl.sup33> on the table's upper bound
 // of workgroups; net is the set's network 0
+static hipError_t launch_multi(int grid, const MzhSearchPlan& pl, const MzhNet& net, const MzhSearchParams& p,
+                               const MzhMultiParams& mp, const MzhBudgetParams* bp, hipStream_t stream) {
+  if (pl.R == 32) {
+    if (pl.ohl) return pl.sup33 ? launch_multi_t<32, true, true>(grid, net, p, mp, bp, stream) : launch_multi_t<32, true, false>(grid, net, p, mp, bp, stream);
+    return pl.sup33 ? launch_multi_t<32, false, true>(grid, net, p, mp, bp, stream) : launch_multi_t<32, false, false>(grid, net, p, mp, bp, stream);
+  }
+  if (pl.ohl) return pl.sup33 ? launch_multi_t<16, true, true>(grid, net, p, mp, bp, stream) : launch_multi_t<16, true, false>(grid, net, p, mp, bp, stream);
+  return pl.sup33 ? launch_multi_t<16, false, true>(grid, net, p, mp, bp, stream) : launch_multi_t<16, false, false>(grid, net, p, mp, bp, stream);
+}
 hipError_t mzh_launch_search_multi(const MzhSearchPlan& pl, const MzhNet& net, const MzhSearchParams& p,
                                    const MzhMultiParams& mp, hipStream_t stream) {
-  const int grid = mzh_multi_max_tiles(p.B, pl.R, mp.M);
-  if (pl.R == 32) {
-    if (pl.ohl) return pl.sup33 ? launch_multi_t<32, true, true>(grid, net, p, mp, stream) : launch_multi_t<32, true, false>(grid, net, p, mp, stream);
-    return pl.sup33 ? launch_multi_t<32, false, true>(grid, net, p, mp, stream) : launch_multi_t<32, false, false>(grid, net, p, mp, stream);
-  }
-  if (pl.ohl) return pl.sup33 ? launch_multi_t<16, true, true>(grid, net, p, mp, stream) : launch_multi_t<16, true, false>(grid, net, p, mp, stream);
-  return pl.sup33 ? launch_multi_t<16, false, true>(grid, net, p, mp, stream) : launch_multi_t<16, false, false>(grid, net, p, mp, stream);
+  return launch_multi(mzh_multi_max_tiles(p.B, pl.R, mp.M), pl, net, p, mp, nullptr, stream);
+}
+// the same kernels on the tile table of the roots' own budgets, on the upper bound of the tiles bp.max_runs runs make
+// (mzh_multi_max_tiles with the runs in place of the networks)
+hipError_t mzh_launch_search_multi_budget(const MzhSearchPlan& pl, const MzhNet& net, const MzhSearchParams& p,
+                                          const MzhMultiParams& mp, const MzhBudgetParams& bp, hipStream_t stream) {
+  return launch_multi(mzh_multi_max_tiles(p.B, pl.R, bp.max_runs), pl, net, p, mp, &bp, stream);
 }
 
 template <int R>
@@ -580,8 +755,10 @@ static size_t probe_smem_bytes() { return (sizeof(ProbeSmem<R>) + 15) & ~(size_t
 size_t mzh_probe_smem_bytes(int R) { return R == 32 ? probe_smem_bytes<32>() : probe_smem_bytes<16>(); }
 
 // the tile table of n rows at R rows per tile (the prologue of every multi-network launch)
-hipError_t mzh_launch_multi_tiles(const MzhMultiParams& mp, int n, int R, hipStream_t stream) {
-  hipLaunchKernelGGL(mzh_multi_tiles_kernel, dim3(1), dim3(MZH_MULTI_MAX_NETS), 0, stream, mp, n, R);
+hipError_t mzh_launch_multi_tiles(const MzhMultiParams& mp, int n, int R, hipStream_t stream, int sims) {
+  MzhBudgetParams bp{};
+  bp.S = sims;
+  hipLaunchKernelGGL(mzh_multi_tiles_kernel, dim3(1), dim3(MZH_MULTI_MAX_NETS), 0, stream, mp, n, R, bp);
   return hipGetLastError();
 }
 

@@ -410,4 +410,11 @@ struct MzhTree {
     mzh_write_results(p, root0 + r, vis, st.rootW[r], st.rootN[r], st.mm[r].mmax, st.mm[r].mmin, st.extra[r],
                       st.steps[r], st.depth[r], [&](int j) { return (int)path[r * PL + j]; });
   }
+  // the same for a root that ran S simulations, its tile's budget, in a launch of p.S
+  __device__ __forceinline__ void results(const int r, const int S) {
+    int vis[MZH_A];
+    for (int a = 0; a < MZH_A; ++a) vis[a] = st.root[r].N[a];
+    mzh_write_results<true>(p, root0 + r, vis, st.rootW[r], st.rootN[r], st.mm[r].mmax, st.mm[r].mmin, st.extra[r],
+                            st.steps[r], st.depth[r], [&](int j) { return (int)path[r * PL + j]; }, S);
+  }
 };

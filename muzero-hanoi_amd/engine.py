@@ -418,14 +418,29 @@ class Engine:
         return out
 
     def search_multi(self, n_sims, *, net_index, obs, tie_idx, noise=None, action_u=None, minmax_in=None,
-                     temperature=1.0, deterministic=False, discount=0.8, eps=0.25, np1_ucb=False, out=None, tile=None):
+                     temperature=1.0, deterministic=False, discount=0.8, eps=0.25, np1_ucb=False, out=None, tile=None,
+                     sims=None, max_runs=None):
         """Batched search over the loaded weight set (load_weight_set): root b under network net_index[b], the
         roots of one network consecutive (net_index [B] non-decreasing, each in [0, set size)).  The other
         arguments and the result are search's; only the cooperative kernel has this form (tile = None | 16 | 32).
-        out["_status"] is the device's [2] int32 verdict: [0] = 1 where it refused net_index (nothing was
-        searched, no output written), [1] the tiles searched."""
+        sims: an int32 device tensor [B], root b runs sims[b] simulations (mzh_search_multi_budget) and gets what a
+        search_multi of sims[b] simulations gives it; n_sims is then the maximum (every entry in [0, n_sims]; it
+        sizes latent's rows and the power table).  Inside a network the budgets may come in any order.  max_runs:
+        an upper bound on the runs of equal (net_index, sims) among consecutive roots, which sizes the grid
+        (default: as many as the engine's tile workspace allows at 16-root tiles, at most B; never below 256).
+        out["_status"] is the device's [2] int32 verdict: [0] = 1 where it refused net_index or sims (nothing
+        was searched, no output written), [1] the tiles searched."""
         if getattr(self, "set_size", 0) < 1:
             raise RuntimeError("search_multi: no weight set loaded (load_weight_set)")
+        if sims is not None:
+            B = int(tie_idx.shape[0])
+            if not isinstance(sims, torch.Tensor) or sims.dtype != torch.int32 or sims.dim() != 1 or sims.shape[0] != B:
+                raise ValueError(f"search_multi: sims must be an int32 tensor with one entry per root ({B}), got "
+                                 f"{getattr(sims, 'dtype', type(sims).__name__)} {tuple(getattr(sims, 'shape', ()))}")
+            if max_runs is not None and int(max_runs) < 1:
+                raise ValueError(f"search_multi: max_runs must be >= 1, got {max_runs}")
+        elif max_runs is not None:
+            raise ValueError("search_multi: max_runs goes with sims")
         a, out = self._search_args(n_sims, obs=obs, replay=None, tie_idx=tie_idx, noise=noise, action_u=action_u,
                                    minmax_in=minmax_in, temperature=temperature, deterministic=deterministic,
                                    discount=discount, eps=eps, out=out, flags=search_flags(None, tile, np1_ucb))
@@ -438,7 +453,18 @@ class Engine:
         m.n_networks = self.set_size
         m.net_index = ptr(ni)
         m.status = ptr(status)
-        check(_lib.lib().mzh_search_multi(self._h, ctypes.byref(a), ctypes.byref(m), self._stream()), "mzh_search_multi")
+        if sims is None:
+            check(_lib.lib().mzh_search_multi(self._h, ctypes.byref(a), ctypes.byref(m), self._stream()), "mzh_search_multi")
+        else:
+            sd = sims.to(self.device).contiguous()
+            out["_keep"].append(sd)
+            b = _lib.BudgetArgs()
+            b.n_sims = ptr(sd)
+            # the workspace holds ceil(max_roots / 16) + 255 tiles; the grid is ceil(B / tile) + min(max_runs, B) - 1
+            room = -(-self.max_roots // 16) + 256 - -(-a.B // 16)
+            b.max_runs = max(1, min(a.B, room)) if max_runs is None else int(max_runs)
+            check(_lib.lib().mzh_search_multi_budget(self._h, ctypes.byref(a), ctypes.byref(m), ctypes.byref(b),
+                                                     self._stream()), "mzh_search_multi_budget")
         out["_plan"] = out.pop("_plan_struct").as_dict()
         out["_status"] = status
         return out

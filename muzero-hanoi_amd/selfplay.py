@@ -125,13 +125,20 @@ class _Lockstep:
             run.advance(kernel)     # the move's one host read; the next run.idx / run.n
 
     eng: the engine; env: the HanoiBatch, its last_obs the starts' observations; mm [B, 2]; net_index [B] int32 on
-    the device with a NetworkSet, else None; start [B] int64 on the device; idx (int64) / idx32 / n: the
+    the device with a NetworkSet, else None; sims [B] int32 on the device (each row's own simulation budget, at most
+    sp.S; a NetworkSet only) or None; start [B] int64 on the device; idx (int64) / idx32 / n: the
     unfinished rows in env order and their count; draw_index [B] on the device or None (rows)."""
 
     def __init__(self, sp, start_idx, minmax, seed, net_index, temperature, deterministic, legacy_rng=False,
-                 draw_index=None):
+                 draw_index=None, sims=None):
         start = torch.as_tensor(np.asarray(start_idx), dtype=torch.int64).reshape(-1)
         B = int(start.shape[0])
+        if sims is not None:  # checked before any device work
+            sims = np.asarray(sims)
+            if not isinstance(sp.network, NetworkSet):
+                raise ValueError("sims [B] needs a NetworkSet: only the multi-network search takes a budget per root")
+            if sims.dtype.kind not in "iu" or sims.shape != (B,) or (B and (sims.min() < 0 or sims.max() > sp.S)):
+                raise ValueError(f"sims must be {B} integer budgets in [0, {sp.S}], the play's n_simulations")
         self.sp, self.temperature, self.deterministic, self.legacy_rng = sp, temperature, deterministic, legacy_rng
         self.replay = isinstance(sp.network, RecordedNetwork)
         if self.replay and B != 1:
@@ -148,6 +155,11 @@ class _Lockstep:
             self.eng = _replay_engine(sp.N, sp.S) if self.replay else engine_for(sp.network, sp.S, B)
         dev = self.eng.device
         self.net_index = torch.as_tensor(ni, dtype=torch.int32).to(dev) if multi else None
+        # the budgets of the rows still playing are a subsequence of these: dropping rows never adds a run
+        self.sims, self.max_runs = None, None
+        if sims is not None:
+            self.sims = torch.as_tensor(sims.astype(np.int32)).to(dev)
+            self.max_runs = 1 + int(np.count_nonzero((np.diff(ni) != 0) | (np.diff(sims) != 0)))
         # with the legacy stream a move's draws are those of its unfinished rows in env order, whatever draw_index
         self.draw_index, self.n_draw = None, B
         if draw_index is not None and not legacy_rng:
@@ -199,6 +211,8 @@ class _Lockstep:
                   temperature=float(self.temperature), deterministic=bool(self.deterministic), discount=sp.discount,
                   eps=sp.eps, np1_ucb=sp.np1_ucb)
         if self.net_index is not None:  # a NetworkSet: idx is increasing, so the networks' envs stay consecutive
+            if self.sims is not None:  # sp.S is the largest budget; the rows keep theirs as they keep their network
+                kw.update(sims=self.sims.index_select(0, idx), max_runs=self.max_runs)
             out = self.eng.search_multi(sp.S, net_index=self.net_index.index_select(0, idx), obs=obs, **kw)
         elif self.replay:
             out = self.eng.search(sp.S, replay=sp.network.next_replay(self.eng.device), **kw)
@@ -243,18 +257,21 @@ class BatchedSelfPlay:
         self.np1_ucb = np1_ucb
 
     def play(self, start_idx, temperature=1.0, deterministic=False, seed=0, legacy_rng=False, minmax=None,
-             record_obs=False, net_index=None):
+             record_obs=False, net_index=None, sims=None, draw_index=None):
         """Play every env from start_idx[b] until done (goal or max_steps).
 
         minmax: [B, 2] (maximum, minimum) of each agent's MinMaxStats at the start (default: fresh,
         -inf / +inf); the final values come back as res["minmax"].  net_index: [B] with a NetworkSet (the
-        class docstring), else None.  Per move: one search over the unfinished envs, one mzh_env_step_observe
+        class docstring), else None.  sims: [B] integers with a NetworkSet, env b searches sims[b] simulations per
+        move (each in [0, n_simulations], any order inside a network; mzh_search_multi_budget), else None: every env
+        n_simulations.  draw_index [B]: as in play_perturbed.  Per move: one search over the unfinished envs, one mzh_env_step_observe
         launch through env_index, one host read (_Lockstep.advance).  Returns device tensors:
         per step t (rows of envs that were still playing): action, reward, pi, root_q, active,
         obs (record_obs: the observation searched); per env: steps, illegal (count), start_idx, minmax.
         An empty start_idx plays nothing: no launch, empty records.  RuntimeError if the env kernel counted an
         error, which a search's own actions cannot cause."""
-        run = _Lockstep(self, start_idx, minmax, seed, net_index, temperature, deterministic, legacy_rng)
+        run = _Lockstep(self, start_idx, minmax, seed, net_index, temperature, deterministic, legacy_rng, draw_index,
+                        sims)
         env, B, dev = run.env, run.env.B, run.eng.device
         rec = dict(action=[], reward=[], pi=[], root_q=[], active=[])
         if record_obs:
@@ -360,7 +377,7 @@ class BatchedSelfPlay:
                                  net_index=torch.from_numpy(net_index.astype(np.int32)) if multi else None)
 
     def play_plans(self, start_idx, max_plan_len, temperature=1.0, deterministic=False, seed=0, legacy_rng=False,
-                   minmax=None, net_index=None):
+                   minmax=None, net_index=None, sims=None):
         """Plan-ahead episodes (acting_experiments/planning_multiple_actions.py:111-183): every env searches
         once and executes the last simulation's selection path (mcts.return_latent_actions()[:max_plan_len])
         open loop, illegal moves included, and searches again only when that plan ran out before the episode
@@ -372,7 +389,8 @@ class BatchedSelfPlay:
         host read (unfinished envs left, error count).  Returns device tensors: per env steps, illegal
         (executed illegal moves), plans (searches), start_idx, minmax; per round r: action [R][L][B]
         (executed moves, -1 where nothing ran), reward [R][L][B] (int8 codes of mzh_env_step, 0 where nothing
-        ran), root_q [R][B] and search_action [R][B] (0 / -1 for envs without a search that round)."""
+        ran), root_q [R][B] and search_action [R][B] (0 / -1 for envs without a search that round).
+        sims: as in play (a budget per env), each >= 1."""
         L = int(max_plan_len)
         if L < 1:
             raise ValueError(f"play_plans: max_plan_len must be >= 1, got {max_plan_len}")
@@ -380,7 +398,9 @@ class BatchedSelfPlay:
             raise ValueError("play_plans: a plan needs n_simulations >= 1")
         if np.asarray(start_idx).size < 1:
             raise ValueError("play_plans: no start states")
-        run = _Lockstep(self, start_idx, minmax, seed, net_index, temperature, deterministic, legacy_rng)
+        if sims is not None and np.asarray(sims).size and np.asarray(sims).min() < 1:
+            raise ValueError("play_plans: a plan needs a budget >= 1 for every env")
+        run = _Lockstep(self, start_idx, minmax, seed, net_index, temperature, deterministic, legacy_rng, sims=sims)
         env, B, dev = run.env, run.env.B, run.eng.device
         plans = torch.zeros(B, dtype=torch.int32, device=dev)
         rec = dict(action=[], reward=[], root_q=[], search_action=[])
@@ -718,7 +738,7 @@ def _batch_starts(n_disks, episodes, start, start_idx, seed, goal_peg):
 
 def evaluate_networks(networks, n_disks, n_sims_range, *, episodes=1, start=None, start_idx=None, max_steps=200,
                       temperature=1.0, deterministic=False, seed=0, goal_peg=2, np1_ucb=False, max_plan_len=None,
-                      dirichlet_alpha=0.25, max_roots=65536, launch="lockstep"):
+                      dirichlet_alpha=0.25, max_roots=65536, launch="lockstep", budgets="each"):
     """evaluate's batched schedule for several networks at once -- the variants of an ablation sweep
     (checkpoint.ablation_variants; the reference runs acting_ablations.py once per variant): per budget one
     batch of len(networks) * episodes envs, network m's episodes consecutive and every network given the same
@@ -729,8 +749,18 @@ def evaluate_networks(networks, n_disks, n_sims_range, *, episodes=1, start=None
     launch: "lockstep" (that move loop) or "episodes": each batch to its end in one launch
     (BatchedSelfPlay.play_episodes over the set, its draw schedule: env b takes row [t, b] of one table drawn from
     the batch's seed); search-per-step episodes only, so not with max_plan_len.
+    budgets: "each" (a batch per budget, as above) or "fused": the budgets of the range play abreast -- per chunk of
+    max_roots one batch of len(networks) * len(n_sims_range) * episodes envs ordered network, then budget, then
+    episode, every env searching with its own budget in the one launch of a move (mzh_search_multi_budget; the
+    engine is sized by the largest budget, every budget >= 0).  The fused batch's synthetic draws are a schedule of
+    their own (the draws of env b of that batch: not those of the per-budget batches), so on more than one budget
+    its episodes are not those of "each"; on one budget the two are the same batch.  Lockstep only.
     networks: a networks.NetworkSet or a sequence of networks.  Returns a list with, per network, the dict
     evaluate returns (minmax None), scored by the same code."""
+    if budgets not in ("each", "fused"):
+        raise ValueError(f"evaluate_networks: budgets must be 'each' or 'fused', not {budgets!r}")
+    if budgets == "fused" and launch == "episodes":
+        raise ValueError("evaluate_networks: budgets='fused' is a lockstep form: the episode launch has one budget")
     nset = _network_set("evaluate_networks", networks)
     _check_plan("evaluate_networks", max_plan_len, n_sims_range)
     if launch not in ("lockstep", "episodes"):
@@ -741,6 +771,30 @@ def evaluate_networks(networks, n_disks, n_sims_range, *, episodes=1, start=None
         raise ValueError(f"evaluate_networks: max_roots must be >= 1, got {max_roots}")
     M = len(nset)
     scores = [_new_score() for _ in range(M)]
+    if budgets == "fused":
+        ns = [int(n) for n in n_sims_range]
+        if not ns or min(ns) < 0:
+            raise ValueError(f"evaluate_networks: budgets='fused' needs budgets >= 0, at least one, got {ns}")
+        sp = BatchedSelfPlay(nset, n_disks, max_steps, max(ns), goal_peg=goal_peg, np1_ucb=np1_ucb,
+                             dirichlet_alpha=dirichlet_alpha)
+        play = sp.play if max_plan_len is None else (lambda s, **kw: sp.play_plans(s, int(max_plan_len), **kw))
+        starts = _batch_starts(n_disks, episodes, start, start_idx, seed, goal_peg)
+        E, K = len(starts), len(ns)
+        all_starts, net_index = np.tile(starts, M * K), np.repeat(np.arange(M), K * E)
+        sims = np.tile(np.repeat(np.asarray(ns, np.int64), E), M)
+        steps, ill = [], []
+        for k, lo in enumerate(range(0, M * K * E, int(max_roots))):
+            sl = slice(lo, min(M * K * E, lo + int(max_roots)))
+            res = play(all_starts[sl], temperature=temperature, deterministic=deterministic, seed=seed + k,
+                       net_index=net_index[sl], sims=sims[sl])
+            steps.append(res["steps"].cpu().numpy())
+            ill.append(res["illegal"].cpu().numpy())
+        steps, ill = np.concatenate(steps), np.concatenate(ill)
+        for i, n in enumerate(ns):
+            for m in range(M):
+                sl = slice((m * K + i) * E, (m * K + i + 1) * E)
+                _score_budget(scores[m], n, n_disks, goal_peg, starts, steps[sl], ill[sl])
+        return [dict(**sc, minmax=None) for sc in scores]
     for n in n_sims_range:
         sp = BatchedSelfPlay(nset, n_disks, max_steps, int(n), goal_peg=goal_peg, np1_ucb=np1_ucb,
                              dirichlet_alpha=dirichlet_alpha)
