@@ -78,7 +78,12 @@ int mzh_stream_synchronize(void* stream);
 /* ---------------------------------------------------------------------------------------------
  * Engine.  Replaces the state the reference keeps in Python objects: the MuZeroNet weights
  * (networks.py:39-67) and the per-search node pool of MCTS/node.py (flat SoA tree workspace).
- *   n_disks   : Hanoi N (observation = 3N one-hot, env/hanoi.py:26-28, utils.py:9-25)
+ *   n_disks   : Hanoi N (observation = 3N one-hot, env/hanoi.py:26-28, utils.py:9-25), 1..16: an observation of
+ *               3..48 columns, zero-padded to 16, 32 or 48 (one to three k-blocks of the first representation
+ *               layer).  The test suite runs every kernel that takes a network at both ends of that range and
+ *               on either side of each block boundary (3, 6, 15, 18, 33 and 48 columns beside 9, 12 and 21;
+ *               tests/test_widths_gpu.py); the training update (mzh_train_update) takes up to 32 columns and is
+ *               run at 3 to 30.
  *   max_sims  : largest n_simulations a search on this engine may use (mcts.py:30)
  *   max_roots : largest root batch B
  *   support   : 33 (TD_return=True) or 1 (TD_return=False), networks.py:34-37

@@ -252,15 +252,21 @@ class Reference:
         print("\n" + line)
 
 
-def case_rows(net, n, seed=0, pool=512):
+def case_rows(net, n, seed=0, pool=512, obs_pool=None):
     """the case's 37 rows: the first 32 well-conditioned state rows and the first 5 well-conditioned arbitrary-float
     rows of a seeded stream that draws observation, action and policy_logit per candidate; well-conditioned: not
     in Reference.bad and without a hidden unit within NEAR0 of the kink.  Returns obs, action, policy_logit and
-    how many candidates were rejected."""
+    how many candidates were rejected.  obs_pool: the candidates' observations, `pool` state rows and then the float
+    rows, where the caller draws them itself (all_states enumerates 3^n states: not beyond a dozen discs); the
+    stream then draws action and policy_logit only."""
     rs = np.random.RandomState(7000 * n + seed)
-    st = state_obs(all_states(n)[rs.randint(0, 3 ** n, size=pool)])
-    fl = rs.uniform(-1.0, 2.0, size=(pool // 8, 3 * n)).astype(np.float32)
-    obs = np.concatenate([st, fl])
+    if obs_pool is None:
+        st = state_obs(all_states(n)[rs.randint(0, 3 ** n, size=pool)])
+        fl = rs.uniform(-1.0, 2.0, size=(pool // 8, 3 * n)).astype(np.float32)
+        obs = np.concatenate([st, fl])
+    else:
+        obs = np.asarray(obs_pool, np.float32)
+        assert obs.shape[1] == 3 * n and len(obs) > pool
     action = rs.randint(0, 6, size=len(obs)).astype(np.int32)
     pl = np.maximum(rs.randint(-3, 6, size=len(obs)), -1).astype(np.int32)
     ref = Reference(net, obs, action, pl)

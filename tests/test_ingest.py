@@ -293,8 +293,11 @@ def test_episode_longer_than_the_ring(device_sampling):
 
 @pytest.mark.gpu
 def test_other_widths():
-    """row widths that are no multiple of anything: A=4, d_state=12, U=3, n_step=2"""
+    """row widths that are no multiple of anything: A=4, d_state=12, U=3, n_step=2; and the observation widths
+    of 1 and 16 discs, d_state 3 and 48"""
     check_equal([make_record(13, 19, 11, A=4, D=12)], 90, False, ptr=80, n_step=2, unroll=3, n_action=4, D=12)
+    check_equal([make_record(14, 19, 11, D=3)], 90, False, ptr=80, D=3)
+    check_equal([make_record(15, 19, 11, D=48)], 90, True, ptr=80, D=48)
 
 
 @pytest.mark.gpu

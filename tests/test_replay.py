@@ -78,15 +78,17 @@ def test_device_sampling_needs_gpu_and_defaults():
 
 
 # ------------------------------------------------------------------------------------------- GPU
-def _pair(size, fill, seed, kind):
+def _pair(size, fill, seed, kind, d_state=9):
     """a host-sampling and a device-sampling Buffer holding the same transitions"""
     from muzero_hanoi_amd.buffer import Buffer
 
     g = np.random.default_rng(seed)
-    bufs = [Buffer(size, 5, d_state=9, n_action=6, device="cuda", device_sampling=d) for d in (False, True)]
+    bufs = [Buffer(size, 5, d_state=d_state, n_action=6, device="cuda", device_sampling=d) for d in (False, True)]
     T = fill
-    st = np.zeros((T, 9), np.float32)
-    st[np.arange(T), g.integers(0, 9, T)] = 1
+    st = np.zeros((T, d_state), np.float32)
+    st[np.arange(T), g.integers(0, d_state, T)] = 1
+    if d_state != 9:  # every column non-zero and distinct, so a dropped, doubled or shifted column changes bits
+        st += g.uniform(0.25, 0.75, (T, d_state)).astype(np.float32)
     data = (st, g.normal(size=(T, 5)).astype(np.float32), g.integers(0, 6, (T, 5)),
             g.dirichlet(np.ones(6), size=(T, 5)).astype(np.float32), g.normal(size=(T, 5)).astype(np.float32),
             _prios(g, T, kind))
@@ -108,7 +110,20 @@ def _host(x):
 def test_device_draw_equals_host_draw(size, fill, kind, m):
     """300,000 transitions: two block passes of np.sum's order and binary steps in HBM before the search
     window (the cdf sample's stride above 16)"""
-    host, dev = _pair(size, fill, size + m, kind)
+    _check_device_draw(size, fill, kind, m)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("d_state", [3, 48])
+def test_device_draw_equals_host_draw_at_the_width_range_ends(d_state):
+    """the sampled-rows comparison with observation rows of the narrowest and the widest engine width (1 and 16
+    discs), every column a distinct non-zero float"""
+    _check_device_draw(300, 200, "uniform", 64, d_state)
+
+
+def _check_device_draw(size, fill, kind, m, d_state=9):
+    host, dev = _pair(size, fill, size + m, kind, d_state)
+    assert dev.states.shape[1] == d_state
     assert np.array_equal(dev.priorities, host.priorities)
     for step in range(3):
         np.random.seed(step)

@@ -40,9 +40,21 @@ whether rows = 1 and rows = 2 gave the same bits:
     n3_s33_B33_U7            2.35e-05        2.34e-05   2.76e-05      2.26e-05   bit-identical
     n4_s33_B7_U1             6.87e-05        5.51e-05   6.67e-05      5.51e-05   bit-identical
     n7_s1_B2_U5              4.68e-07        3.65e-07   4.41e-07      4.22e-07   bit-identical
+    n1_s33_B24_U5            6.70e-05        5.81e-05   6.99e-05      6.01e-05   bit-identical
+    n1_s1_B7_U1              6.91e-07        3.47e-07   4.93e-07      4.62e-07   bit-identical
+    n5_s33_B24_U5            5.39e-05        4.33e-05   5.80e-05      4.50e-05   bit-identical
+    n6_s1_B24_U5             8.76e-07        6.15e-07   6.46e-07      6.13e-07   bit-identical
+    n10_s33_B33_U5           2.00e-04        1.82e-04   2.13e-04      1.94e-04   bit-identical
+    n10_s1_B24_U5            5.57e-07        3.22e-07   4.80e-07      3.61e-07   bit-identical
 
-The baseline moves a little with the host's torch build and thread count (a second host gave
-7.02e-05 / 5.98e-05 for n7_s33_B129_U5); the floors are the larger figures.  With support 33 both
+The last six rows cover the observation widths the update accepts beyond 9 to 21: in_dim 3, 15, 18 and 30 (the
+widest; the rows kernel stages the observation as [R][32] and train_check refuses in_dim > 32).  The floors are
+those of the first nine cases and stay there: n10_s33_B33_U5's baseline is larger than both, and its bound is
+4 x its own baseline like any other case's.
+
+The baseline moves with the host's torch build and thread count (a second host gave 7.02e-05 / 5.98e-05 for
+n7_s33_B129_U5, 2.92e-04 / 2.57e-04 for n1_s33_B24_U5 and 1.11e-04 / 1.02e-04 for n10_s33_B33_U5); the floors are
+the larger figures of the first nine.  With support 33 both
 torch fp32 and the kernel are dominated by the cancellation in the signed parabolic transform
 (sqrt(.) / 2 / eps - 1 / 2 / eps), which the kernel evaluates op by op as torch does.
 """
@@ -70,6 +82,12 @@ CASES = {
     "n3_s33_B33_U7": (3, 33, 33, 7, True, 0),     # U != 5: the LDS per-step plan, acts indexing
     "n4_s33_B7_U1": (4, 33, 7, 1, True, 0),       # U = 1, one tail workgroup at rows = 2
     "n7_s1_B2_U5": (7, 1, 2, 5, True, 0),         # the smallest batch the reference supports
+    "n1_s33_B24_U5": (1, 33, 24, 5, True, 0),     # in_dim 3: the narrowest observation, 29 unused stage columns
+    "n1_s1_B7_U1": (1, 1, 7, 1, True, 0),         # in_dim 3 with support 1, U = 1
+    "n5_s33_B24_U5": (5, 33, 24, 5, True, 0),     # in_dim 15: one column short of a 16-column block
+    "n6_s1_B24_U5": (6, 1, 24, 5, True, 0),       # in_dim 18: two columns into the second block
+    "n10_s33_B33_U5": (10, 33, 33, 5, True, 0),   # in_dim 30: the widest accepted, two columns from the stage's end
+    "n10_s1_B24_U5": (10, 1, 24, 5, True, 0),     # in_dim 30 with support 1
 }
 
 

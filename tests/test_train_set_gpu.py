@@ -245,6 +245,10 @@ VARIANTS = {
     "support 1, in_dim 12": case(n_disks=4, support=1, fills=(37, 515), kinds=("uniform", "heavy")),
     "in_dim 21": case(n_disks=7, fills=(37, 515), kinds=("heavy", "uniform")),
     "one network": case(fills=(37,), kinds=("heavy",), rounds=2),
+    # the widest and the narrowest observation the training update accepts: the [R][32] stage filled to two columns
+    # from its end, and 3 columns of it
+    "in_dim 30": case(n_disks=10, fills=(37, 515), kinds=("heavy", "uniform")),
+    "in_dim 3": case(n_disks=1, fills=(37, 515), kinds=("uniform", "heavy")),
 }
 
 
