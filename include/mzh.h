@@ -906,6 +906,27 @@ int mzh_play_episodes(mzh_engine* eng, const mzh_episode_args* args, mzh_stream 
 int mzh_play_episodes_multi(mzh_engine* eng, const mzh_episode_args* args, const mzh_multi_args* multi,
                             mzh_stream stream);
 
+/* Episodes of agents of different configurations in one launch: mzh_play_episodes_multi with env b running
+ * sweep->n_sims[b] simulations per move under sweep->discount[b].  Env b plays bit for bit as mzh_play_episodes plays
+ * it on an engine holding network net_index[b] alone with args.n_sims = n_sims[b] and args.discount = discount[b],
+ * from the same start state, the same column b of the [T][B] tables and the same minmax_in[b].  `args` and `multi`
+ * are mzh_play_episodes_multi's with that call's contract (a lone network is a set of one); args.n_sims is the
+ * launch's maximum: it decides the capacity check, the LDS plan (whether the latents sit in LDS) and the length of
+ * pow_table (n_sims + 1 entries), none of which enters a result.  Two launches, as mzh_play_episodes_multi: the
+ * prologue checks net_index and the budgets, then the sweep form of the episode kernel plays; a workgroup reads its
+ * env's budget and discount once per env.
+ * Refused before any launch: everything mzh_play_episodes_multi refuses without an engine, in its order; then sweep
+ * NULL or sweep->n_sims NULL (MZH_ERR_ARG), still without an engine; then that call's remaining refusals in their
+ * order, from engine NULL on.
+ * Refused on the device, exactly as a bad net_index is (and a bad net_index still is): a budget outside
+ * [0, args.n_sims] -- no env plays, no output of args is written (err_count included), and status[0] = 1. */
+typedef struct mzh_episode_sweep_args {
+  const int32_t* n_sims;   /* [B] device: simulations per move of env b, each in [0, args.n_sims] */
+  const double* discount;  /* [B] device, nullable: NULL = args.discount for every env */
+} mzh_episode_sweep_args;
+int mzh_play_episodes_sweep(mzh_engine* eng, const mzh_episode_args* args, const mzh_multi_args* multi,
+                            const mzh_episode_sweep_args* sweep, mzh_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

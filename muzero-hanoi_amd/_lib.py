@@ -137,6 +137,11 @@ class EpisodeArgs(ctypes.Structure):
                 ("minmax_out", _vp), ("err_count", _vp)]
 
 
+class EpisodeSweepArgs(ctypes.Structure):
+    """mirror of struct mzh_episode_sweep_args (include/mzh.h)"""
+    _fields_ = [("n_sims", _vp), ("discount", _vp)]
+
+
 class PlanArgs(ctypes.Structure):
     """mirror of struct mzh_plan_args (include/mzh.h)"""
     _fields_ = [("n_disks", _i32), ("goal_peg", _i32), ("max_steps", _i32), ("B", _i32), ("n", _i32),
@@ -238,6 +243,8 @@ SIGNATURES = {
     "mzh_episode_ingest": (ctypes.c_int, [ctypes.POINTER(IngestArgs), _vp]),
     "mzh_play_episodes": (ctypes.c_int, [_vp, ctypes.POINTER(EpisodeArgs), _vp]),
     "mzh_play_episodes_multi": (ctypes.c_int, [_vp, ctypes.POINTER(EpisodeArgs), ctypes.POINTER(MultiArgs), _vp]),
+    "mzh_play_episodes_sweep": (ctypes.c_int, [_vp, ctypes.POINTER(EpisodeArgs), ctypes.POINTER(MultiArgs),
+                                               ctypes.POINTER(EpisodeSweepArgs), _vp]),
 }
 
 _lib = None

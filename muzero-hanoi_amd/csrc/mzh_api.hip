@@ -1856,8 +1856,9 @@ extern "C" int mzh_episode_ingest(const mzh_ingest_args* a, mzh_stream stream) {
 
 // Whole episodes in one launch on the latency kernel (mzh.h): mzh_play_episodes (m == NULL, the engine's network)
 // and mzh_play_episodes_multi (the loaded set).  The checks that need no engine come first.
+// sweep: mzh_play_episodes_sweep, the set form with the envs' own budgets and discounts (w)
 static int play_episodes_common(mzh_engine* eng, const mzh_episode_args* a, const mzh_multi_args* m, bool multi,
-                                mzh_stream stream) {
+                                mzh_stream stream, bool sweep = false, const mzh_episode_sweep_args* w = nullptr) {
   if (!a) return fail(MZH_ERR_ARG, "play_episodes: args is NULL");
   if (a->B < 1 || a->n_sims < 0) return fail(MZH_ERR_ARG, "play_episodes: B=%d n_sims=%d", a->B, a->n_sims);
   if (a->goal_peg < 0 || a->goal_peg > 2) return fail(MZH_ERR_ARG, "play_episodes: goal_peg=%d outside 0..2", a->goal_peg);
@@ -1879,6 +1880,10 @@ static int play_episodes_common(mzh_engine* eng, const mzh_episode_args* a, cons
     if (!m->net_index) return fail(MZH_ERR_ARG, "play_episodes_multi: net_index is NULL");
     if (m->n_networks < 1 || m->n_networks > MZH_MULTI_MAX_NETS)
       return fail(MZH_ERR_ARG, "play_episodes_multi: n_networks=%d outside [1, %d]", m->n_networks, MZH_MULTI_MAX_NETS);
+  }
+  if (sweep) {
+    if (!w) return fail(MZH_ERR_ARG, "play_episodes_sweep: sweep is NULL");
+    if (!w->n_sims) return fail(MZH_ERR_ARG, "play_episodes_sweep: n_sims is NULL");
   }
   if (!eng) return fail(MZH_ERR_ARG, "play_episodes: engine is NULL");
   if (a->B > eng->max_roots) return fail(MZH_ERR_CAPACITY, "play_episodes: B=%d > max_roots=%d", a->B, eng->max_roots);
@@ -1914,9 +1919,16 @@ static int play_episodes_common(mzh_engine* eng, const mzh_episode_args* a, cons
   // the device check of net_index: the tile prologue of the other multi calls with the whole batch as the tile size
   // (one tile per network that has envs, at most min(M, B): inside the table), whose count the episode kernel reads
   const MzhMultiParams mp = multi_params(eng, m);
-  hipError_t e = mzh_launch_multi_tiles(mp, a->B, a->B, (hipStream_t)stream);
+  // (the sweep form: of the budgets too, each in [0, n_sims], by the same workgroup)
+  hipError_t e = mzh_launch_multi_tiles(mp, a->B, a->B, (hipStream_t)stream, sweep ? a->n_sims : 0,
+                                        sweep ? w->n_sims : nullptr);
   if (e != hipSuccess) return hip_fail(e, "play_episodes_multi net_index check launch");
   const MzhEpisodeSet es{m->net_index, eng->mntiles, eng->set_stride};
+  if (sweep) {
+    const MzhEpisodeSweep sw{w->n_sims, w->discount};
+    e = mzh_launch_episodes_sweep(pl, eng->setnet, eng->setonet, p, ep, es, sw, (hipStream_t)stream);
+    return e == hipSuccess ? MZH_OK : hip_fail(e, "play_episodes_sweep launch");
+  }
   e = mzh_launch_episodes_set(pl, eng->setnet, eng->setonet, p, ep, es, (hipStream_t)stream);
   return e == hipSuccess ? MZH_OK : hip_fail(e, "play_episodes_multi launch");
 }
@@ -1928,4 +1940,9 @@ extern "C" int mzh_play_episodes(mzh_engine* eng, const mzh_episode_args* a, mzh
 extern "C" int mzh_play_episodes_multi(mzh_engine* eng, const mzh_episode_args* a, const mzh_multi_args* m,
                                        mzh_stream stream) {
   return play_episodes_common(eng, a, m, true, stream);
+}
+
+extern "C" int mzh_play_episodes_sweep(mzh_engine* eng, const mzh_episode_args* a, const mzh_multi_args* m,
+                                       const mzh_episode_sweep_args* w, mzh_stream stream) {
+  return play_episodes_common(eng, a, m, true, stream, true, w);
 }

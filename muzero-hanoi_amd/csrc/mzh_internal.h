@@ -275,12 +275,18 @@ struct MzhBudgetParams {
   int S;                  // the launch's n_sims: every budget lies in [0, S]
   int max_runs;           // the caller's bound on the runs (the search grid is sized by it)
   int cap;                // entries of MzhMultiParams::tiles
+  // [B] caller's (nullable; only with n_sims == nullptr): budgets the prologue only checks, each in [0, S], and refuses
+  // as it refuses a bad net_index -- the tiles stay the networks' segments (mzh_play_episodes_sweep, whose kernel
+  // reads the budgets itself)
+  const int32_t* check_sims;
 };
 hipError_t mzh_launch_search_multi_budget(const MzhSearchPlan& pl, const MzhNet& net, const MzhSearchParams& p,
                                           const MzhMultiParams& mp, const MzhBudgetParams& bp, hipStream_t stream);
 // mzh_multi_tiles_kernel (mzh_search.hip) on mp.net_index [n]: the prologue of every multi-network launch (sims: the
 // budget written into every tile, the launch's n_sims for a search, 0 for the row kernels, which never read it)
-hipError_t mzh_launch_multi_tiles(const MzhMultiParams& mp, int n, int R, hipStream_t stream, int sims = 0);
+// check_sims: MzhBudgetParams::check_sims, with sims their upper bound
+hipError_t mzh_launch_multi_tiles(const MzhMultiParams& mp, int n, int R, hipStream_t stream, int sims = 0,
+                                  const int32_t* check_sims = nullptr);
 
 // Where a cooperative workgroup's rows [root0, root0 + nvalid), nvalid <= R, come from: MzhGridTile (workgroup
 // b owns the R rows from b * R: the single-network kernels) or a tile table entry (the multi-network kernels).
@@ -437,6 +443,15 @@ struct MzhEpisodeSet {
 };
 hipError_t mzh_launch_episodes_set(const MzhSearchPlan& pl, const MzhNet& net, const MzhOneNet& on, const MzhSearchParams& p,
                                    const MzhEpisodeParams& ep, const MzhEpisodeSet& es, hipStream_t stream);
+// the sweep side of mzh_play_episodes_sweep (a sixth kernel argument of the episode form): env b runs n_sims[b]
+// simulations per move, at most the launch's p.S, which sizes everything, under discount[b]
+struct MzhEpisodeSweep {
+  const int32_t* n_sims;   // [B] caller's, checked by mzh_multi_tiles_kernel before the episode launch
+  const double* discount;  // [B] caller's, nullable: p.discount for every env
+};
+hipError_t mzh_launch_episodes_sweep(const MzhSearchPlan& pl, const MzhNet& net, const MzhOneNet& on,
+                                     const MzhSearchParams& p, const MzhEpisodeParams& ep, const MzhEpisodeSet& es,
+                                     const MzhEpisodeSweep& sw, hipStream_t stream);
 size_t mzh_one_smem_bytes(int S, bool latl);
 hipError_t mzh_launch_one(const MzhSearchPlan& pl, const MzhNet& net, const MzhOneNet& on, const MzhSearchParams& p,
                           hipStream_t stream);

@@ -515,6 +515,19 @@ __device__ __forceinline__ int one_fresh(int v) {
 __device__ __forceinline__ const MzhEpisodeParams& one_ep(const MzhEpisodeParams& e) { return e; }
 __device__ __forceinline__ const MzhEpisodeParams& one_ep(const MzhEpisodeParams& e, const MzhEpisodeSet&) { return e; }
 __device__ __forceinline__ const MzhEpisodeSet& one_set(const MzhEpisodeParams&, const MzhEpisodeSet& s) { return s; }
+// the sweep form's sixth (the set form's arguments before it)
+__device__ __forceinline__ const MzhEpisodeParams& one_ep(const MzhEpisodeParams& e, const MzhEpisodeSet&,
+                                                          const MzhEpisodeSweep&) {
+  return e;
+}
+__device__ __forceinline__ const MzhEpisodeSet& one_set(const MzhEpisodeParams&, const MzhEpisodeSet& s,
+                                                        const MzhEpisodeSweep&) {
+  return s;
+}
+__device__ __forceinline__ const MzhEpisodeSweep& one_sweep(const MzhEpisodeParams&, const MzhEpisodeSet&,
+                                                            const MzhEpisodeSweep& w) {
+  return w;
+}
 
 // the views of the blob `off` bytes after o's (a set's networks lie at a constant stride: MzhEpisodeSet)
 __device__ __forceinline__ MzhOneNet one_net_at(const MzhOneNet& o, size_t off) {
@@ -564,9 +577,15 @@ __device__ __forceinline__ void one_load_net(const MzhOneNet& on, int t, bool A,
 // argument): env r plays under network net_index[r] of a loaded set, `on` being network 0's views.  A workgroup holds
 // the rows and the LDS image of its env's network and loads another network's only where its next env has one; every
 // other line is the episode form's, so an env plays bit for bit as on an engine holding its network alone.
+// EPA = MzhEpisodeParams, MzhEpisodeSet, MzhEpisodeSweep: the sweep form of the set form (mzh_play_episodes_sweep; a
+// sixth kernel argument): env r runs n_sims[r] <= p.S simulations per move under discount[r].  Everything sized by the
+// budget -- the LDS layout, the UCB table, pow_table, the latents' stride p.E and LATL -- stays the launch's, sized by
+// p.S; the env's own budget Sr (read once per env through a uniform address and made a scalar: a scalar loop bound) only
+// bounds the simulation loop and its `S > 0` / look-ahead tests, and its discount is the tree's.  None of the sized
+// things enters a result, so env r plays bit for bit as a lone launch of n_sims[r] and discount[r] plays it.
 template <bool SUP33, bool MMIN, bool LATL, class... EPA>
 __global__ __launch_bounds__(512, 2) void mzh_search_one_kernel(MzhNet net, MzhOneNet on, MzhSearchParams p, EPA... epa) {
-  constexpr bool EP = sizeof...(EPA) != 0, SET = sizeof...(EPA) == 2;
+  constexpr bool EP = sizeof...(EPA) != 0, SET = sizeof...(EPA) >= 2, SWEEP = sizeof...(EPA) == 3;
   extern __shared__ __align__(128) unsigned char smem_raw[];
   MzhOneSmem& sm = *reinterpret_cast<MzhOneSmem*>(smem_raw);
   float4* l2 = reinterpret_cast<float4*>(smem_raw + kSmBytes);
@@ -641,6 +660,20 @@ __global__ __launch_bounds__(512, 2) void mzh_search_one_kernel(MzhNet net, MzhO
         }
       }
     }
+    // the simulations and the discount of this trip's searches: the launch's, or (the sweep form) env r's own
+    int Sr = S;
+    double discr = disc;
+    if constexpr (SWEEP) {
+      const MzhEpisodeSweep& sw = one_sweep(epa...);
+      // (uniform addresses, but not provably read-only memory: vector loads, made scalars here so that the loop
+      // bound and the tree's discount take no vector register across the move loop)
+      Sr = __builtin_amdgcn_readfirstlane(sw.n_sims[r]);
+      if (sw.discount) {
+        const int2 d = *reinterpret_cast<const int2*>(&sw.discount[r]);
+        const int2 u{__builtin_amdgcn_readfirstlane(d.x), __builtin_amdgcn_readfirstlane(d.y)};
+        discr = __builtin_bit_cast(double, u);
+      }
+    }
     if constexpr (EP) {  // env r: oneHot_encoding(c_state) (utils.py:9-25) of its start; a peg outside 0..2 skips it
       const MzhEpisodeParams& ep = one_ep(epa...);
       if (wave == 0) {
@@ -665,7 +698,7 @@ __global__ __launch_bounds__(512, 2) void mzh_search_one_kernel(MzhNet net, MzhO
     const __amdgpu_buffer_rsrc_t lres = mzh_rsrc(p.htree + (size_t)r * p.E * MZH_H);
     const int tr = one_fresh(t), lane = tr & 63, n = tr & 255, c = lane & 7;
     const bool grp = wave == 0 && lane < 8;  // the root's 8-lane group (tree phases)
-    MzhOneTree tree{p, sm.root, tb, path, pc, pcv, table, inv, lane, disc, noised};
+    MzhOneTree tree{p, sm.root, tb, path, pc, pcv, table, inv, lane, discr, noised};
     const size_t ri = EP ? (size_t)mv * p.B + r : (size_t)r;  // the row of p's per-search arrays
     if constexpr (EP) {
       if (sm.pad[0] == 0) break;  // uniform: written before the last barrier
@@ -767,11 +800,11 @@ __global__ __launch_bounds__(512, 2) void mzh_search_one_kernel(MzhNet net, MzhO
       rs.leafA = 0;
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
       __builtin_amdgcn_wave_barrier();
-      if (S > 0) tree.template select<MMIN>(c, rs);
+      if (Sr > 0) tree.template select<MMIN>(c, rs);
       if (c == 0) sm.rsv = rs;
     }
     int lsum = 0;  // p.lockstep_levels: this root's selection levels below the root, summed
-    if (wave == 0 && S > 0) {
+    if (wave == 0 && Sr > 0) {
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
       __builtin_amdgcn_wave_barrier();
       const int e = sm.rsv.leafE, a = sm.rsv.leafA;
@@ -784,7 +817,7 @@ __global__ __launch_bounds__(512, 2) void mzh_search_one_kernel(MzhNet net, MzhO
     }
     __syncthreads();
     MZH_STAMP_DECL
-    for (int s = 0; s < S; ++s) {
+    for (int s = 0; s < Sr; ++s) {
       const int ts = one_fresh(t), ls = ts & 63, ns = ts & 255;
       // ---------------- expand via the network (mcts.py:88-106, networks.py:96-150) ----------------
       if (A) {  // dynamic_net.0: 64 latent steps, the one-hot column, bias, ReLU
@@ -863,7 +896,7 @@ __global__ __launch_bounds__(512, 2) void mzh_search_one_kernel(MzhNet net, MzhO
         MZH_STAMP(9);
         tree.backup(ls & 7, s, rs, ho.value, ho.reward, ho.pp);
         MZH_STAMP(10);
-        if (s + 1 < S) {
+        if (s + 1 < Sr) {
           __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
           __builtin_amdgcn_wave_barrier();
           tree.template select<MMIN>(ls & 7, rs);
@@ -871,7 +904,7 @@ __global__ __launch_bounds__(512, 2) void mzh_search_one_kernel(MzhNet net, MzhO
         if ((ls & 7) == 0) sm.rsv = rs;
         MZH_STAMP(11);
       }
-      if (wave == 0 && s + 1 < S) {
+      if (wave == 0 && s + 1 < Sr) {
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
         __builtin_amdgcn_wave_barrier();
         const int e = sm.rsv.leafE, a = sm.rsv.leafA;
@@ -1028,6 +1061,32 @@ hipError_t mzh_launch_episodes_set(const MzhSearchPlan& pl, const MzhNet& net, c
                   : launch_episode_set_t<true, false>(net, on, p, ep, es, pl.grid, stream);
   return pl.ohl ? launch_episode_set_t<false, true>(net, on, p, ep, es, pl.grid, stream)
                 : launch_episode_set_t<false, false>(net, on, p, ep, es, pl.grid, stream);
+}
+
+template <bool SUP33, bool LATL>
+static hipError_t launch_episode_sweep_t(const MzhNet& net, const MzhOneNet& on, const MzhSearchParams& p,
+                                         const MzhEpisodeParams& ep, const MzhEpisodeSet& es, const MzhEpisodeSweep& sw,
+                                         int grid, hipStream_t stream) {
+  const size_t smem = mzh_one_smem_bytes(p.S, LATL);
+  const void* fn = reinterpret_cast<const void*>(
+      &mzh_search_one_kernel<SUP33, true, LATL, MzhEpisodeParams, MzhEpisodeSet, MzhEpisodeSweep>);
+  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((mzh_search_one_kernel<SUP33, true, LATL, MzhEpisodeParams, MzhEpisodeSet, MzhEpisodeSweep>),
+                     dim3(grid), dim3(kThreads), smem, stream, net, on, p, ep, es, sw);
+  return hipGetLastError();
+}
+
+// the sweep form of the set launch (mzh_play_episodes_sweep): es.ntiles is the verdict of mzh_multi_tiles_kernel on
+// es.net_index AND sw.n_sims (every budget in [0, p.S]), launched before this on the same stream
+hipError_t mzh_launch_episodes_sweep(const MzhSearchPlan& pl, const MzhNet& net, const MzhOneNet& on,
+                                     const MzhSearchParams& p, const MzhEpisodeParams& ep, const MzhEpisodeSet& es,
+                                     const MzhEpisodeSweep& sw, hipStream_t stream) {
+  if (pl.sup33)
+    return pl.ohl ? launch_episode_sweep_t<true, true>(net, on, p, ep, es, sw, pl.grid, stream)
+                  : launch_episode_sweep_t<true, false>(net, on, p, ep, es, sw, pl.grid, stream);
+  return pl.ohl ? launch_episode_sweep_t<false, true>(net, on, p, ep, es, sw, pl.grid, stream)
+                : launch_episode_sweep_t<false, false>(net, on, p, ep, es, sw, pl.grid, stream);
 }
 
 #ifdef MZH_STAMPS

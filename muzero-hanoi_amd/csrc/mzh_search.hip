@@ -414,7 +414,8 @@ __device__ __forceinline__ void mzh_budget_tiles(const MzhMultiParams& mp, const
 // net_index leaves tile count 0 (the search kernel's workgroups all return) and status[0] = 1.  An entry
 // indexes LDS only after it passed the range and order checks, and nothing else ever uses it: the search
 // kernel takes the network from the table.  Every tile carries the budget bp.S.  With bp.n_sims the roots have
-// budgets of their own and the tiles are cut by mzh_budget_tiles.
+// budgets of their own and the tiles are cut by mzh_budget_tiles.  With bp.check_sims the tiles are the networks'
+// segments still, and a budget outside [0, bp.S] refuses the call as a bad net_index does.
 __global__ __launch_bounds__(MZH_MULTI_MAX_NETS) void mzh_multi_tiles_kernel(MzhMultiParams mp, int B, int R,
                                                                              MzhBudgetParams bp) {
   constexpr int T = MZH_MULTI_MAX_NETS;
@@ -431,6 +432,9 @@ __global__ __launch_bounds__(MZH_MULTI_MAX_NETS) void mzh_multi_tiles_kernel(Mzh
   // boundary i (0 <= i <= B) lies between entries i - 1 and i, with -1 before the first and M after the last:
   // networks prev + 1 .. v start at root i
   int bad = 0;
+  if (bp.check_sims)  // budgets the launch's kernel reads itself: each in [0, bp.S], or the call is refused
+    for (int i = tid; i < B; i += T)
+      if ((unsigned)bp.check_sims[i] > (unsigned)bp.S) bad = 1;
   for (int i = tid; i <= B; i += T) {
     const int prev = i > 0 ? mp.net_index[i - 1] : -1;
     const int v = i < B ? mp.net_index[i] : M;
@@ -755,9 +759,11 @@ static size_t probe_smem_bytes() { return (sizeof(ProbeSmem<R>) + 15) & ~(size_t
 size_t mzh_probe_smem_bytes(int R) { return R == 32 ? probe_smem_bytes<32>() : probe_smem_bytes<16>(); }
 
 // the tile table of n rows at R rows per tile (the prologue of every multi-network launch)
-hipError_t mzh_launch_multi_tiles(const MzhMultiParams& mp, int n, int R, hipStream_t stream, int sims) {
+hipError_t mzh_launch_multi_tiles(const MzhMultiParams& mp, int n, int R, hipStream_t stream, int sims,
+                                  const int32_t* check_sims) {
   MzhBudgetParams bp{};
   bp.S = sims;
+  bp.check_sims = check_sims;
   hipLaunchKernelGGL(mzh_multi_tiles_kernel, dim3(1), dim3(MZH_MULTI_MAX_NETS), 0, stream, mp, n, R, bp);
   return hipGetLastError();
 }

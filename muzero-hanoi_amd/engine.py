@@ -471,7 +471,7 @@ class Engine:
 
     def play_episodes(self, n_sims, state, max_steps, *, tie_idx, noise=None, action_u=None, minmax_in=None,
                       goal_peg=2, temperature=1.0, deterministic=False, discount=0.8, eps=0.25, np1_ucb=False,
-                      record_obs=False, visits=False, out=None, err=None, net_index=None):
+                      record_obs=False, visits=False, out=None, err=None, net_index=None, sims=None, discounts=None):
         """Whole episodes in one launch (mzh_play_episodes): env b starts from state[b] ([B, n_disks] uint8) and
         plays until it is done; move t of env b searches with row [t, b] of tie_idx [T, B] int32, noise [T, B, 6]
         float64 (None: no root noise) and action_u [T, B] float64 (None when deterministic), its MinMaxStats
@@ -486,8 +486,17 @@ class Engine:
         net_index [B] (non-decreasing, each in [0, set size)): env b plays under network net_index[b] of the loaded
         weight set instead of the engine's network (mzh_play_episodes_multi), with the result a lone engine of
         that network gives; the dict then has "_status", the device's [2] int32 verdict: [0] = 1 where it refused
-        net_index (nothing played, nothing written), [1] the networks that had envs."""
+        net_index (nothing played, nothing written), [1] the networks that had envs.
+        sims [B] int32 / discounts [B] float64 (device tensors; with net_index only): env b searches sims[b]
+        simulations per move under discounts[b] (mzh_play_episodes_sweep) and plays as a lone engine of its network
+        plays it with that budget and discount.  n_sims is then the launch's maximum (every entry in [0, n_sims]; a
+        budget outside is refused on the device as a bad net_index is); discounts alone goes with sims = n_sims for
+        every env, sims alone with `discount` for every env.  Both None: the calls and launches above."""
         d = self.device
+        sweep = sims is not None or discounts is not None
+        if sweep and net_index is None:
+            raise ValueError("play_episodes: sims / discounts [B] need net_index: only the episodes of a weight set "
+                             "take a budget and a discount per env")
         if net_index is not None and getattr(self, "set_size", 0) < 1:
             raise RuntimeError("play_episodes: no weight set loaded (load_weight_set)")
         if tie_idx.dim() != 2:
@@ -545,8 +554,22 @@ class Engine:
             keep.append(ni)
             m = _lib.MultiArgs()
             m.n_networks, m.net_index, m.status = self.set_size, ptr(ni), ptr(res["_status"])
-            check(_lib.lib().mzh_play_episodes_multi(self._h, ctypes.byref(a), ctypes.byref(m), self._stream()),
-                  "mzh_play_episodes_multi")
+            if sweep:
+                for name, t, dt in (("sims", sims, torch.int32), ("discounts", discounts, torch.float64)):
+                    if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != (B,)):
+                        got = f"{getattr(t, 'dtype', type(t).__name__)} {tuple(getattr(t, 'shape', ()))}"
+                        raise ValueError(f"play_episodes: {name} must be a {dt} tensor with one entry per env ({B}), "
+                                         f"got {got}")
+                sd = torch.full((B,), int(n_sims), dtype=torch.int32, device=d) if sims is None else dev(
+                    "sims", sims, torch.int32, (B,))
+                w = _lib.EpisodeSweepArgs()
+                w.n_sims, w.discount = ptr(sd), ptr(dev("discounts", discounts, torch.float64, (B,)))
+                keep.append(sd)
+                check(_lib.lib().mzh_play_episodes_sweep(self._h, ctypes.byref(a), ctypes.byref(m), ctypes.byref(w),
+                                                         self._stream()), "mzh_play_episodes_sweep")
+            else:
+                check(_lib.lib().mzh_play_episodes_multi(self._h, ctypes.byref(a), ctypes.byref(m), self._stream()),
+                      "mzh_play_episodes_multi")
         res["_keep"] = keep + [pt]
         return res
 

@@ -23,6 +23,7 @@ Same constructor and `training_loop(n_loops, min_replay_size, print_acc)` as the
     the search engine repacks the weights (networks.engine_for tracks parameter versions).
 """
 import ctypes
+import inspect
 import logging
 import math
 import warnings
@@ -35,7 +36,7 @@ from torch.autograd.graph import increment_version
 from .buffer import Buffer
 from .mcts import MCTS
 from .networks import MuZeroNet, NetworkSet
-from .rng import predraw
+from .rng import predraw, uses_noise
 from .selfplay import BatchedSelfPlay, episode_records, episodes_result, ingest_records, play_game
 from .utils import adjust_temperature, organise_transitions
 
@@ -209,10 +210,11 @@ class Muzero:
                                root_exploration_eps=self.mcts.root_exploration_eps, goal_peg=env.goal[0],
                                np1_ucb=self.mcts.np1_ucb)
 
-    def _draw_table(self, sp, n_games, deterministic=False):
-        """play_episodes' table for n_games envs from the global NumPy stream, move-major"""
+    def _draw_table(self, sp, n_games, deterministic=False, alpha=None):
+        """play_episodes' table for n_games envs from the global NumPy stream, move-major (alpha: the Dirichlet alpha
+        of the draws where it is not sp's, a population's agent under a launch of several configurations)"""
         T = int(self.env.max_steps)
-        flat = predraw(T * n_games, deterministic=deterministic, alpha=sp.alpha, eps=sp.eps)
+        flat = predraw(T * n_games, deterministic=deterministic, alpha=sp.alpha if alpha is None else alpha, eps=sp.eps)
         return tuple(None if x is None else x.reshape((T, n_games) + x.shape[1:]) for x in flat)
 
     def _games_played(self, res):
@@ -264,9 +266,23 @@ class MuzeroPopulation:
     per loop, the agents that updated in it.
     Agent m ends exactly as torch.manual_seed(s); mz = Muzero(..., selfplay="device"); np.random.seed(s);
     mz.training_loop(...) ends: parameters, optimiser state, buffer, MinMaxStats, tot_accuracy and stream
-    (self.streams[m], a np.random.get_state() tuple).  The caller's global NumPy stream is left as it was found."""
+    (self.streams[m], a np.random.get_state() tuple).  The caller's global NumPy stream is left as it was found.
 
-    def __init__(self, seeds, *, weights="device", update="each", **muzero_kwargs):
+    overrides: None, or one dict per seed -- agent m is Muzero(**{**muzero_kwargs, **overrides[m]}), so agents of
+    different configurations train abreast and the contract above holds for each with its own configuration.  The
+    keys of SWEEP_KEYS may differ per agent; everything else (the env, unroll_n_steps, TD_return, n_ep_x_loop, the
+    device and the selfplay / ingest / update_impl modes) is the launch's and the record's shape and stays shared.
+    Agents of different n_mcts_simulations or discount play in one mzh_play_episodes_sweep launch (the set's engine
+    made for the largest budget, env b with its agent's budget and discount); each agent's draw table and its
+    post-launch predraw use its own dirichlet_alpha, its ingest its own n_TD_step and buffer, its updates its own
+    lr, batch_s and n_update_x_loop.  Either all agents search with root noise or none does (the launch's noise table
+    is all or none, and a noise-free root keeps float32 priors); update="set" shares one batch_s and n_update_x_loop.
+    Without overrides, or with every dict empty, the launches and the results are those of a population of seeds."""
+
+    SWEEP_KEYS = ("n_mcts_simulations", "discount", "dirichlet_alpha", "lr", "n_TD_step", "buffer_size", "batch_s",
+                  "n_update_x_loop")
+
+    def __init__(self, seeds, *, weights="device", update="each", overrides=None, **muzero_kwargs):
         # update: "each" = every agent runs the lone loop's own draws, updates and write-backs one after the other;
         # "set" = the agents' update rounds as one launch sequence for all of them (SetUpdate: four launches and one
         # host read per loop instead of four launches and a synchronisation per agent and round), every agent still
@@ -282,22 +298,64 @@ class MuzeroPopulation:
         if muzero_kwargs.setdefault("selfplay", "device") != "device":
             raise ValueError("MuzeroPopulation trains Muzero(selfplay='device') agents: selfplay must be 'device', "
                              f"not {muzero_kwargs['selfplay']!r}")
-        self.seeds, self.weights, self.update = seeds, weights, update
+        overrides = self._check_overrides(seeds, update, overrides, muzero_kwargs)
+        self.seeds, self.weights, self.update, self.overrides = seeds, weights, update, overrides
         self.agents = []
-        for seed in seeds:
+        for seed, over in zip(seeds, overrides):
             torch.manual_seed(seed)
-            self.agents.append(Muzero(**muzero_kwargs))
+            self.agents.append(Muzero(**{**muzero_kwargs, **over}))
         self.streams = [np.random.RandomState(seed).get_state() for seed in seeds]
         self.networks = NetworkSet([a.networks for a in self.agents])
         self.active_history = []  # update="set": per loop, the indices of the agents that updated in it
         self._set_update = SetUpdate(self.agents) if update == "set" else None
+
+    @classmethod
+    def _check_overrides(cls, seeds, update, overrides, muzero_kwargs):
+        """the agents' own settings as one dict per seed (all empty without overrides), refused before any agent is
+        built: a list of another length, a key outside SWEEP_KEYS, root noise for some agents only, and with
+        update="set" a batch_s or n_update_x_loop of an agent's own"""
+        if overrides is None:
+            return [{} for _ in seeds]
+        overrides = [dict(o) for o in overrides]
+        if len(overrides) != len(seeds):
+            raise ValueError(f"MuzeroPopulation: overrides has {len(overrides)} entries for {len(seeds)} seeds (one "
+                             "dict per agent)")
+        for m, over in enumerate(overrides):
+            for key in over:
+                if key not in cls.SWEEP_KEYS:
+                    raise ValueError(f"MuzeroPopulation: agent {m} overrides {key!r}, which every agent of a "
+                                     "population shares (the launch's and the record's shape); the keys an agent "
+                                     f"may set are {', '.join(cls.SWEEP_KEYS)}")
+                if update == "set" and key in ("batch_s", "n_update_x_loop"):
+                    raise ValueError(f"MuzeroPopulation(update='set'): agent {m} overrides {key!r}, but the set's "
+                                     "update rounds share one shape; use update='each'")
+        if "dirichlet_alpha" in muzero_kwargs or all("dirichlet_alpha" in o for o in overrides):
+            # the eps every agent's MCTS is built with (Muzero passes none: the constructor's default)
+            eps = inspect.signature(MCTS.__init__).parameters["root_exploration_eps"].default
+            alphas = [{**muzero_kwargs, **o}["dirichlet_alpha"] for o in overrides]
+            noisy = [uses_noise(False, x, eps) for x in alphas]
+            if any(noisy) != all(noisy):
+                m = noisy.index(not noisy[0])
+                raise ValueError(f"MuzeroPopulation: agent {m} with 'dirichlet_alpha'={alphas[m]} searches "
+                                 f"{'with' if noisy[m] else 'without'} root noise and agent 0 with {alphas[0]} "
+                                 f"{'with' if noisy[0] else 'without'}: the launch's noise table is for all agents or "
+                                 "for none, and a noise-free root keeps float32 priors")
+        return overrides
 
     def training_loop(self, n_loops, min_replay_size, print_acc=50):
         """Muzero.training_loop of every agent, loop by loop abreast.  Returns the list of the agents' tot_accuracy."""
         logging.info("Training started \n")
         agents, M = self.agents, len(self.agents)
         first, E = agents[0], agents[0].n_ep_x_loop
-        T, sp = int(first.env.max_steps), first._selfplay(self.networks)
+        # the launch's settings: the set's engine is made for the largest budget; where budgets or discounts differ,
+        # env b plays with its agent's own (the sweep form of the launch), else the launch is a population of seeds'
+        budgets = [int(a.mcts.n_simulations) for a in agents]
+        T, sp = int(first.env.max_steps), agents[int(np.argmax(budgets))]._selfplay(self.networks)
+        alphas = [a.mcts.root_dirichlet_alpha for a in agents]  # each agent's draws take its own Dirichlet alpha
+        sweep = {}
+        if len(set(budgets)) > 1 or len({float(a.discount) for a in agents}) > 1:
+            sweep = dict(sims=np.repeat(np.asarray(budgets, np.int32), E),
+                         discounts=np.repeat(np.asarray([a.discount for a in agents], np.float64), E))
         start = np.full(M * E, first.env.init_state_idx, np.int64)
         net_index = np.repeat(np.arange(M), E)
         logs = [a._new_log() for a in agents]
@@ -309,13 +367,14 @@ class MuzeroPopulation:
                 tables, drawn_from = [], list(self.streams)
                 for m, a in enumerate(agents):
                     np.random.set_state(self.streams[m])
-                    tables.append(a._draw_table(sp, E))
+                    tables.append(a._draw_table(sp, E, alpha=alphas[m]))
                     self.streams[m] = np.random.get_state()
                 draws = tuple(None if col[0] is None else torch.from_numpy(np.concatenate(col, axis=1))
                               for col in zip(*tables))
                 minmax = np.repeat([[a.mcts.min_max_stats.maximum, a.mcts.min_max_stats.minimum] for a in agents], E,
                                    axis=0)
-                out = sp._launch_episodes(start, draws, minmax, adjust_temperature(n * E), False, net_index, self.weights)
+                out = sp._launch_episodes(start, draws, minmax, adjust_temperature(n * E), False, net_index,
+                                          self.weights, **sweep)
                 *steps, n_err = (int(x) for x in torch.cat([out["steps"], out["err"]]).cpu())  # the one host read
                 if n_err:
                     raise RuntimeError(f"mzh_play_episodes_multi refused {n_err} start state(s)")
@@ -326,7 +385,7 @@ class MuzeroPopulation:
                     cols = slice(m * E, (m + 1) * E)
                     if E == 1:  # the one-env schedule: the stream as the moves played leave it
                         np.random.set_state(drawn_from[m])
-                        predraw(steps[m], deterministic=False, alpha=sp.alpha, eps=sp.eps)
+                        predraw(steps[m], deterministic=False, alpha=alphas[m], eps=sp.eps)
                     else:
                         np.random.set_state(self.streams[m])
                     played = a._games_played(episodes_result(out, start[cols], max(steps[cols]), cols))

@@ -294,7 +294,7 @@ class BatchedSelfPlay:
         return dict(res, steps=env.steps_total, illegal=env.illegal_total, start_idx=run.start, minmax=run.mm)
 
     def play_episodes(self, start_idx, temperature=1.0, deterministic=False, seed=0, legacy_rng=False, minmax=None,
-                      draws=None, net_index=None, weights="auto"):
+                      draws=None, net_index=None, weights="auto", sims=None, discounts=None):
         """`play(record_obs=True)` as ONE launch (Engine.play_episodes, mzh_play_episodes): a workgroup of the
         latency kernel takes an env and plays it to its end -- search, action draw, env step and record -- without
         returning to the host.  A live network or, with net_index [B] (the class docstring), a NetworkSet whose
@@ -316,6 +316,10 @@ class BatchedSelfPlay:
         after the launch the stream is put back and advanced by rng.predraw(steps), so it is left exactly
         where play(legacy_rng=True) leaves it.
         weights: how a NetworkSet's engine picks up changed parameters (networks.engine_for_set).
+        sims [B] integers / discounts [B] floats, with a NetworkSet only: env b searches sims[b] simulations per move
+        (each in [0, n_simulations]; None: n_simulations) under discounts[b] (None: the play's discount), all envs
+        still in the one launch (mzh_play_episodes_sweep), each as a lone play of its network with that budget and
+        discount.  Both None: the launches above.
         RuntimeError if the kernel refused a start state (a peg outside 0..2: not reachable from start_idx)."""
         start = np.asarray(start_idx, np.int64).reshape(-1)
         B, T = int(start.shape[0]), int(self.max_steps)
@@ -323,8 +327,20 @@ class BatchedSelfPlay:
         if isinstance(self.network, RecordedNetwork):
             raise ValueError("play_episodes: live networks only (no RecordedNetwork)")
         multi = isinstance(self.network, NetworkSet)
+        if (sims is not None or discounts is not None) and not multi:  # checked before any device work
+            raise ValueError("play_episodes: sims / discounts [B] need a NetworkSet: only the episodes of a network "
+                             "set take a budget and a discount per env")
         if multi != (net_index is not None):
             raise ValueError("play_episodes: net_index [B] is required with a NetworkSet and only accepted with one")
+        if sims is not None:
+            sims = np.asarray(sims)
+            if sims.dtype.kind not in "iu" or sims.shape != (B,) or (B and (sims.min() < 0 or sims.max() > self.S)):
+                raise ValueError(f"play_episodes: sims must be {B} integer budgets in [0, {self.S}], the play's "
+                                 "n_simulations")
+        if discounts is not None:
+            discounts = np.asarray(discounts, np.float64)
+            if discounts.shape != (B,):
+                raise ValueError(f"play_episodes: discounts must be {B} floats, got shape {discounts.shape}")
         if multi:
             ni = np.asarray(net_index, np.int64).reshape(-1)
             if ni.shape[0] != B or (B and (ni.min() < 0 or ni.max() >= len(self.network) or np.any(np.diff(ni) < 0))):
@@ -348,7 +364,8 @@ class BatchedSelfPlay:
             draws = tuple(None if x is None else torch.from_numpy(x).reshape((T, B) + x.shape[1:]) for x in flat)
         t_max = 0
         try:
-            out = self._launch_episodes(start, draws, minmax, temperature, deterministic, ni if multi else None, weights)
+            out = self._launch_episodes(start, draws, minmax, temperature, deterministic, ni if multi else None,
+                                        weights, sims, discounts)
             steps = out["steps"]
             t_max, n_err = (int(x) for x in torch.stack([steps.max(), out["err"][0]]).cpu())  # the one host read
         finally:
@@ -359,9 +376,11 @@ class BatchedSelfPlay:
             raise RuntimeError(f"mzh_play_episodes refused {n_err} start state(s)")
         return episodes_result(out, start, t_max)
 
-    def _launch_episodes(self, start, draws, minmax, temperature, deterministic, net_index, weights="auto"):
+    def _launch_episodes(self, start, draws, minmax, temperature, deterministic, net_index, weights="auto", sims=None,
+                         discounts=None):
         """play_episodes' launch, without its host read: Engine.play_episodes' dict for the starts `start` (int64
-        array [B]) on the checked table `draws`; net_index: an int64 array [B] with a NetworkSet, else None"""
+        array [B]) on the checked table `draws`; net_index: an int64 array [B] with a NetworkSet, else None; sims /
+        discounts: checked arrays [B] (a NetworkSet only) or None"""
         B, T = int(start.shape[0]), int(self.max_steps)
         multi = net_index is not None
         eng = engine_for_set(self.network, self.S, B, weights=weights) if multi else engine_for(self.network, self.S, B)
@@ -374,7 +393,11 @@ class BatchedSelfPlay:
                                  goal_peg=self.goal_peg, temperature=float(temperature),
                                  deterministic=bool(deterministic), discount=self.discount, eps=self.eps,
                                  np1_ucb=self.np1_ucb, record_obs=True,
-                                 net_index=torch.from_numpy(net_index.astype(np.int32)) if multi else None)
+                                 net_index=torch.from_numpy(net_index.astype(np.int32)) if multi else None,
+                                 sims=None if sims is None else torch.from_numpy(
+                                     np.asarray(sims).astype(np.int32)).to(dev),
+                                 discounts=None if discounts is None else torch.from_numpy(
+                                     np.asarray(discounts, np.float64)).to(dev))
 
     def play_plans(self, start_idx, max_plan_len, temperature=1.0, deterministic=False, seed=0, legacy_rng=False,
                    minmax=None, net_index=None, sims=None):
