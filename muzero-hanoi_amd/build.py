@@ -16,7 +16,8 @@ CSRC = os.path.join(HERE, "csrc")
 REPO = os.path.dirname(HERE)
 LIB = os.path.join(HERE, "libmzh.so")
 OBJ = os.path.join(HERE, "_obj")
-SOURCES = ["mzh_api.hip", "mzh_search.hip", "mzh_wave.hip", "mzh_one.hip", "mzh_env.hip", "mzh_train.hip",
+SOURCES = ["mzh_api.hip", "mzh_api_weights.hip", "mzh_api_memo.hip", "mzh_api_search.hip", "mzh_api_rows.hip",
+           "mzh_api_train.hip", "mzh_search.hip", "mzh_wave.hip", "mzh_one.hip", "mzh_env.hip", "mzh_train.hip",
            "mzh_replay.hip", "mzh_ingest.hip", "mzh_saliency.hip", "mzh_repack.hip", "mzh_pgrad.hip"]
 # host-only sources, compiled by g++: mzh_rng.cpp like the NumPy C code it restates (no -march: no FMA;
 # see csrc/mzh_rng.cpp), mzh_pack.cpp (the weight packers: copies only, no HIP) so that a plain C++

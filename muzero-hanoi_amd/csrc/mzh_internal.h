@@ -1,6 +1,6 @@
 // mzh_internal.h -- parameter blocks shared by the launchers (mzh_search.hip) and the C ABI
-// implementation (mzh_api.hip), and the device-pointer form of the wave and latency weight layouts that
-// mzh_pack.cpp fills (its offsets, and the MZH_ONE_* constants, come from mzh_pack.h).
+// implementation (the host units mzh_api*.hip, through mzh_host.h), and the device-pointer form of the wave and
+// latency weight layouts that mzh_pack.cpp fills (its offsets, and the MZH_ONE_* constants, come from mzh_pack.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -231,7 +231,7 @@ struct MzhOneNet {
   const float4* l2;
 };
 
-// Every template argument of one search launch, decided once on the host (mzh_api.hip make_plan) and
+// Every template argument of one search launch, decided once on the host (mzh_api_search.hip make_plan) and
 // used both to launch and to report the launched instantiation (mzh_search_plan_query)
 struct MzhSearchPlan {
   int wave;    // 1: mzh_wave_kernel<nt, replay, sup33>; 0: mzh_search_kernel<R, replay, ohl, sup33, mmin>

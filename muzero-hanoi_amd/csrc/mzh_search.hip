@@ -666,7 +666,7 @@ static hipError_t launch_search_occ2(const MzhNet& net, const MzhSearchParams& p
   return hipGetLastError();
 }
 
-// the instantiation the plan names (mzh_api.hip make_plan decides every template argument)
+// the instantiation the plan names (mzh_api_search.hip make_plan decides every template argument)
 hipError_t mzh_launch_search(const MzhSearchPlan& pl, const MzhNet& net, const MzhSearchParams& p, hipStream_t stream) {
   if (pl.occ2) {
     if (pl.sup33) return pl.mmin ? launch_search_occ2<true, true>(net, p, stream) : launch_search_occ2<true, false>(net, p, stream);

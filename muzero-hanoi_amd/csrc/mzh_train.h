@@ -1,5 +1,5 @@
 // mzh_train.h -- parameter blocks of the fused training update (mzh_train.hip), filled by the C
-// ABI (mzh_api.hip: mzh_train_update, with the layer shapes of mzh_pack.h's table).
+// ABI (mzh_api_train.hip: mzh_train_update, with the layer shapes of mzh_pack.h's table).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

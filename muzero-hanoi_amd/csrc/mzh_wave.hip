@@ -1125,7 +1125,7 @@ hipError_t mzh_launch_wave_search(const MzhSearchPlan& pl, const MzhWNet& net, c
 }
 
 // ------------------------------------------------------------------------------------------
-// Expansion-memo fill (mzh_api.hip memo_build).  Level rows are ordered (state, node): row r of a level is
+// Expansion-memo fill (mzh_api_memo.hip memo_fill).  Level rows are ordered (state, node): row r of a level is
 // move r % 6 from row r / 6 of the level above.
 // ------------------------------------------------------------------------------------------
 // the level's recurrent-inference input: parent latents (natural unit order) repeated per move, and the moves

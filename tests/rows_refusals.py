@@ -1,5 +1,5 @@
 """What mzh_probe_actions, mzh_saliency and mzh_param_grads refuse before any device or engine is needed: the cases
-and the checks, once, for the three entry points -- they share one argument checker (rows_check, csrc/mzh_api.hip).
+and the checks, once, for the three entry points -- they share one argument checker (rows_check, csrc/mzh_api_rows.hip).
 tests/test_legality_cpu.py, test_saliency_cpu.py and test_pgrad_cpu.py each run them against their own entry point;
 every text must carry that entry point's prefix.
 """

@@ -11,8 +11,9 @@ import pytest
 from conftest import ROOT
 
 # (n_disks, support): in_dim 3, 12, 18, 33, 48 -> 1, 1, 2, 3, 3 first-layer k-blocks, both head kinds, ragged
-# in_dim.  The hashes are those of the blob the packers produced while they were still part of
-# mzh_api.hip (recorded from that code, canonical weight i = i + 1): the device blob is byte-identical.
+# in_dim.  The hashes are those of the blob the packers produced while they were still part of the C ABI's
+# host code (now split: the loaders that upload the blob are in csrc/mzh_api_weights.hip), recorded from that
+# code with canonical weight i = i + 1: the device blob is byte-identical.
 CASES = [(1, 1, "b7827b302f6215ec"), (4, 33, "0ab989dc40ac5b9d"), (6, 1, "d5adb99db29eb745"),
          (11, 33, "de9ba4f6e5d06fe5"), (16, 33, "991661f028a0f789")]
 

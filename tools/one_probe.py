@@ -1,4 +1,4 @@
-"""Latency kernel vs cooperative kernel by batch size (the crossover behind mzh_api.hip kOneMaxRoots), and the
+"""Latency kernel vs cooperative kernel by batch size (the crossover behind mzh_api_search.hip kOneMaxRoots), and the
 drop-in run_mcts call broken into kernel and host time.
 
     python tools/one_probe.py [--out profiles/r06_one_probe.json] [--run-mcts-only]
