@@ -676,10 +676,14 @@ __device__ __forceinline__ void mzh_mma_store(floatx4* f, float* bv, const MzhCh
 }
 
 // normalize_h_state (networks.py:191-196): 8 lanes per row, 8 elements per lane.
-// a / b for a >= 0 and a normal b > 0, from y = RN(1/b) (Markstein: q = RN(a*y), the fma residual
-// is exact, one correction step gives RN(a/b)).  Exact unless the residual can underflow: `slow`
+// a / b for a >= 0 and a normal b in (0, 2^126], from y = RN(1/b) (Markstein: q = RN(a*y), the fma
+// residual is exact, one correction step gives RN(a/b)).  Exact unless the residual can underflow: `slow`
 // flags a != 0 with a or the quotient below 2^-100, and the caller redoes the wave with IEEE
-// division (tests/test_markstein.py checks the fp32 and fp64 forms against true division).
+// division.  Above b = 2^126 y is subnormal and short of bits, and some quotients come out one ulp off
+// with `slow` clear: a caller whose b can be that large decides it from b (the replay draw does; the
+// normalisations' b is a difference of latents).  tests/test_markstein.py checks this form on the CPU
+// (oracle/mzh_oracle.c orc_markstein_f32) against true division on both sides of the bound; the fp64 form
+// it checks is mzh_mcts.h mzh_div.
 __device__ __forceinline__ float mzh_fdiv(float a, float b, float y, bool& slow) {
   const float q = a * y;
   const float r = __builtin_fmaf(-q, b, a);

@@ -282,9 +282,14 @@ __device__ __forceinline__ void replay_sample_body(Args& a, const int n, const d
   // partial sum of the P_i is a multiple of 2^-51 below 4, so these float64 additions in any order are
   // exact and the prefixes are NumPy's cumsum values; else (or if invalid) the values written here are
   // replaced below.  Quotients by Markstein from y = RN(1/s) (mzh_fdiv: exact unless an operand is tiny,
-  // then the wave divides in IEEE).
+  // then the wave divides in IEEE).  mzh_fdiv needs a normal s with a normal reciprocal: above s = 2^126 y is
+  // subnormal, carries fewer than 24 bits and leaves about 1 quotient in 10^7 one ulp off
+  // (tests/test_markstein.py); for a subnormal s below 2^-128 y is inf and a wave that holds only p_i = 0 (no
+  // lane flags) would keep 0 * inf = NaN.  Outside [2^-126, 2^126] every wave starts each tile flagged and
+  // takes the IEEE quotients.
   constexpr int NS = 4, SUB = RT * 4;
   const float y = 1.0f / s;
+  const bool ieee = !(s >= 0x1p-126f && s <= 0x1p126f);
   int valid = (s > 0.f && s < __builtin_inff()) ? 1 : 0, exact = 1;
   double carry = 0.0;
   static_assert(NS * NWAVE == 64, "one wave scans the wave totals");
@@ -316,7 +321,7 @@ __device__ __forceinline__ void replay_sample_body(Args& a, const int n, const d
 #pragma unroll
       for (int t = 0; t < 4; ++t) x[j][t] = xn[j][t];
     if (t0 + NS * SUB < n) load_tile(t0 + NS * SUB, xn);
-    bool slow = false;
+    bool slow = ieee;
     float q[NS][4];
 #pragma unroll
     for (int j = 0; j < NS; ++j)

@@ -417,6 +417,55 @@ long orc_markstein_mismatches(long n, uint64_t seed) {
   return bad;
 }
 
+/* The fp32 form (csrc/mzh_device.h mzh_fdiv): the same three operations from y = RN(1/b) and its `slow`
+ * predicate (a != 0 with a or the result below 2^-100: the caller then divides in IEEE). */
+float orc_markstein_f32(float a, float b, int* slow) {
+  const float y = 1.0f / b;
+  const float q = a * y;
+  const float r = fmaf(-q, b, a);
+  const float res = fmaf(r, y, q);
+  *slow = (a != 0.0f) & ((a < 0x1p-100f) | (res < 0x1p-100f));
+  return res;
+}
+
+/* Property check for mzh_fdiv over the replay draw's operands, P_i = p_i / np.sum(p): 0 <= a <= b, a over
+ * all exponents from b's down to the subnormals (and 0, and b itself).  above == 0: b uniform in exponent and
+ * mantissa over the normal floats up to 2^126, the largest b whose reciprocal is normal; above == 1: b over
+ * (2^126, FLT_MAX], where y is subnormal and carries fewer than 24 bits, a within 2^-8 of b (the mismatches
+ * there are rare, about 2 in 10^7).  Returns how many results with `slow` clear differ from a / b. */
+long orc_markstein_f32_mismatches(long n, uint64_t seed, int above) {
+  long bad = 0;
+  mk_s = seed ? seed : 88172645463325252ull;
+  for (long i = 0; i < n; ++i) {
+    uint32_t bb, ab;
+    if (above) {
+      bb = (253u << 23) | (uint32_t)(mk_next() & 0x7fffffu);       /* [2^126, 2^127) */
+      if (mk_next() & 7) bb += 1u << 23;                            /* mostly [2^127, FLT_MAX]: y loses 2 bits */
+      if (bb == (253u << 23)) bb += 1;                              /* 2^126 itself is below the bound */
+    } else {
+      bb = ((uint32_t)(1 + mk_next() % 252) << 23) | (uint32_t)(mk_next() & 0x7fffffu); /* [2^-126, 2^126) */
+      if (mk_next() % 64 == 0) bb = 253u << 23;                     /* 2^126 */
+    }
+    switch (above ? 7 : mk_next() % 8) {
+      case 0: ab = 0; break;
+      case 1: ab = bb; break;
+      case 2: ab = (uint32_t)(mk_next() % ((uint64_t)bb + 1)); break; /* any bit pattern at or below b's */
+      default: {                                                     /* within 2^-30 of b: the draw's range */
+        const uint32_t eb = bb >> 23, down = (uint32_t)(mk_next() % (above ? 8 : 31));
+        ab = ((eb > down ? eb - down : 0u) << 23) | (uint32_t)(mk_next() & 0x7fffffu);
+        if (ab > bb) ab = bb;
+      }
+    }
+    float a, b;
+    memcpy(&a, &ab, 4);
+    memcpy(&b, &bb, 4);
+    int slow;
+    const float res = orc_markstein_f32(a, b, &slow);
+    if (!slow && res != a / b) ++bad;
+  }
+  return bad;
+}
+
 double orc_ucb_table(int n) {
   return (log((double)(n + PB_C_BASE + 1) / (double)PB_C_BASE) + PB_C_INIT) * sqrt((double)n);
 }

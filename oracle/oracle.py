@@ -47,6 +47,10 @@ def lib():
         L.orc_logits_expectation.argtypes = [ctypes.c_void_p, ctypes.c_int]
         L.orc_markstein_mismatches.restype = ctypes.c_long
         L.orc_markstein_mismatches.argtypes = [ctypes.c_long, ctypes.c_uint64]
+        L.orc_markstein_f32.restype = ctypes.c_float
+        L.orc_markstein_f32.argtypes = [ctypes.c_float, ctypes.c_float, ctypes.POINTER(ctypes.c_int)]
+        L.orc_markstein_f32_mismatches.restype = ctypes.c_long
+        L.orc_markstein_f32_mismatches.argtypes = [ctypes.c_long, ctypes.c_uint64, ctypes.c_int]
         L.orc_ucb_table.restype = ctypes.c_double
         L.orc_ucb_table.argtypes = [ctypes.c_int]
         L.orc_hanoi_solver.restype = ctypes.c_long
